@@ -14,7 +14,9 @@ thread: one slice's pair-HMM passes fill the CUs another slice's chain kernel le
 of the shard.  There is no barrier between steps inside the timed region (slice i of step s+1 starts when slice i of
 step s has been fetched); the region is bracketed by barrier + torch.cuda.synchronize() on both sides.
 
-Prints ONE JSON line on rank 0.  DESIGN.md "Measurement" says how each field is obtained.
+Prints ONE JSON line on rank 0.  DESIGN.md "Measurement" says how each field is obtained.  A plain run sets up, warms up, times
+`--steps` steps and prints the line (`--dump-outputs DIR`: and writes the last timed step's outputs); `--full` adds every other
+measurement (serial pass, roofline detail, 8-GPU projection, one-shot and stage calls, CPU baseline, oracle parity samples).
 """
 import argparse
 import hashlib
@@ -26,10 +28,12 @@ import threading
 import time
 from concurrent.futures import ThreadPoolExecutor
 
-import numpy as np
+T_START = time.perf_counter()   # the line's startup_s: from here (before numpy and torch load) to the first warm-up step
+
+import numpy as np  # noqa: E402
 # torch first: it bundles its own libamdhip64.so.7 / libhsa-runtime64.so.1 (same sonames as /opt/rocm), and the
 # process must end up with ONE HIP runtime; libjtk_lc.so then binds to the already loaded one.
-import torch
+import torch  # noqa: E402
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -57,8 +61,9 @@ KERNELS_OF_FAMILY = {
 }
 
 
-def make_batch_parallel(config, chunk_ids, threads=8):
+def make_batch_parallel(config, chunk_ids, threads=None):
     cfg = dict(synth.CONFIGS[config])
+    threads = threads or synth_threads()
     with ThreadPoolExecutor(max_workers=threads) as ex:   # ctypes releases the GIL inside jtk_synth_pileup
         pile = list(ex.map(lambda c: synth.make_pileup(int(c), cfg), chunk_ids))
     return jb.pack(pile), cfg
@@ -87,6 +92,66 @@ def usable_cpus():
         except (OSError, ValueError, IndexError):
             continue
     return n, quota
+
+
+def synth_threads():
+    """host threads for the synthetic inputs (every pile-up is seeded by its chunk id: the same batch for any count): the CPUs
+    this process may use (affinity mask, cgroup quota, OMP_NUM_THREADS) shared by the ranks on this node, at least 8"""
+    n_aff, quota = usable_cpus()
+    n = n_aff if quota is None else max(1, min(n_aff, int(quota + 0.5)))
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return max(8, n // max(1, int(os.environ.get("LOCAL_WORLD_SIZE", "1"))))
+
+
+# what --dump-outputs may write in all, and the elements of each ragged output (consensus, re-threaded ops) kept in its sample
+DUMP_BYTES_MAX = 64 << 20
+DUMP_RAGGED_MAX = 4 << 20
+
+
+def ragged_sample(n_seg, est_len, cap=DUMP_RAGGED_MAX, seed=20260101):
+    """a fixed, seeded choice of segments (chunks or reads) whose estimated lengths -- from the INPUTS, so that two builds pick
+    the same ones -- add up to at most `cap`: all of them when they fit"""
+    est = np.asarray(est_len, dtype=np.float64)
+    if est.sum() <= cap:
+        return np.arange(n_seg, dtype=np.int64)
+    order = np.random.default_rng(seed).permutation(n_seg)
+    keep = order[np.cumsum(est[order]) <= cap]
+    return np.sort(keep).astype(np.int64)
+
+
+def dump_outputs(path, batch, merged, pieces):
+    """--dump-outputs: what the timed path handed its caller in its last step, as <path>/<name>.npy in float64 (float32 for the
+    sampled bases / ops).  merged = label / log_post / result of the whole shard; pieces = [(output dict of a slice, first chunk,
+    first read)] for the consensus and re-threaded ops (empty with --fetch results)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = dict(label=merged["label"].astype(np.float64), log_post=merged["log_post"].astype(np.float64))
+    for f in merged["result"].dtype.names:
+        arrays["result_" + f] = merged["result"][f].astype(np.float64)
+    if pieces:
+        cons, ops = {}, {}
+        for o, c0, r0 in pieces:
+            co, oo = o["cons_off"].astype(np.int64), o["ops_out_off"].astype(np.int64)
+            for c in range(len(co) - 1):
+                cons[c0 + c] = o["cons"][co[c]:co[c + 1]]
+            for r in range(len(oo) - 1):
+                ops[r0 + r] = o["ops_out"][oo[r]:oo[r + 1]]
+        arrays["cons_len"] = np.array([len(cons[c]) for c in range(batch.n_chunks)], dtype=np.float64)
+        arrays["ops_len"] = np.array([len(ops[r]) for r in range(batch.n_reads)], dtype=np.float64)
+        # (estimates: a consensus is about as long as its template, a read's re-threaded ops as its input ops, + 25 %)
+        pick_c = ragged_sample(batch.n_chunks, batch.chunks["tmpl_len"].astype(np.float64) * 1.25)
+        pick_r = ragged_sample(batch.n_reads, np.diff(batch.ops_off.astype(np.int64)) * 1.25)
+        arrays["cons_sample_chunks"] = pick_c.astype(np.float64)
+        arrays["cons_sample"] = np.concatenate([cons[c] for c in pick_c] or [np.zeros(0, np.uint8)]).astype(np.float32)
+        arrays["ops_sample_reads"] = pick_r.astype(np.float64)
+        arrays["ops_sample"] = np.concatenate([ops[r] for r in pick_r] or [np.zeros(0, np.uint8)]).astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES_MAX:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total / 2**20:.1f} MiB (limit {DUMP_BYTES_MAX >> 20} MiB)")
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return total
 
 
 def cpu_baseline(params, batch, budget_s=100.0):
@@ -278,7 +343,18 @@ def main():
                          "output SURVEY 8(d)'s byte formula counts; default since round 6), results = without consensus / ops")
     ap.add_argument("--dump-labels", default="", help="rank 0 writes the whole job's labels, cluster numbers and scores in chunk-id "
                                                       "order to this .npz (tests compare an N-rank run with the 1-rank run)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the timed path returned in its last step to DIR/<name>.npy (float64; a fixed, seeded "
+                         "sample of the consensus and re-threaded ops as float32), at most 64 MiB: labels, posteriors, per-chunk "
+                         "records (result_*), consensus / ops lengths and the sample with the chunk / read ids it holds")
+    ap.add_argument("--full", action="store_true",
+                    help="also take everything beside the headline figure: the first call of a fresh process, the serial pass and "
+                         "the roofline / secondary bounds built on it, the 8-GPU shard projection, the one-shot and stage calls, the "
+                         "CPU baseline and the oracle parity samples (each still switched off by its --no-* option; --weak-probe "
+                         "needs it too)")
     args = ap.parse_args()
+    if args.weak_probe and not args.full:
+        ap.error("--weak-probe is one of the --full measurements: give --full with it")
     # the bench process owns its GPU: let the library keep the workspaces of a finished one-shot call for the next one
     # (default 32 GB so that it cannot starve other users of the device in a shared process; a 2500-chunk call needs ~95 GB)
     os.environ.setdefault("JTK_LC_POOL_GB", "160")
@@ -292,7 +368,7 @@ def main():
     # What the FIRST stage call of a fresh process costs (device workspaces are mapped for the first time: the pipeline's
     # situation), measured where the driver can see it: a child process, run to completion before this one touches the GPU.
     fresh = None
-    if args.gpus == 1 and "WORLD_SIZE" not in os.environ and not args.no_e2e and os.path.exists(ffi.LIB_PATH):
+    if args.full and args.gpus == 1 and "WORLD_SIZE" not in os.environ and not args.no_e2e and os.path.exists(ffi.LIB_PATH):
         import subprocess
         wl0 = WORKLOADS[args.workload]
         try:
@@ -388,6 +464,7 @@ def main():
         def one_step():
             r = api.cluster_chunks(params, batch, device=local_rank)
             return r, api.last_timing()
+        t_warm = time.perf_counter()
         for _ in range(args.warmup):
             one_step()
         barrier()
@@ -401,6 +478,8 @@ def main():
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             elapsed = float(tt.item())
         value = n_total * args.steps / elapsed
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, batch, out, [(out, 0, 0)] if "cons_off" in out else [])
         alg = batch.algorithmic_bytes(k_per_chunk=out["result"]["cluster_num"]) / max(1, batch.n_chunks)
         achieved = value * alg / 1e9
         km = tm["kernel_ms"]
@@ -409,6 +488,7 @@ def main():
                 metric="chunks clustered/sec (whole node), 60x ONT 2kbp chunks", value=value, unit="chunks/s", n_gpus=world,
                 steps=args.steps, warmup=args.warmup, ms_per_step=elapsed / args.steps * 1e3, higher_is_better=True,
                 scaling=args.scaling, vs_baseline=None, dtype="f64", data="synthetic",
+                startup_s=t_warm - T_START, warmup_s=t0 - t_warm,
                 config=dict(workload=args.workload, chunks_total=int(n_total), chunks_this_rank=int(batch.n_chunks),
                             reads_per_chunk=int(reads_per_chunk), chunk_len=int(cfg["tmpl_len"]), copy_num=int(cfg["copy_num"]),
                             band_frac=cfg["band_frac"], sharding="1 gpu" if world == 1 else f"{args.scaling}: LPT over {world} ranks",
@@ -440,7 +520,7 @@ def main():
                                        device=torch.device("cuda", local_rank) if backend == "nccl" else None)
     ktime = {n: 0.0 for n in ffi.KERNEL_NAMES}
     klaunch = {n: 0 for n in ffi.KERNEL_NAMES}
-    state = dict(dev_ms=0.0, gathered=None, last=None)
+    state = dict(dev_ms=0.0, gathered=None, last=None, steps_done=0)
     fetch_bufs = [None] * n_streams   # a slice's output arrays, allocated by its first fetch and overwritten by the later ones
 
     def run_steps(n_steps, timed, serial=False):
@@ -486,6 +566,7 @@ def main():
             if len(pending[s]) == n_streams:             # step s is complete on this rank
                 outs = [pending[s][j] for j in range(n_streams)]
                 del pending[s]
+                state["steps_done"] += int(timed)
                 merged = dict(label=np.concatenate([o["label"] for o in outs]),
                               log_post=np.concatenate([o["log_post"] for o in outs]),
                               result=np.concatenate([o["result"] for o in outs]),
@@ -497,6 +578,7 @@ def main():
         for th in threads:
             th.join()
 
+    t_warm = time.perf_counter()
     for _ in range(args.warmup):
         run_steps(1, timed=False)
     barrier()
@@ -513,6 +595,64 @@ def main():
     ok = int((out["result"]["status"] == 0).sum())
     overl_k = {n: ktime[n] / args.steps for n in ffi.KERNEL_NAMES}
     overl_slice_ms = state["dev_ms"] / (args.steps * n_streams)
+    if args.dump_outputs and rank == 0:   # (before anything else runs the sessions: fetch_bufs hold the last timed step)
+        dump_outputs(args.dump_outputs, batch, out, [(fetch_bufs[i], bounds[i], int(read_bounds[i])) for i in range(n_streams)]
+                     if args.fetch == "all" else [])
+    alg_bytes_shard = batch.algorithmic_bytes(k_per_chunk=out["result"]["cluster_num"])
+    alg_bytes_per_chunk = alg_bytes_shard / max(1, batch.n_chunks)
+    achieved = value * alg_bytes_per_chunk / 1e9
+    line = dict(metric="chunks clustered/sec (whole node), 60x ONT 2kbp chunks", value=value, unit="chunks/s",
+                n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=elapsed / args.steps * 1e3,
+                higher_is_better=True, scaling=args.scaling, vs_baseline=None, dtype="f64", data="synthetic",
+                config=dict(workload=args.workload, chunks_total=int(n_total), chunks_this_rank=int(batch.n_chunks),
+                            reads_per_chunk=int(reads_per_chunk), chunk_len=int(cfg["tmpl_len"]),
+                            copy_num=int(cfg["copy_num"]), band_frac=cfg["band_frac"],
+                            sharding=(f"{args.scaling}: chunks dealt LPT to {world} ranks, one all-gather of "
+                                      "(label, log_post, k, score) per step over RCCL") if world > 1 else "1 gpu",
+                            slices_in_flight=n_streams,
+                            step=("one pass over the dataset incl. the copy of EVERY output to the host: labels, posteriors, k, score, "
+                                  "consensus and re-threaded ops" if args.fetch == "all" else
+                                  "one pass over the dataset incl. fetch of labels, posteriors, k, score (no consensus / ops)"),
+                            fetched_bytes_per_step=dict(consensus=int(out.get("cons_bytes", 0)), ops=int(out.get("ops_bytes", 0)),
+                                                        labels=int(out["label"].nbytes), log_post=int(out["log_post"].nbytes))),
+                slice_pass_latency_ms=overl_slice_ms, chunks_ok=ok, lib_sha16=sha,
+                mean_polish_rounds=float(out["result"]["polish_rounds"].mean()),
+                mean_cluster_num=float(out["result"]["cluster_num"].mean()),
+                # what the timed region ran: the passes completed in it (all slices) and the kernel launches they made
+                timed_steps=state["steps_done"], timed_kernel_launches=dict(klaunch),
+                startup_s=t_warm - T_START, warmup_s=t0 - t_warm)
+    if gather is not None and rank == 0:
+        g = state["gathered"]
+        line["gathered_reads"] = int(sum(len(x["label"]) for x in g))
+        line["gather_ok"] = bool(np.array_equal(g[0]["label"], out["label"]))
+    if args.dump_labels and rank == 0:
+        # the whole job in chunk-id order: rank r's chunks are parts[r] (ascending), reads_per_chunk reads each
+        per_rank = state["gathered"] if gather is not None else [dict(label=out["label"], cluster_num=out["result"]["cluster_num"],
+                                                                      score=out["result"]["score"])]
+        lab = np.zeros(n_total * reads_per_chunk, dtype=np.uint32)
+        kk = np.zeros(n_total, dtype=np.uint32)
+        sc = np.zeros(n_total, dtype=np.float64)
+        for r, g in enumerate(per_rank):
+            ids = np.asarray(parts[r] if args.scaling == "strong" else list(parts[r]), dtype=np.int64)
+            lab.reshape(n_total, reads_per_chunk)[ids] = g["label"].reshape(len(ids), reads_per_chunk)
+            kk[ids] = g["cluster_num"]
+            sc[ids] = g["score"]
+        np.savez(args.dump_labels, label=lab, cluster_num=kk, score=sc)
+    if not args.full:
+        # ---- a plain run ends here: the headline figure and what the timed steps themselves measured
+        line["roofline"] = dict(bound="hbm", achieved=achieved, peak=HBM_PEAK_GBPS * world, unit="GB/s",
+                                frac=achieved / (HBM_PEAK_GBPS * world), algorithmic_bytes_per_chunk=alg_bytes_per_chunk,
+                                overlapped_kernel_ms_per_step=overl_k,
+                                note="achieved = value x algorithmic bytes per chunk (SURVEY.md 8d), frac = achieved / (8 TB/s x "
+                                     "n_gpus); the serial pass, measured traffic and secondary bounds come with --full")
+        for s_ in sessions:
+            s_.close()
+        if rank == 0:
+            print(json.dumps(line))
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- a serial pass (slices one after another, nothing overlapped): per-kernel device time that adds up
     for n in ffi.KERNEL_NAMES:
@@ -544,9 +684,6 @@ def main():
         dist.all_gather_object(per_rank_profiles, my_profile)
 
     # ---- roofline: achieved = chunks/s (whole job) x algorithmic bytes per chunk; frac against 8 TB/s per GPU
-    alg_bytes_shard = batch.algorithmic_bytes(k_per_chunk=out["result"]["cluster_num"])
-    alg_bytes_per_chunk = alg_bytes_shard / max(1, batch.n_chunks)
-    achieved = value * alg_bytes_per_chunk / 1e9
     dom = max(serial_k, key=lambda n: serial_k[n])
     traffic, traffic_note = pmc_traffic(args.workload, sha)
     # secondary bounds: f64 rate of the banded pair-HMM and the chain's cycles per proposal
@@ -626,43 +763,8 @@ def main():
                          "limits are the `secondary` ones.  traffic = PMC-measured HBM bytes per launch of the dominant "
                          "kernel family, only when the committed profile was taken on this exact library build")
 
-    line = dict(metric="chunks clustered/sec (whole node), 60x ONT 2kbp chunks", value=value, unit="chunks/s",
-                n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=elapsed / args.steps * 1e3,
-                higher_is_better=True, scaling=args.scaling, vs_baseline=None, dtype="f64", data="synthetic",
-                config=dict(workload=args.workload, chunks_total=int(n_total), chunks_this_rank=int(batch.n_chunks),
-                            reads_per_chunk=int(reads_per_chunk), chunk_len=int(cfg["tmpl_len"]),
-                            copy_num=int(cfg["copy_num"]), band_frac=cfg["band_frac"],
-                            sharding=(f"{args.scaling}: chunks dealt LPT to {world} ranks, one all-gather of "
-                                      "(label, log_post, k, score) per step over RCCL") if world > 1 else "1 gpu",
-                            slices_in_flight=n_streams,
-                            step=("one pass over the dataset incl. the copy of EVERY output to the host: labels, posteriors, k, score, "
-                                  "consensus and re-threaded ops" if args.fetch == "all" else
-                                  "one pass over the dataset incl. fetch of labels, posteriors, k, score (no consensus / ops)"),
-                            fetched_bytes_per_step=dict(consensus=int(out.get("cons_bytes", 0)), ops=int(out.get("ops_bytes", 0)),
-                                                        labels=int(out["label"].nbytes), log_post=int(out["log_post"].nbytes))),
-                roofline=roofline, slice_pass_latency_ms=overl_slice_ms,
-                serial_step_agrees=steps_agree, chunks_ok=ok, lib_sha16=sha,
-                mean_polish_rounds=float(out["result"]["polish_rounds"].mean()),
-                mean_cluster_num=float(out["result"]["cluster_num"].mean()))
+    line.update(roofline=roofline, serial_step_agrees=steps_agree)
     line["per_rank"] = per_rank_profiles   # (N > 1: every rank's serial-pass breakdown and its slowest chain)
-    if gather is not None and rank == 0:
-        g = state["gathered"]
-        line["gathered_reads"] = int(sum(len(x["label"]) for x in g))
-        line["gather_ok"] = bool(np.array_equal(g[0]["label"], out["label"]))
-    if args.dump_labels and rank == 0:
-        # the whole job in chunk-id order: rank r's chunks are parts[r] (ascending), reads_per_chunk reads each
-        per_rank = state["gathered"] if gather is not None else [dict(label=out["label"], cluster_num=out["result"]["cluster_num"],
-                                                                      score=out["result"]["score"])]
-        lab = np.zeros(n_total * reads_per_chunk, dtype=np.uint32)
-        kk = np.zeros(n_total, dtype=np.uint32)
-        sc = np.zeros(n_total, dtype=np.float64)
-        for r, g in enumerate(per_rank):
-            ids = np.asarray(parts[r] if args.scaling == "strong" else list(parts[r]), dtype=np.int64)
-            lab.reshape(n_total, reads_per_chunk)[ids] = g["label"].reshape(len(ids), reads_per_chunk)
-            kk[ids] = g["cluster_num"]
-            sc[ids] = g["score"]
-        np.savez(args.dump_labels, label=lab, cluster_num=kk, score=sc)
-
     for s in sessions:
         s.close()
     # ---- N > 1: the weak-scaling figure next to the strong one.  Strong scaling of the fixed 2,500-chunk data set ends on each

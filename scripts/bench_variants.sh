@@ -2,6 +2,7 @@
 # Diagnostic (GPU box): the default bench line for builds of the library with extra compile flags, beside the product.
 # usage: bench_variants.sh "name1:-DFLAG ..." "name2:@prebuilt.so" "name3:"   (an empty flag list = the product library itself)
 set -u
+EXTRA="--full ${EXTRA:-}"   # the line it prints reads the serial pass, stage_e2e and the 8-GPU projection
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 mkdir -p gpurun_out
 for spec in "$@"; do

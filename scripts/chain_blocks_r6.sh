@@ -14,7 +14,7 @@ sp=d['roofline']['serial_pass']['kernel_ms']
 pr=d['per_rank'][0]
 print('value %.1f ms_per_step %.1f serial %s slowest chain %.1f median %.1f' % (d['value'], d['ms_per_step'], {k:round(v,1) for k,v in sp.items()}, pr['slowest_chunk_chain_ms'] or 0, pr['median_chain_ms'] or 0))
 "; }
-B="--steps 8 --warmup 2 --no-cpu-baseline --no-shard8 --no-e2e"
+B="--full --steps 8 --warmup 2 --no-cpu-baseline --no-shard8 --no-e2e"
 echo "-- cfg3: $(timeout 600 python3 bench.py $B 2>/dev/null | short)" | tee -a $OUT
 echo "-- cfg2: $(timeout 600 python3 bench.py --workload cfg2_ont_diploid_500x60x2kbp $B 2>/dev/null | short)" | tee -a $OUT
 echo "-- cfg5: $(timeout 600 python3 bench.py --workload cfg5_hifi_diploid_2500x40x2kbp $B 2>/dev/null | short)" | tee -a $OUT

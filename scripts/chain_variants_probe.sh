@@ -10,8 +10,8 @@ line() { python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('$1'
 for rep in 1 2; do
   echo "== poisson, light <= 127 reads"; timeout 300 python3 scripts/poisson_coverage_bench.py 500 | tail -1
   echo "== poisson, light <= 63 reads";  JTK_LC_LIB=$L63 timeout 300 python3 scripts/poisson_coverage_bench.py 500 | tail -1
-  timeout 300 python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-e2e --no-shard8 | line "headline side-stream"
-  JTK_MCMC_SIDE=0 timeout 300 python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-e2e --no-shard8 | line "headline one-stream "
-  JTK_LC_LIB=$L63 timeout 300 python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-e2e --no-shard8 | line "headline light63   "
-  JTK_STRIPE_SHARED=0 timeout 300 python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-e2e --no-shard8 | line "headline own stripes"
+  timeout 300 python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-e2e --no-shard8 | line "headline side-stream"
+  JTK_MCMC_SIDE=0 timeout 300 python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-e2e --no-shard8 | line "headline one-stream "
+  JTK_LC_LIB=$L63 timeout 300 python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-e2e --no-shard8 | line "headline light63   "
+  JTK_STRIPE_SHARED=0 timeout 300 python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-e2e --no-shard8 | line "headline own stripes"
 done

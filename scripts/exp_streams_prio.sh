@@ -4,7 +4,7 @@
 set -u
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 O=gpurun_out
-COMMON="--no-cpu-baseline --no-e2e --no-shard8"
+COMMON="--full --no-cpu-baseline --no-e2e --no-shard8"
 run() {  # name lib workload streams steps
   local name=$1 lib=$2 wl=$3 st=$4 steps=$5
   if [ -n "$lib" ]; then export JTK_LC_LIB=$PWD/jtk_amd/_build/exp_$lib/libjtk_lc_$lib.so; else unset JTK_LC_LIB; fi

@@ -14,12 +14,12 @@ fi
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 # the bench lines below carry roofline.traffic from THIS profile (bench.py matches it by the hash of the kernel sources)
 [ -s $O/prof_traffic_$TAG.json ] && cp $O/prof_traffic_$TAG.json profiles/${TAG}_pmc_traffic.json
-# (the default line first: it is the one the driver repeats; the other configurations after it)
-timeout 1200 python3 bench.py --steps 20 --warmup 5 > $O/bench_${TAG}_final.json 2> $O/bench_${TAG}_final.err   # the driver's command
+# (the headline configuration first, with every measurement beside the headline figure; the other configurations after it)
+timeout 1200 python3 bench.py --full --steps 20 --warmup 5 > $O/bench_${TAG}_final.json 2> $O/bench_${TAG}_final.err   # the driver's step count, --full
 # (cfg 4 WITH its cpu_baseline rung: the oracle on the first chunks of the same workload, a few minutes of host time)
-timeout 2700 python3 bench.py --workload cfg4_ont_4copy_2500x160x2kbp --steps 1 --warmup 0 --no-e2e --no-shard8 > $O/bench_${TAG}_cfg4_2500.json 2> $O/bench_${TAG}_cfg4_2500.err
-timeout 600 python3 bench.py --workload cfg5_hifi_diploid_2500x40x2kbp --steps 8 --warmup 2 --no-e2e --no-cpu-baseline --no-shard8 > $O/bench_${TAG}_cfg5.json 2> $O/bench_${TAG}_cfg5.err
-timeout 600 python3 bench.py --workload cfg2_ont_diploid_500x60x2kbp --steps 8 --warmup 2 --no-e2e --no-cpu-baseline --no-shard8 > $O/bench_${TAG}_cfg2.json 2> $O/bench_${TAG}_cfg2.err
+timeout 2700 python3 bench.py --full --workload cfg4_ont_4copy_2500x160x2kbp --steps 1 --warmup 0 --no-e2e --no-shard8 > $O/bench_${TAG}_cfg4_2500.json 2> $O/bench_${TAG}_cfg4_2500.err
+timeout 600 python3 bench.py --full --workload cfg5_hifi_diploid_2500x40x2kbp --steps 8 --warmup 2 --no-e2e --no-cpu-baseline --no-shard8 > $O/bench_${TAG}_cfg5.json 2> $O/bench_${TAG}_cfg5.err
+timeout 600 python3 bench.py --full --workload cfg2_ont_diploid_500x60x2kbp --steps 8 --warmup 2 --no-e2e --no-cpu-baseline --no-shard8 > $O/bench_${TAG}_cfg2.json 2> $O/bench_${TAG}_cfg2.err
 timeout 600 python3 scripts/poisson_coverage_bench.py 500 > $O/poisson_$TAG.log 2>&1
 # One library, one set of numbers: a bench line whose lib_sha16 is not the hash of the library the committed rocprof / PMC profile was
 # taken on (gpurun_out/prof_libsha_$TAG.txt, written by profile_bench.sh) is set aside as .STALE -- it must not reach profiles/.
@@ -45,7 +45,7 @@ for f in ("cfg4_2500", "cfg5", "cfg2", "final"):
         print(f"final_round: {path} lib_sha16 {got} == profile's")
 PY
 # summary: the last line of every bench file that survived the check (a file set aside as .STALE is named, not parsed); the script
-# FAILS when the default line -- the one the driver repeats -- is not there
+# FAILS when the headline configuration's line is not there
 python3 - "$TAG" <<'PY'
 import json, os, sys
 tag = sys.argv[1]

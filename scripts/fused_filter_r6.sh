@@ -13,7 +13,7 @@ d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 sp=d['roofline']['serial_pass']['kernel_ms']
 print('value %.1f ms_per_step %.1f serial %s' % (d['value'], d['ms_per_step'], {k:round(v,1) for k,v in sp.items()}))
 "; }
-B="--steps 10 --warmup 2 --no-cpu-baseline --no-shard8 --no-e2e"
+B="--full --steps 10 --warmup 2 --no-cpu-baseline --no-shard8 --no-e2e"
 echo "-- fused:   $(timeout 600 python3 bench.py $B 2>/dev/null | short)" | tee -a $OUT
 echo "-- unfused: $(JTK_FILTER_FUSED=0 timeout 600 python3 bench.py $B 2>/dev/null | short)" | tee -a $OUT
 echo "-- fused:   $(timeout 600 python3 bench.py $B 2>/dev/null | short)" | tee -a $OUT

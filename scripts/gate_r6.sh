@@ -17,8 +17,8 @@ for cfg in "6 0" "6 2" "6 3" "6 4" "8 3" "12 3" "12 4" "6 1"; do
   echo "-- streams $1 gate slots $2: $(JTK_LC_PHASE_SLOTS=$2 timeout 600 python3 bench.py --steps 12 --warmup 2 --streams $1 --no-cpu-baseline --no-shard8 --no-e2e 2>/dev/null | short)" | tee -a $OUT
 done
 for g in 0 2 3; do
-echo "-- one-shot call, gate slots $g: $(JTK_LC_PHASE_SLOTS=$g timeout 600 python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-shard8 2>/dev/null | short)" | tee -a $OUT
+echo "-- one-shot call, gate slots $g: $(JTK_LC_PHASE_SLOTS=$g timeout 600 python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-shard8 2>/dev/null | short)" | tee -a $OUT
 done
 for sl in 6 8; do
-echo "-- one-shot call, $sl slices, gate slots 3: $(JTK_LC_SLICES=$sl JTK_LC_PHASE_SLOTS=3 timeout 600 python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-shard8 2>/dev/null | short)" | tee -a $OUT
+echo "-- one-shot call, $sl slices, gate slots 3: $(JTK_LC_SLICES=$sl JTK_LC_PHASE_SLOTS=3 timeout 600 python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-shard8 2>/dev/null | short)" | tee -a $OUT
 done

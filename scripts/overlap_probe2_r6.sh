@@ -10,7 +10,7 @@ OUT=gpurun_out/overlap_probe2_r6.txt
 echo "== $(date -u +%FT%TZ)" >> $OUT
 echo "-- parity" | tee -a $OUT
 timeout 1200 python3 -m pytest tests/test_golden.py tests/test_gpu_parity.py tests/test_gpu_defining_shapes.py -x -q -m gpu -k "not large_pileups and not beyond_1023 and not recursive_split" 2>&1 | tail -3 | tee -a $OUT
-B="python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-shard8 --no-e2e"
+B="python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-shard8 --no-e2e"
 short() { python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
@@ -26,7 +26,7 @@ for w in 11 10 8; do echo "-- phmm waves per CU $w: $(JTK_PHMM_WAVES_PER_CU=$w t
 echo "-- general chain kernel on the main stream: $(JTK_MCMC_SIDE=0 timeout 600 $B 2>/dev/null | short)" | tee -a $OUT
 for n in 64 96 128; do echo "-- chain on $n CUs (spread): $(GPU_MAX_HW_QUEUES=24 JTK_CHAIN_CUS=$n timeout 600 $B 2>/dev/null | short)" | tee -a $OUT; done
 echo "-- chain on the first 64 CUs: $(GPU_MAX_HW_QUEUES=24 JTK_CHAIN_CUS=64 JTK_CHAIN_CUS_SPREAD=0 timeout 600 $B 2>/dev/null | short)" | tee -a $OUT
-echo "-- e2e: $(timeout 900 python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-shard8 2>/dev/null | python3 -c "
+echo "-- e2e: $(timeout 900 python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-shard8 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print({k:(round(v,3) if isinstance(v,float) else v) for k,v in (d.get('e2e') or {}).items() if k in ('chunks_per_s','seconds','first_call_seconds','h2d_ms','d2h_ms','matches_resident')})

@@ -11,7 +11,7 @@ echo "== $(date -u +%FT%TZ)" >> $OUT
 timeout 120 scripts/bin/pcie_probe 2>&1 | tee -a $OUT
 echo "-- parity" | tee -a $OUT
 timeout 900 python3 -m pytest tests/test_golden.py tests/test_gpu_parity.py -x -q -m gpu -k "not large_pileups and not beyond_1023 and not recursive_split" 2>&1 | tail -3 | tee -a $OUT
-B="python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-shard8"
+B="python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-shard8"
 short() { python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])

@@ -15,7 +15,7 @@ d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 sp=d['roofline']['serial_pass']['kernel_ms']
 print('value %.1f ms_per_step %.1f serial %s' % (d['value'], d['ms_per_step'], {k:round(v,1) for k,v in sp.items()}))
 "; }
-B="--steps 10 --warmup 2 --no-cpu-baseline --no-shard8 --no-e2e"
+B="--full --steps 10 --warmup 2 --no-cpu-baseline --no-shard8 --no-e2e"
 echo "-- cfg3: $(timeout 600 python3 bench.py $B 2>/dev/null | short)" | tee -a $OUT
 echo "-- cfg2: $(timeout 600 python3 bench.py --workload cfg2_ont_diploid_500x60x2kbp $B 2>/dev/null | short)" | tee -a $OUT
 echo "-- cfg5: $(timeout 600 python3 bench.py --workload cfg5_hifi_diploid_2500x40x2kbp $B 2>/dev/null | short)" | tee -a $OUT

@@ -12,5 +12,5 @@ for l in sys.stdin:
 for spec in "$@"; do
   set -- $spec
   lib=$1; shift
-  env JTK_LC_LIB=$PWD/jtk_amd/_build/$lib "$@" python bench.py --no-cpu-baseline --no-e2e --steps 6 2>/dev/null | show "$lib $*"
+  env JTK_LC_LIB=$PWD/jtk_amd/_build/$lib "$@" python bench.py --full --no-cpu-baseline --no-e2e --steps 6 2>/dev/null | show "$lib $*"
 done

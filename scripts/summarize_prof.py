@@ -31,10 +31,12 @@ def main(root, tag):
     m = re.search(r"--workload (\S+)", cmd)
     if m:
         workload = m.group(1)
-    # passes of the workload in the profiled command: warm-up + timed steps + the one serial pass after them
+    # passes of the workload in the profiled command: warm-up + timed steps (+ with --full the one serial pass after them)
     ms, mw = re.search(r"--steps (\d+)", cmd), re.search(r"--warmup (\d+)", cmd)
-    n_passes = (int(ms.group(1)) if ms else 6) + (int(mw.group(1)) if mw else 1) + 1
-    clean = "--no-shard8" in cmd  # otherwise the launches of the 313-chunk shard runs are in the sums too
+    full = re.search(r"(^|\s)--full(\s|$)", cmd) is not None
+    n_passes = (int(ms.group(1)) if ms else 10) + (int(mw.group(1)) if mw else 3) + (1 if full else 0)
+    # a --full run without --no-shard8 also runs the 313-chunk shards: their launches would be in the sums too
+    clean = "--no-shard8" in cmd or not full
     out = [f"== rocprofv3 --kernel-trace --stats -- {cmd} ==", f"(library sha256[:16] {sha}; kernel sources {jbuild.source_sha16()}; workload {workload})",
            f"{'kernel':28s} {'calls':>6s} {'total_ms':>12s} {'avg_ms':>12s} {'pct':>7s}"]
     pmc = {}

@@ -1,4 +1,6 @@
-"""bench.py's contract on a small dataset: the one-rank line carries every field the driver reads, and the N > 1 path
+"""bench.py's contract on a small dataset: the one-rank line carries every field the driver reads (--full: every measurement
+beside the headline; a plain run: the headline alone, --steps timed passes, dumped outputs that do not change between runs),
+and the N > 1 path
 (strong scaling, LPT shards, one result all-gather per step) runs as two gloo ranks sharing GPU 0
 (JTK_BENCH_BACKEND=gloo; the real launch uses RCCL with one rank per GPU)."""
 import json
@@ -43,7 +45,7 @@ def run_bounded(cmd, env, timeout):
 def test_one_rank_line_has_the_contract_fields(jtk_lib):
     assert jtk_lib.jtk_lc_device_ok(0) == 1
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--chunks", "32", "--steps", "2", "--warmup", "1",
-                        "--streams", "2"], capture_output=True, text=True, cwd=ROOT, timeout=1200)
+                        "--streams", "2", "--full"], capture_output=True, text=True, cwd=ROOT, timeout=1200)
     assert r.returncode == 0, r.stderr[-2000:]
     line = last_json(r.stdout)
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -74,6 +76,51 @@ def test_one_rank_line_has_the_contract_fields(jtk_lib):
     assert line["per_rank"][0]["rank"] == 0 and line["per_rank"][0]["chunks"] == 32
 
 
+def test_plain_run_is_lean_and_dumps_the_same_outputs_every_run(jtk_lib, tmp_path):
+    """a plain run: the headline fields only (no serial pass, no CPU baseline); --steps sets how many passes the timed region
+    runs (the kernel launches it counts scale with it); --dump-outputs writes the last step's outputs, which do not depend on
+    how many steps came before"""
+    assert jtk_lib.jtk_lc_device_ok(0) == 1
+    lines = {}
+    for steps in (3, 2):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--chunks", "32", "--steps", str(steps), "--warmup", "1",
+                            "--streams", "2", "--dump-outputs", str(tmp_path / str(steps))], capture_output=True, text=True, cwd=ROOT,
+                           timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines[steps] = last_json(r.stdout)
+    line = lines[3]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline", "config", "startup_s"):
+        assert key in line, key
+    for key in ("cpu_baseline", "e2e", "stage_e2e", "shard8_projection", "per_rank", "serial_step_agrees"):
+        assert key not in line, key
+    assert line["chunks_ok"] == 32 and line["dtype"] == "f64" and line["higher_is_better"] is True
+    assert abs(line["value"] - 32 * 3 / (line["ms_per_step"] * 3e-3)) < 1e-6 * line["value"]
+    # the timed region ran exactly --steps passes: counted as they complete, and the launches they made are 3 : 2
+    assert lines[3]["timed_steps"] == 3 and lines[2]["timed_steps"] == 2
+    la, lb = lines[3]["timed_kernel_launches"], lines[2]["timed_kernel_launches"]
+    assert set(la) == set(lb) and la["phmm"] > 0 and la["mcmc"] > 0
+    for fam in la:
+        assert 2 * la[fam] == 3 * lb[fam], (fam, la, lb)
+    import numpy as np
+    names = sorted(os.listdir(tmp_path / "3"))
+    assert names == sorted(os.listdir(tmp_path / "2"))
+    assert {"label.npy", "log_post.npy", "result_score.npy", "result_cluster_num.npy", "cons_sample.npy", "ops_sample.npy"} <= set(names)
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "3" / n), np.load(tmp_path / "2" / n)
+        assert a.dtype in (np.float32, np.float64) and a.dtype == b.dtype and a.shape == b.shape, n
+        assert np.array_equal(a.view(np.uint8), b.view(np.uint8)), n
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert len(np.load(tmp_path / "3" / "label.npy")) == 32 * 60
+
+
+def test_weak_probe_needs_full():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--weak-probe"], capture_output=True, text=True, cwd=ROOT,
+                       timeout=300)
+    assert r.returncode == 2 and "--full" in r.stderr
+
+
 def test_two_rank_strong_scaling_path(jtk_lib):
     """`python3 bench.py --gpus 2` AS TYPED -- no launcher around it (the driver's N > 1 command has none either): bench.py
     starts its own ranks as child processes and relays rank 0's line and the exit code."""
@@ -82,7 +129,7 @@ def test_two_rank_strong_scaling_path(jtk_lib):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"),
                         "--gpus", "2", "--chunks", "24", "--steps", "2", "--warmup", "1", "--streams", "2", "--no-e2e",
-                        "--weak-probe"],
+                        "--weak-probe", "--full"],
                        capture_output=True, text=True, cwd=ROOT, env=env, timeout=1200)
     assert r.returncode == 0, r.stderr[-3000:]
     line = last_json(r.stdout)

@@ -136,12 +136,15 @@ def test_synthetic_dataset_has_exactly_the_reference_fields():
     assert set(ds["model_param"]["forward"]) == set(D.SCHEMA["HMMParam"])
     assert set(ds["processed_stages"][0]) == set(D.SCHEMA["ProcessedStage"])
     assert set(ds["masked_kmers"]) == set(D.SCHEMA["MaskInfo"])
-    # the derive field lists themselves, against the reference source when it is there (not on the GPU box)
-    ref = "/root/reference/definitions/src/lib.rs"
-    if os.path.exists(ref):
+    # the derive field lists themselves: tests/golden/reference_schema.json holds those of definitions/src/lib.rs, struct by
+    # struct in declaration order; with JTK_REFERENCE_CHECKOUT naming a ban-m/jtk checkout the list is checked against its source
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_schema.json")) as fh:
+        wire = {struct: tuple(fields) for struct, fields in json.load(fh).items()}
+    assert wire == D.SCHEMA
+    if os.environ.get("JTK_REFERENCE_CHECKOUT"):
         import re
-        src = open(ref).read()
-        for struct, fields in D.SCHEMA.items():
+        src = open(os.path.join(os.environ["JTK_REFERENCE_CHECKOUT"], "definitions", "src", "lib.rs")).read()
+        for struct, fields in wire.items():
             body = re.search(r"pub struct %s \{(.*?)\n\}" % struct, src, flags=re.S).group(1)
             assert tuple(re.findall(r"^\s*pub ([a-z_0-9]+):", body, flags=re.M)) == fields, struct
     for breakage in ("error_rate.mism_sd", "model_param.reverse", "selected_chunks.0.copy_num", "encoded_reads.1.nodes.0.cigar"):
