@@ -340,7 +340,7 @@ __global__ __launch_bounds__(FIN_TILE) void column_filter_fused_kernel(const Rea
 }
 
 // one wave per chunk: ordered compaction of the candidates, the greedy pick, then the feature matrix.
-// TABLE = true: the entries come from the materialised table (finalize_kernel ran: rounds 1-5, JTK_FILTER_FUSED=0); false: every
+// TABLE = true: the entries come from the materialised table (finalize_kernel ran: polish_only, max_n > 65535); false: every
 // entry of a candidate column is evaluated from the row sums when it is needed (fin_entry: the same expressions, the same bits)
 // TRACE = true (pick_trace_kernel, jtk_lc_session_trace): the same pick once more for ONE chunk, leaving what the reference's
 // trace! rows need -- tr[0] = candidates (TOTAL :467), tr[1] = picks, tr[2 ..] = the picked candidates' list indices in pick order

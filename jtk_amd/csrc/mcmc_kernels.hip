@@ -1199,7 +1199,7 @@ typedef __attribute__((address_space(3))) const double lds_c_f64;
 typedef __attribute__((address_space(3))) float lds_f32;
 __device__ __forceinline__ double lo_f64(u32x4 v) { return jtk_bits_f64(((uint64_t)v.y << 32) | v.x); }
 __device__ __forceinline__ double hi_f64(u32x4 v) { return jtk_bits_f64(((uint64_t)v.w << 32) | v.z); }
-__device__ __forceinline__ void lds_store_sz(SzEnt *p, const SzEnt &e) {
+__device__ __forceinline__ void lds_put_sz(SzEnt *p, const SzEnt &e) {
     lds_u32x4 *q = (lds_u32x4 *)p;
     const uint64_t a = jtk_f64_bits(e.rem), b = jtk_f64_bits(e.add);
     u32x4 v, w;
@@ -1491,7 +1491,7 @@ __device__ __attribute__((noinline)) double mcmc_chain_tab(LdsShape shape, uint3
                 e.nr = nr[c];
                 e.um = um;
                 e.pad[0] = e.pad[1] = 0;
-                lds_store_sz(&m.sz[c], e);
+                lds_put_sz(&m.sz[c], e);
             }
         }
         wsync();
@@ -2112,12 +2112,12 @@ __device__ __attribute__((noinline)) double mcmc_chain_k2(K2Mem m_in, uint32_t n
     //      block's look-up of its reads' entries is in flight while its two logarithms are computed, every position of the
     //      stream belongs to exactly one block (a window used to re-read the tail of its predecessor), and the move itself is
     //      ~60 instructions.  Solo chains -7 .. -10 % (profiles/r06_chain_solo.txt); requesting the next block's records a block
-    //      ahead (JTK_K2_LOOKAHEAD 128) adds nothing: the chain is now bound by its producer wave.
+    //      ahead adds nothing: the chain is now bound by its producer wave (and the general kernel, whose ring holds 1,024
+    //      positions, loses 9 %: its consumer then waits for the producer 64 positions earlier in every superblock).
     uint32_t w_base = 0;          // stream position of lane 0
     uint32_t w_idx = 0, w_w0 = 0; // per lane: the read the proposal starting here picks; its end (mod 64) | HW_CROSS, or HW_OUT
     float w_lrej = 0.0f, w_lacc = 0.0f;  // per lane: diff below w_lrej: certainly rejected; above w_lacc: certainly accepted
     uint32_t hopw = 0;
-    uint32_t r_next = 0;          // per lane: the record of position w_base + 64 + lane
     uint32_t n_blocks = 0;        // (statistics build: windows loaded)
     auto hop_finish = [&](const u32x4_t tv) {
         const float diff = __uint_as_float(tv.x);
@@ -2150,37 +2150,22 @@ __device__ __attribute__((noinline)) double mcmc_chain_k2(K2Mem m_in, uint32_t n
         hop_finish(tv);
     };
     // the records of [base, base + 128) exist and may not be overwritten
-#ifndef JTK_K2_LOOKAHEAD
-// Records that must exist beyond a block's base.  64: the block's own records are read when it is entered (default).  128: the
-// next block's records are requested a block ahead (r_next) -- measured (profiles/r06_chain_solo.txt): nothing for the light
-// kernel (the chain is bound by its producer wave, not by this round trip) and -9 % for the general kernel, whose ring holds
-// 1,024 positions: the consumer then waits for the producer 64 positions earlier in every superblock.
-#define JTK_K2_LOOKAHEAD 64u
-#endif
     auto block_claim = [&](uint32_t base) {
         rng.pos = base;
         rng_release(rng, lane);
-        rng_wait_rec(rng, base + JTK_K2_LOOKAHEAD);
+        rng_wait_rec(rng, base + 64u);  // the block's own records, read when it is entered
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         w_base = base;
     };
     auto block_first = [&](uint32_t base) {   // the chain's first block, or the one behind a proposal with scalar draws that went far
         block_claim(base);
         const uint32_t r = *(lds_vu32 *)(uintptr_t)(rec_lds + (((base + lane) & rn_mask) << 2));
-#if JTK_K2_LOOKAHEAD >= 128u
-        r_next = *(lds_vu32 *)(uintptr_t)(rec_lds + (((base + 64u + lane) & rn_mask) << 2));
-#endif
         block_setup(r);
         n_blocks++;
     };
-    auto block_advance = [&]() {              // on to the block at w_base + 64: its records came in while this one was walked
+    auto block_advance = [&]() {              // on to the block at w_base + 64
         block_claim(w_base + 64u);
-#if JTK_K2_LOOKAHEAD >= 128u
-        const uint32_t r = r_next;
-        r_next = *(lds_vu32 *)(uintptr_t)(rec_lds + (((w_base + 64u + lane) & rn_mask) << 2));
-#else   // (measurement: no request ahead -- the block's own records are read now)
         const uint32_t r = *(lds_vu32 *)(uintptr_t)(rec_lds + (((w_base + lane) & rn_mask) << 2));
-#endif
         block_setup(r);
         n_blocks++;
     };
@@ -2476,9 +2461,6 @@ __device__ __forceinline__ bool mcmc_clustering(const Lds &m, uint32_t n, uint32
         if (!kmeans(m, n, D, K, rng, lane)) return false;
         const double lk = mcmc_with_filter<K, LIGHT, HUGE>(m, n, D, cov, rng, lane);
         if (ubool(lk != lk)) return false;  // the reference panicked inside mcmc_with_filter
-#ifdef JTK_DEBUG_LK
-        if (lane == 0 && n == 65) printf("DEVLK n %u D %u it %d lk %.17g pos %u\n", n, D, it, lk, rng.pos);
-#endif
         if (!have || !(lk < best)) {  // max_by: the last maximum wins
             best = lk;
             have = true;
@@ -2650,12 +2632,6 @@ __device__ __forceinline__ void mcmc_body(const ChunkMeta *chunks, ChunkState *s
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __syncthreads();
-#ifdef JTK_MCMC_PRIO_PRODUCER  // experiments: wave priority of the two halves of a chain workgroup (s_setprio 0..3)
-    if (wave == 1) __builtin_amdgcn_s_setprio(JTK_MCMC_PRIO_PRODUCER);
-#endif
-#ifdef JTK_MCMC_PRIO_CONSUMER
-    if (wave == 0) __builtin_amdgcn_s_setprio(JTK_MCMC_PRIO_CONSUMER);
-#endif
     if (wave == 1) {  // Xoshiro256StarStar::seed_from_u64(chunk.id * 3490)  (local_clustering/mod.rs:97)
         producer_main(m.ctl, m.ring, m.rec, seg_log, uni64(cm.chunk_id) * 3490ULL,
                       rng_resume ? rng_resume + 4 * (uint64_t)ci : nullptr, lane);
@@ -3043,7 +3019,7 @@ int mcmc_upload_jump_table(hipStream_t s) {
 
 // `split`: 2 + 2 * n_chunks words of device scratch, or null.  With it the launch is two kernels: the light one (168
 // registers, the diploid chunks of <= 63 reads with <= 2 variant columns) and the general one for the rest; without it (or
-// with JTK_MCMC_SPLIT=0) the general kernel runs everything.  `side` (with its two events), if given, is a second stream the
+// with rng_resume) the general kernel runs everything.  `side` (with its two events), if given, is a second stream the
 // general kernel runs on, beside the light one instead of before it.
 int launch_mcmc(hipStream_t s, uint32_t n_chunks, const ChunkMeta *chunks, ChunkState *state,
                 const jtk_lc_params_t *params, const double *feat, const uint32_t *vtype, const uint64_t *vt_off,
@@ -3054,18 +3030,15 @@ int launch_mcmc(hipStream_t s, uint32_t n_chunks, const ChunkMeta *chunks, Chunk
     lds_k = clamp_k(lds_k);
     const size_t lds = mcmc_lds_core(lds_n, lds_d, lds_k, JTK_SEG_LOG_GENERAL);  // the general kernel: a 12 KiB ring
     if (mcmc_upload_jump_table(s) != 0) return -1;  // the caller fails the call: nothing was launched
-    const uint32_t flags = 0u;  // (reserved)
-    static const bool no_split = getenv("JTK_MCMC_SPLIT") && atoi(getenv("JTK_MCMC_SPLIT")) == 0;
-    if (!split || no_split || flags || rng_resume) {
+    if (!split || rng_resume) {
         mcmc_kernel<<<n_chunks, 128, lds, s>>>(chunks, state, params, feat, vtype, vt_off, vt_stride_mode, label, post,
                                               post_stride, lg, lg_off, lds_n, lds_d, lds_k,
-                                              JTK_SEG_LOG_GENERAL, flags, rng_resume, order, nullptr);
+                                              JTK_SEG_LOG_GENERAL, 0u, rng_resume, order, nullptr);
         return 0;
     }
     chain_split_kernel<<<1, 64, 0, s>>>(n_chunks, order, chunks, state, split);
     hipStream_t hs = s;
-    static const bool no_side = getenv("JTK_MCMC_SIDE") && atoi(getenv("JTK_MCMC_SIDE")) == 0;  // experiments: one stream
-    if (!no_side && side && ev_fork && ev_join && hipEventRecord(ev_fork, s) == hipSuccess &&
+    if (side && ev_fork && ev_join && hipEventRecord(ev_fork, s) == hipSuccess &&
         hipStreamWaitEvent(side, ev_fork, 0) == hipSuccess)
         hs = side;
     mcmc_kernel<<<n_chunks, 128, lds, hs>>>(chunks, state, params, feat, vtype, vt_off, vt_stride_mode, label, post, post_stride,

@@ -1,6 +1,6 @@
 // phmm_kernels.hip -- band preparation and table finalisation of the banded pair-HMM for gfx950 (CDNA4); the sweep itself
-// (phmm_kernel) lives in phmm_sweep.hip.  (The round-2 sweep that used to sit here behind -DJTK_PHMM_WITH_R2 is in
-// scripts/experiments/legacy/phmm_kernel_r2.hip.inc.)
+// (phmm_kernel) lives in phmm_sweep.hip.  (The round-2 sweep that used to sit here is in the history:
+// `git show 0ae82d9:scripts/experiments/legacy/phmm_kernel_r2.hip.inc`.)
 //
 // Replaces kiley `modification_table_antidiagonal` as called from
 // haplotyper/src/local_clustering/pseudo_mcmc.rs:45-68 and the per-read inner step of

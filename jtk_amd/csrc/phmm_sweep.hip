@@ -41,18 +41,6 @@ namespace {
 #define S_SMETA (S_STAGE + 384)  // their (row, exponent)
 #define S_VAR (S_SMETA + 32)   // delta words | block exponents | replay bits | template codes | read codes
 #define JTK_BFW_BYTES(n_blk) ((n_blk) + 8u)  // one bit per group of 8 diagonals, n_blk blocks of 64 diagonals; + slack for the look-ahead
-#ifndef JTK_PHMM_REPLAY
-#define JTK_PHMM_REPLAY 1      // 0: every pair through the stripe (rounds 2-3)
-#endif
-#ifndef JTK_PHMM_FWD_PREFETCH
-#define JTK_PHMM_FWD_PREFETCH 1     // the forward sweep's fast steps do the same (and load a half group's read bytes a step early)
-#endif
-#ifndef JTK_PHMM_BASE_CMPX
-#define JTK_PHMM_BASE_CMPX 1        // the row sums split by read base through v_cmpx (0: v_cmp + s_and_saveexec, rounds 3-5)
-#endif
-#ifndef JTK_PHMM_REPLAY_PREFETCH
-#define JTK_PHMM_REPLAY_PREFETCH 1  // the replayed steps fetch their emission entries one step ahead (0: when they need them)
-#endif
 
 __device__ __forceinline__ double rot_from_prev(double v) {  // lane l <- lane (l-1)&63
     int lo = __double2loint(v), hi = __double2hiint(v);
@@ -85,19 +73,6 @@ __device__ __forceinline__ uint64_t uni64(uint64_t v) {
     return (uint64_t)(uint32_t)uni((int)(uint32_t)(v >> 32)) << 32 | (uint32_t)uni((int)(uint32_t)v);
 }
 __device__ __forceinline__ double uni_f64(double v) { return jtk_bits_f64(uni64(jtk_f64_bits(v))); }
-// v with lane l (uniform, a scalar register) replaced by the scalar x: v_writelane_b32 ignores EXEC, so one lane's state changes
-// without a saveexec / branch / restore around it
-__device__ __forceinline__ __attribute__((unused)) int wlane(int x, int l, int v) {
-    x = __builtin_amdgcn_readfirstlane(x);  // (a uniform value the compiler keeps in a vector register is not an "s" operand)
-    l = __builtin_amdgcn_readfirstlane(l);
-    asm("s_mov_b32 m0, %2\n\tv_writelane_b32 %0, %1, m0" : "+v"(v) : "s"(x), "s"(l) : "m0");  // (two SGPRs: the select goes through M0)
-    return v;
-}
-__device__ __forceinline__ __attribute__((unused)) double wl_zero(double v, int l) {  // v with lane l set to +0.0
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    asm("v_writelane_b32 %0, 0, %2\n\tv_writelane_b32 %1, 0, %2" : "+v"(lo), "+v"(hi) : "s"(l));
-    return __hiloint2double(hi, lo);
-}
 __device__ __forceinline__ uint64_t rotl64(uint64_t m, int s) { return (m << (s & 63)) | (m >> ((64 - s) & 63)); }
 __device__ __forceinline__ bool lanes(uint64_t m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
 // A block that must run under an EXEC mask (and not be turned into selects over everything it assigns): an empty volatile
@@ -109,23 +84,9 @@ __device__ __forceinline__ bool lanes(uint64_t m) { return __builtin_amdgcn_inve
 #define MARK(x)
 #endif
 
-// acc_sub += x_sub * vm and acc_ins += x_ins * vm on the lanes whose read base is `Q` (y8 == 8 Q): the row sums split by
-// read base.  fma(x, 0, acc) == acc exactly, so leaving the other lanes out changes no bit (oracle/phmm.c masks vm).
-#define BASE_FMA(Q, acc_sub, acc_ins, x_sub, x_ins, vmv, y8v)                                                         \
-    {                                                                                                               \
-        uint64_t sv_;                                                                                               \
-        asm("v_cmp_eq_u32_e32 vcc, %[q8], %[y8]\n\t"                                                                \
-            "s_and_saveexec_b64 %[sv], vcc\n\t"                                                                     \
-            "v_fmac_f64_e32 %[a], %[xa], %[vm]\n\t"                                                                 \
-            "v_fmac_f64_e32 %[b], %[xb], %[vm]\n\t"                                                                 \
-            "s_mov_b64 exec, %[sv]"                                                                                 \
-            : [a] "+v"(acc_sub), [b] "+v"(acc_ins), [sv] "=&s"(sv_)                                                 \
-            : [y8] "v"(y8v), [xa] "v"(x_sub), [xb] "v"(x_ins), [vm] "v"(vmv), [q8] "n"(8 * (Q))                      \
-            : "vcc", "scc");                                                                                               \
-    }
-#if defined(JTK_PHMM_X_NOBASE)   // timing-only probe: no split by read base
-#define BASE_FMAS(xs_, xi_, vmv, y8v) { acc[0] = fma(xs_, vmv, acc[0]); acc[5] = fma(xi_, vmv, acc[5]); }
-#elif JTK_PHMM_BASE_CMPX  // v_cmpx writes EXEC itself: 4 instructions per base instead of 5 (round 6: -1.3 % of a pass)
+// acc[q] += xs_ * vm and acc[5 + q] += xi_ * vm on the lanes whose read base is q (y8 == 8 q): the row sums split by read
+// base.  fma(x, 0, acc) == acc exactly, so leaving the other lanes out changes no bit (oracle/phmm.c masks vm).  v_cmpx writes
+// EXEC itself: 4 instructions per base instead of the 5 of v_cmp + s_and_saveexec (round 6: -1.3 % of a pass).
 #define BASE_FMAS(xs_, xi_, vmv, y8v)                                                                               \
     {                                                                                                               \
         uint64_t sv_;                                                                                               \
@@ -151,13 +112,6 @@ __device__ __forceinline__ bool lanes(uint64_t m) { return __builtin_amdgcn_inve
             : [y8] "v"(y8v), [xa] "v"(xs_), [xb] "v"(xi_), [vm] "v"(vmv)                                            \
             : "vcc", "scc");                                                                                        \
     }
-#else
-#define BASE_FMAS(xs_, xi_, vmv, y8v)                 \
-    BASE_FMA(0, acc[0], acc[5], xs_, xi_, vmv, y8v)   \
-    BASE_FMA(1, acc[1], acc[6], xs_, xi_, vmv, y8v)   \
-    BASE_FMA(2, acc[2], acc[7], xs_, xi_, vmv, y8v)   \
-    BASE_FMA(3, acc[3], acc[8], xs_, xi_, vmv, y8v)
-#endif
 // acc = fma(y, vd, fma(x, hM, acc)) where the x term only counts on lanes with rowv >= thr_x and the y term on lanes with
 // rowv >= thr_y (the del-3 source row i-4 must lie inside the band of ITS diagonal: the one case the three spare lanes of
 // the lane ring cannot tell apart)
@@ -272,7 +226,6 @@ __device__ __forceinline__ void sweep_read(const int L, const int n, const int r
                  aII = uni_f64(h->a[4]), aID = uni_f64(h->a[5]), aDM = uni_f64(h->a[6]), aDI = uni_f64(h->a[7]),
                  aDD = uni_f64(h->a[8]);
     const uint64_t BAND = (2ull << (2 * r)) - 1;  // 2r+1 ones
-#if JTK_PHMM_REPLAY
     // bit g of the replay bits: the backward sweep takes the diagonals 8g .. 8g+7 as a fast group (its own conditions, below) and
     // the forward sweep takes both 8(g-1) .. and 8g .. as fast groups, so that the pairs of the diagonals 8g-5 .. 8g+2 can be
     // replayed from the checkpoint after diagonal 8g-6.  Lane-parallel, once per read.
@@ -295,7 +248,6 @@ __device__ __forceinline__ void sweep_read(const int L, const int n, const int r
         const uint32_t lo = lds_u8(S_BFW + (g >> 3)), hi = lds_u8(S_BFW + (g >> 3) + 1);
         return ((uint32_t)uni((int)(lo | hi << 8)) >> (g & 7u)) & 3u;
     };
-#endif
 
     // =========================== forward ===========================
     int c = 0, EF = 0;                                   // c == c[t-1] between steps
@@ -317,19 +269,11 @@ __device__ __forceinline__ void sweep_read(const int L, const int n, const int r
         bool fast_ready = false;
         uint64_t band = 0;
         int lo6 = 0;
-#if JTK_PHMM_FWD_PREFETCH
         uint32_t Wn = 0;           // the read bytes of the coming half group
         double eMn = 0.0, eIn = 0.0;  // the emission entries of the coming step
-#endif
         while (t <= T) {
             uint32_t db = 0;
             bool fast = (t & 7) == 0 && t >= f_lo && t + 7 <= f_hi;
-#ifdef JTK_PHMM_NOFAST_FWD
-#if JTK_PHMM_REPLAY
-#error "JTK_PHMM_NOFAST_FWD needs -DJTK_PHMM_REPLAY=0: the replay bits assume the forward sweep's fast groups"
-#endif
-            fast = false;
-#endif
             if (fast) {
                 db = delta_byte(t >> 3);
                 // a lane that leaves the band takes its next row at the THIRD move after its own (three spare lanes): its
@@ -388,78 +332,46 @@ __device__ __forceinline__ void sweep_read(const int L, const int n, const int r
                 xrow = S_EM + xs_of(row);
                 band = rotl64(BAND, lo6);
                 fast_ready = true;
-#if JTK_PHMM_FWD_PREFETCH
                 Wn = window4(EY0 + (uint32_t)(t - row));
                 eMn = lds_f64(xrow | (Wn & 24u));
                 eIn = lds_f64(S_EI + (Wn & 0xffu));
-#endif
             }
             uint32_t W = 0;  // the read bytes of the half group's columns j .. j+3, j = (t + u) - row
             double2 *out = scratch + (int64_t)t * 64;
-#if JTK_PHMM_REPLAY
             // the pairs of the steps 0..2 are the backward group g's, those of the steps 3..7 group g+1's: a group that replays
             // wants the checkpoint after step 2 (in the slots of the diagonals t+3, t+4) instead of its pairs
             const uint32_t bf2 = bf_bits((uint32_t)t >> 3);
 #define FWD_STORES(u) ((u) < 3 ? !(bf2 & 1u) : !(bf2 & 2u))
-#else
-#define FWD_STORES(u) true
-#endif
             const bool block_start = (t & (JTK_SCALE_BLOCK - 1)) == 0;  // step u == 0 opens a scaling block
 #pragma unroll
             for (int u = 0; u < 8; u++) {
-#if JTK_PHMM_FWD_PREFETCH
                 // (see the replayed steps in the backward sweep: entries of step u+1 fetched during step u by every lane.  The
                 // read bytes of the next half group are loaded at the end of this one -- the same state of `row` as at its top)
                 if ((u & 3) == 0) W = Wn;
                 const double eMk = eMn, eIk = eIn;
 #define FWD_EMISSIONS const double eMv = eMk, eIv = eIk;
-#else
-                if ((u & 3) == 0) W = window4(EY0 + (uint32_t)(t + u - row));
-#define FWD_EMISSIONS const double eMv = lds_f64(xrow | (byte & 24u)), eIv = lds_f64(S_EI + byte);
-#endif
                 const double pM = rot_from_prev(toM_2), pD = rot_from_prev(toD_1);
                 toM_2 = toM_1;  // every lane: a lane outside the band shifts its zeros along
                 if ((db >> u) & 1) {  // the band moves up: row c - r leaves it, its lane is spare for the next three moves
-#if defined(JTK_PHMM_X_WLANE)
-                    toM_1 = wl_zero(toM_1, lo6);
-                    toI_1 = wl_zero(toI_1, lo6);
-                    toD_1 = wl_zero(toD_1, lo6);
-                    row = wlane(c - r + 64, lo6, row);
-                    xrow = (uint32_t)wlane((int)(S_EM + (((uint32_t)c & 3u) << 5)), lo6, (int)xrow);
-#else
                     if (lanes(1ull << lo6)) {
                         KEEP_MASKED;
                         toM_1 = 0.0;
                         toI_1 = 0.0;
                         toD_1 = 0.0;
                         row += 64;
-#ifdef JTK_PHMM_X_NOXS
-                        xrow = S_EM + (((uint32_t)row & 3u) << 5);
-#else
                         xrow = S_EM + xs_of(row);
-#endif
                     }
-#endif
                     lo6 = (lo6 + 1) & 63;
                     c += 1;
                     band = (band << 1) | (band >> 63);
                 }
                 const bool in_band = lanes(band);
-#if JTK_PHMM_FWD_PREFETCH
                 {
                     if ((u & 3) == 3) Wn = window4(EY0 + (uint32_t)(t + u + 1 - row));
                     const uint32_t bnext = ((u & 3) == 3 ? Wn : W >> (8 * ((u & 3) + 1))) & 0xffu;
-#ifdef JTK_PHMM_X_NOEM
-                    eMn = jtk_bits_f64(0x3fd0000000000000ull | bnext);
-                    eIn = jtk_bits_f64(0x3fd0000000000000ull | xrow);
-#else
                     eMn = lds_f64(xrow | (bnext & 24u));
                     eIn = lds_f64(S_EI + bnext);
-#endif
                 }
-#else
-                const uint32_t byte = (W >> (8 * (u & 3))) & 0xffu;
-#endif
                 if (u == 0) {
                     // the group's first diagonal may open a scaling block (the maximum over the band decides the block's
                     // exponent): the band's work is split around that rare step
@@ -514,13 +426,11 @@ __device__ __forceinline__ void sweep_read(const int L, const int n, const int r
                         KEEP_MASKED;
                         out[u * 64 + lane] = make_double2(toM_2, toD_1);
                     }
-#if JTK_PHMM_REPLAY
                     if (u == 2 && (bf2 & 2u)) {
                         KEEP_MASKED;
                         out[3 * 64 + lane] = make_double2(toM_1, toM_2);
                         out[4 * 64 + lane] = make_double2(toI_1, toD_1);
                     }
-#endif
                 }
             }
 #undef FWD_STORES
@@ -583,36 +493,17 @@ __device__ __forceinline__ void sweep_read(const int L, const int n, const int r
         uint64_t band = 0;
         int lo6 = 0;
         int rowG = 0;  // exponent of the lane's finished row, until the group's flush
-        // pairs on their way from the stripe: qA = those the steps u = 0..3 of the coming group put into the ring (loaded
-        // while the previous group ran its steps 4..7), qB = those of the steps u = 4..7 (loaded at the group's start)
-#if JTK_PHMM_REPLAY
         // q[k] = the replayed pair of diagonal 8g-5+k (step u of the group puts q[7-u] into the ring); ck0 / ck1 = the
         // checkpoint of the NEXT group below, on its way from the stripe while this group runs
         double2 q[8], ck0 = make_double2(0.0, 0.0), ck1 = ck0;
-#else
-        double2 qA[4], qB[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) qA[k] = qB[k] = make_double2(0.0, 0.0);
-#endif
         while (t >= 0) {
             uint32_t w16 = 0;
-#if JTK_PHMM_REPLAY
             bool fast = (t & 7) == 7 && (bf_bits((uint32_t)t >> 3) & 1u);
             int carry = 0;
             if (fast) {
                 w16 = delta_byte(t >> 3) << 8 | delta_byte((t >> 3) - 1);  // bit k: c[t-15+k] - c[t-16+k]
                 carry = delta_bit(t + 1);
             }
-#else
-            bool fast = (t & 7) == 7 && t - 7 >= f_lo && t <= f_hi && t < T && t >= 23;
-            int carry = 0;
-            if (fast) {
-                w16 = delta_byte(t >> 3) << 8 | delta_byte((t >> 3) - 1);  // bit k: c[t-15+k] - c[t-16+k]
-                carry = delta_bit(t + 1);
-                // band moves at the steps t .. t-3 / t-4 .. t-7: at most three per half group (see the forward sweep)
-                fast = carry + __builtin_popcount((w16 >> 13) & 7u) <= 3 && ((w16 >> 9) & 0xfu) != 0xfu;
-            }
-#endif
             if (!fast) {
                 // ---- generic step
                 fast_ready = false;
@@ -720,13 +611,8 @@ __device__ __forceinline__ void sweep_read(const int L, const int n, const int r
                 xrow = S_EM + xs_of(row);
                 band = rotl64(BAND, lo6);
                 fast_ready = true;
-#if JTK_PHMM_REPLAY
                 ck0 = scratch[(int64_t)(t - 12) * 64 + lane];
                 ck1 = scratch[(int64_t)(t - 11) * 64 + lane];
-#else
-#pragma unroll
-                for (int k = 0; k < 4; k++) qA[k] = scratch[(int64_t)(t - 5 - k) * 64 + lane];
-#endif
             }
             const int tb = t;
             uint32_t W = 0;     // read bytes of the half group's columns j-3 .. j, j = (tb - u) - row: step u uses byte 3 - (u & 3)
@@ -736,7 +622,6 @@ __device__ __forceinline__ void sweep_read(const int L, const int n, const int r
             double Fsp = 1.0;
             if (low_group) Fsp = fast_pow2(uni(s_EF[(tb >> 6) - 1]) - uni(s_EF[tb >> 6]));
             const double2 *pin = scratch + (int64_t)(tb - 5) * 64 + lane;  // P_{tb-5}; step u puts pin[-64 u] into the ring
-#if JTK_PHMM_REPLAY
             MARK("replay_begin");
             {   // ---- replay the forward steps of the diagonals tb-12 .. tb-5 from the checkpoint after diagonal tb-13
                 double fM1 = ck0.x, fM2 = ck0.y, fI1 = ck1.x, fD1 = ck1.y;
@@ -749,7 +634,6 @@ __device__ __forceinline__ void sweep_read(const int L, const int n, const int r
                 uint32_t xrowf = S_EM + xs_of(rowf);
                 uint32_t yb = EY0 + (uint32_t)(tb - 12 - rowf);  // the read byte of diagonal tb-12+k: smem[yb + k]
                 uint64_t bandf = rotl64(BAND, lo6f);
-#if JTK_PHMM_REPLAY_PREFETCH
                 // The emission entries of step k+1 are fetched during step k, the read byte they are indexed with during step
                 // k-1, by EVERY lane: a step otherwise starts with two dependent LDS round trips (byte, then entry) in front of its
                 // chain of multiplies.  Valid because a lane's row changes when it LEAVES the band and it is back at the third
@@ -762,28 +646,13 @@ __device__ __forceinline__ void sweep_read(const int L, const int n, const int r
                     eMn = lds_f64(xrowf | (b0 & 24u));
                     eIn = lds_f64(S_EI + b0);
                 }
-#endif
 #pragma unroll
                 for (int k = 0; k < 8; k++) {
                     const double pM = rot_from_prev(fM2), pD = rot_from_prev(fD1);
                     fM2 = fM1;
-#if JTK_PHMM_REPLAY_PREFETCH
                     const double eMk = eMn, eIk = eIn;
 #define REPLAY_EMISSIONS(kk) const double eMv = eMk, eIv = eIk;
-#else
-#define REPLAY_EMISSIONS(kk)                    \
-    const uint32_t byte = lds_u8(yb + (kk)); \
-    const double eMv = lds_f64(xrowf | (byte & 24u)), eIv = lds_f64(S_EI + byte);
-#endif
                     if ((w16 >> (3 + k)) & 1u) {
-#if defined(JTK_PHMM_X_WLANE)
-                        fM1 = wl_zero(fM1, lo6f);
-                        fI1 = wl_zero(fI1, lo6f);
-                        fD1 = wl_zero(fD1, lo6f);
-                        rowf = wlane(lof + k + 64, lo6f, rowf);
-                        yb = (uint32_t)wlane((int)(EY0 + (uint32_t)(tb - 12 - lof - k - 64)), lo6f, (int)yb);
-                        xrowf = (uint32_t)wlane((int)(S_EM + (((uint32_t)lo6f & 3u) << 5)), lo6f, (int)xrowf);
-#else
                         if (lanes(1ull << lo6f)) {
                             KEEP_MASKED;
                             fM1 = 0.0;
@@ -791,28 +660,16 @@ __device__ __forceinline__ void sweep_read(const int L, const int n, const int r
                             fD1 = 0.0;
                             rowf += 64;
                             yb -= 64;
-#ifdef JTK_PHMM_X_NOXS
-                            xrowf = S_EM + (((uint32_t)rowf & 3u) << 5);
-#else
                             xrowf = S_EM + xs_of(rowf);
-#endif
                         }
-#endif
                         lo6f = (lo6f + 1) & 63;
                         bandf = (bandf << 1) | (bandf >> 63);
                     }
-#if JTK_PHMM_REPLAY_PREFETCH
                     if (k < 7) {
-#ifdef JTK_PHMM_X_NOEM
-                        eMn = jtk_bits_f64(0x3fd0000000000000ull | bn);
-                        eIn = jtk_bits_f64(0x3fd0000000000000ull | xrowf);
-#else
                         eMn = lds_f64(xrowf | (bn & 24u));
                         eIn = lds_f64(S_EI + bn);
-#endif
                         if (k < 6) bn = lds_u8(yb + (uint32_t)(k + 2));
                     }
-#endif
                     const bool in_bandf = lanes(bandf);
                     if (k == 5 && low_group) {  // diagonal tb-7 opens a scaling block: the forward step scaled by 2^-e == Fsp
                         KEEP_MASKED;
@@ -850,7 +707,6 @@ __device__ __forceinline__ void sweep_read(const int L, const int n, const int r
                 }
             }
             MARK("replay_end");
-#endif
 #pragma unroll
             for (int u = 0; u < 8; u++) {
                 if ((u & 3) == 0) W = window4(EY0 + (uint32_t)(tb - u - row - 3));
@@ -871,14 +727,6 @@ __device__ __forceinline__ void sweep_read(const int L, const int n, const int r
                 const int dn = u == 0 ? carry : (int)((w16 >> (16 - u)) & 1u);  // c[t+1] - c[t]
                 if (dn) {  // the band moves down: row c + r leaves it, final
                     const int hi6 = (lo6 + 2 * r) & 63;
-#if defined(JTK_PHMM_X_WLANE)
-                    hM_1 = wl_zero(hM_1, hi6);
-                    hI_1 = wl_zero(hI_1, hi6);
-                    bD_1 = wl_zero(bD_1, hi6);
-                    rowG = wlane(Gprev, hi6, rowG);
-                    row = wlane(c + r - 64, hi6, row);
-                    xrow = (uint32_t)wlane((int)(S_EM + (((uint32_t)c & 3u) << 5)), hi6, (int)xrow);
-#else
                     if (lanes(1ull << hi6)) {
                         KEEP_MASKED;
                         hM_1 = 0.0;
@@ -886,35 +734,15 @@ __device__ __forceinline__ void sweep_read(const int L, const int n, const int r
                         bD_1 = 0.0;
                         rowG = Gprev;
                         row -= 64;
-#ifdef JTK_PHMM_X_NOXS
-                        xrow = S_EM + (((uint32_t)row & 3u) << 5);
-#else
                         xrow = S_EM + xs_of(row);
-#endif
                     }
-#endif
                     left |= 1ull << hi6;
                     lo6 = (lo6 - 1) & 63;
                     c -= 1;
                     band = (band >> 1) | (band << 63);
                 }
-#if !JTK_PHMM_REPLAY
-                if (u == 0) {
-#pragma unroll
-                    for (int k = 0; k < 4; k++) qB[k] = pin[-64 * (4 + k)];
-                }
-#endif
                 {  // the pair five diagonals below enters the ring
-#if JTK_PHMM_REPLAY
                     double2 v = q[7 - u];
-#else
-                    double2 v = u < 4 ? qA[u & 3] : qB[u & 3];
-                    if (u == 3) {  // qA is free again: the next group's first four pairs (a group that turns out generic
-                                   // reloads what it needs)
-#pragma unroll
-                        for (int k = 0; k < 4; k++) qA[k] = pin[-64 * (8 + k)];
-                    }
-#endif
                     if (u >= 2 && low_group) {
                         KEEP_MASKED;  // a (rare) uniform branch, not two selects per step
                         v.x *= Fsp;
@@ -982,11 +810,7 @@ __device__ __forceinline__ void sweep_read(const int L, const int n, const int r
                 } else {
                     if (in_band) {
                         KEEP_MASKED;
-#ifdef JTK_PHMM_X_NOEM
-                        const double eMv = jtk_bits_f64(0x3fd0000000000000ull | y8), eIv = jtk_bits_f64(0x3fd0000000000000ull | xrow);
-#else
                         const double eMv = lds_f64(xrow | y8), eIv = lds_f64(S_EI + byte);
-#endif
                         const double vm = fma(aMD, xd, fma(aMI, hI_1, aMM * xm));
                         const double vi = fma(aID, xd, fma(aII, hI_1, aIM * xm));
                         const double vd = fma(aDD, xd, fma(aDI, hI_1, aDM * xm));
@@ -1014,7 +838,6 @@ __device__ __forceinline__ void sweep_read(const int L, const int n, const int r
 #pragma unroll
                         for (int k = 0; k < JTK_ACC_N; k++) acc[k] = 0.0;
                     }
-#ifndef JTK_PHMM_X_NOFLUSH
                     if ((uint32_t)lane < 8u * nleft) {
                         KEEP_MASKED;
                         const double2 v = reinterpret_cast<const double2 *>(smem + S_STAGE)[lane];  // slot lane / 8, part lane % 8
@@ -1022,7 +845,6 @@ __device__ __forceinline__ void sweep_read(const int L, const int n, const int r
                         reinterpret_cast<double2 *>(raw + (uint64_t)meta.x * JTK_ACC_N)[lane & 7] = v;
                         if ((lane & 7) == 0) rawG[meta.x] = meta.y;
                     }
-#endif
                 }
                 if ((u & 3) == 3) left = 0;
             }

@@ -191,57 +191,11 @@ struct StripePool {
     uint64_t stride = 0;  // doubles
     uint32_t n = 0;
     StripeSet set() const {
-        static const uint32_t unfenced = getenv("JTK_STRIPE_UNFENCED") ? 1u : 0u;  // measurement only
-        return StripeSet{mem.as<double>(), stride, owner.as<uint32_t>(), n, unfenced};
+        return StripeSet{mem.as<double>(), stride, owner.as<uint32_t>(), n};
     }
 };
 std::mutex g_stripe_mutex;
 std::shared_ptr<StripePool> g_stripes[JTK_POOL_DEVICES];
-
-// The pair-HMM gate (round 6).  A pass of a batch is two phases with opposite needs: the polish rounds + tables + filter fill the
-// device (or could), the chain kernels that follow keep a few hundred long-lived workgroups busy for 100-300 ms and leave the
-// rest of the device idle.  Slices that start together STAY together: they share the device during their pair-HMM rounds, finish
-// them at the same time and then all sit in their chain kernels at once (profiles/r06_trace_summary.txt: 200-300 ms per
-// 880 ms step in which the device ran nothing but chain workgroups; without the chain kernels the same step takes 627 ms).
-// The gate admits at most JTK_LC_PHASE_SLOTS batches per device to the pair-HMM phase at a time, first come first served; a
-// batch leaves it when its chain kernels are queued.  The admitted batches get the whole device, finish their rounds sooner, and
-// their chains run under the next batches' pair-HMM rounds.  MEASURED AND NOT ADOPTED (profiles/r06_gate.txt: 2,810 / 2,888 /
-// 2,982 chunks/s with 2 / 3 / 4 slots against 2,902 without; start offsets between the slices, r06_stagger.txt, do nothing
-// either): a chain workgroup that runs beside pair-HMM waves takes their registers and LDS for as long as it lives, which costs
-// about what the idle tail of the lockstep costs.  Default 0 = no gate; the switch stays for measurements.  No effect on results.
-struct PhaseGate {
-    std::mutex m;
-    std::condition_variable cv;
-    uint64_t next_ticket = 0, released = 0;
-};
-PhaseGate g_gate[JTK_POOL_DEVICES];
-int phase_slots() {
-    static const int v = []() {
-        const char *e = getenv("JTK_LC_PHASE_SLOTS");
-        return e ? atoi(e) : 0;
-    }();
-    return v;
-}
-struct PhaseHold {
-    PhaseGate *g = nullptr;
-    explicit PhaseHold(int device) {
-        if (phase_slots() <= 0 || device < 0 || device >= JTK_POOL_DEVICES) return;  // 0: no gate (rounds 1-5)
-        g = &g_gate[device];
-        std::unique_lock<std::mutex> lock(g->m);
-        const uint64_t ticket = g->next_ticket++;
-        g->cv.wait(lock, [&]() { return ticket < g->released + (uint64_t)phase_slots(); });
-    }
-    void release() {
-        if (!g) return;
-        {
-            std::lock_guard<std::mutex> lock(g->m);
-            g->released++;
-        }
-        g->cv.notify_all();
-        g = nullptr;
-    }
-    ~PhaseHold() { release(); }
-};
 
 struct KernelTimer {
     hipEvent_t a = nullptr, b = nullptr;
@@ -348,17 +302,13 @@ struct jtk_lc_session {
     hipEvent_t ev_round[2] = {nullptr, nullptr};
     // the chain launch: light / general chunk lists made on the device (mcmc_kernels.hip), the general kernel on its own stream
     DevPtr d_chain_split;
-    hipStream_t side = nullptr, chain_main = nullptr;   // chain_main: experiment JTK_CHAIN_CUS (CU-masked chain streams)
-    hipEvent_t ev_chain[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipStream_t side = nullptr;
+    hipEvent_t ev_chain[2] = {nullptr, nullptr};
     ~jtk_lc_session() {
         if (stream) (void)hipStreamSynchronize(stream);  // blocks go back to the pool, not through hipFree's implicit sync
         if (side) {
             (void)hipStreamSynchronize(side);
             (void)hipStreamDestroy(side);
-        }
-        if (chain_main) {
-            (void)hipStreamSynchronize(chain_main);
-            (void)hipStreamDestroy(chain_main);
         }
         for (auto &e : ev_chain)
             if (e) (void)hipEventDestroy(e);
@@ -737,24 +687,6 @@ static int session_create_ex(const jtk_lc_params_t *params, size_t n_chunks, con
         const char *force = getenv("JTK_LC_SIDE_STREAM");
         const bool on = force ? atoi(force) != 0 : (g_queues_by_library || g_host_queues >= 8);
         if (on) {
-            // experiment (JTK_CHAIN_CUS=n): the chain's two kernels on streams confined to n CUs, so that their long-lived
-            // waves do not take wave slots all over the device (the light kernel then runs on `chain_main`, the general one on `side`)
-            static const int chain_cus = getenv("JTK_CHAIN_CUS") ? atoi(getenv("JTK_CHAIN_CUS")) : 0;
-            if (chain_cus > 0) {
-                hipDeviceProp_t prop;
-                HIP_TRY(hipGetDeviceProperties(&prop, device));
-                const int n_cu = prop.multiProcessorCount;
-                std::vector<uint32_t> mask((n_cu + 31) / 32, 0u);
-                static const int spread = getenv("JTK_CHAIN_CUS_SPREAD") ? atoi(getenv("JTK_CHAIN_CUS_SPREAD")) : 1;
-                for (int k = 0; k < chain_cus && k < n_cu; k++) {
-                    const int cu = spread ? (int)((int64_t)k * n_cu / chain_cus) : k;   // spread over the device, or the first n
-                    mask[cu / 32] |= 1u << (cu % 32);
-                }
-                HIP_TRY(hipExtStreamCreateWithCUMask(&s->side, (uint32_t)mask.size(), mask.data()));
-                HIP_TRY(hipExtStreamCreateWithCUMask(&s->chain_main, (uint32_t)mask.size(), mask.data()));
-                HIP_TRY(hipEventCreateWithFlags(&s->ev_chain[2], hipEventDisableTiming));
-                HIP_TRY(hipEventCreateWithFlags(&s->ev_chain[3], hipEventDisableTiming));
-            } else
             HIP_TRY(hipStreamCreateWithFlags(&s->side, hipStreamNonBlocking));
             HIP_TRY(hipEventCreateWithFlags(&s->ev_chain[0], hipEventDisableTiming));
             HIP_TRY(hipEventCreateWithFlags(&s->ev_chain[1], hipEventDisableTiming));
@@ -791,23 +723,21 @@ static int session_create_ex(const jtk_lc_params_t *params, size_t n_chunks, con
         uint32_t per_cu = (uint32_t)((160u * 1024u) / phmm_lds_bytes(s->max_tmpl, s->max_read));
         if (per_cu > 12) per_cu = 12;
         if (per_cu < 1) per_cu = 1;
-        if (const char *e = getenv("JTK_PHMM_WAVES_PER_CU")) per_cu = (uint32_t)atoi(e);  // tuning experiments only
         const uint32_t want = (uint32_t)prop.multiProcessorCount * per_cu;
         s->n_waves = n_reads < want ? (uint32_t)n_reads : want;
         if (s->n_waves == 0) s->n_waves = 1;
         // one stripe per wave the DEVICE can hold (3 per SIMD by registers = 12 per CU; 16 leaves room): the set is shared
         const uint64_t stride = (uint64_t)(s->max_tmpl + s->max_read + 8 + JTK_SCRATCH_GUARD) * 64 * 2;  // doubles
         const uint32_t n_stripes = (uint32_t)prop.multiProcessorCount * 16;
-        static const bool private_set = getenv("JTK_STRIPE_SHARED") && atoi(getenv("JTK_STRIPE_SHARED")) == 0;  // experiments
         std::lock_guard<std::mutex> lock(g_stripe_mutex);
-        std::shared_ptr<StripePool> mine;  // JTK_STRIPE_SHARED=0: a set of this session's own, as before round 3
+        std::shared_ptr<StripePool> mine;
         // A session that launches far fewer waves than the device holds (one pile-up's modification table, the five training
         // pile-ups of the model refit) neither needs nor may grow the device's set: n_waves stripes of its own (a 60-read call
         // holds 0.3 GB, not the 19 GB of 4,096 stripes).  It uses the device's set if one of sufficient stride is already there.
         const bool small = (uint64_t)s->n_waves * 4u <= n_stripes &&
                            !(device < JTK_POOL_DEVICES && g_stripes[device] && g_stripes[device]->stride >= stride);
-        std::shared_ptr<StripePool> &cur = (private_set || small || device >= JTK_POOL_DEVICES) ? mine : g_stripes[device];
-        const uint32_t n_want = (private_set || small) ? s->n_waves : n_stripes;
+        std::shared_ptr<StripePool> &cur = (small || device >= JTK_POOL_DEVICES) ? mine : g_stripes[device];
+        const uint32_t n_want = small ? s->n_waves : n_stripes;
         if (!cur || cur->stride < stride || cur->n < n_want) {
             auto p = std::make_shared<StripePool>();
             p->stride = std::max<uint64_t>(stride, cur ? cur->stride : 0);
@@ -825,20 +755,15 @@ static int session_create_ex(const jtk_lc_params_t *params, size_t n_chunks, con
         }
         s->stripes = cur;
     }
-    {  // narrow bands: two reads of a chunk per wave (phmm_pair.hip); JTK_PHMM_PAIR=0 keeps them on phmm_kernel
-        static const bool pair_on = []() {
-            const char *e = getenv("JTK_PHMM_PAIR");
-            return !(e && e[0] == '0');
-        }();
+    {  // narrow bands: two reads of a chunk per wave (phmm_pair.hip)
         std::vector<uint32_t> items;
-        if (pair_on)
-            for (size_t c = 0; c < n_chunks; c++) {
-                const ChunkMeta &cm = s->h_chunks[c];
-                if (cm.radius > JTK_PAIR_MAX_RADIUS || s->h_state0[c].status != 0) continue;
-                const uint32_t voters = cm.take_num ? std::min(cm.take_num, cm.n_reads) : cm.n_reads;
-                for (uint32_t r = 0; r + 1 < voters; r += 2) items.push_back(cm.read_first + r);
-                if (voters & 1u) items.push_back((cm.read_first + voters - 1) | 0x80000000u);
-            }
+        for (size_t c = 0; c < n_chunks; c++) {
+            const ChunkMeta &cm = s->h_chunks[c];
+            if (cm.radius > JTK_PAIR_MAX_RADIUS || s->h_state0[c].status != 0) continue;
+            const uint32_t voters = cm.take_num ? std::min(cm.take_num, cm.n_reads) : cm.n_reads;
+            for (uint32_t r = 0; r + 1 < voters; r += 2) items.push_back(cm.read_first + r);
+            if (voters & 1u) items.push_back((cm.read_first + voters - 1) | 0x80000000u);
+        }
         s->n_pair_items = (uint32_t)items.size();
         if (s->n_pair_items) {
             hipDeviceProp_t prop;
@@ -906,7 +831,6 @@ static int run_split(jtk_lc_session_t *s);
 // one pass of the kernel sequence over the resident batch
 static int run_batch(jtk_lc_session_t *s, int skip_polish) {
     HIP_TRY(hipSetDevice(s->device));
-    PhaseHold phase(s->device);   // the pair-HMM gate: held until the chain kernels are queued (or the pass ends)
     const double h2d = g_timing.h2d_ms;
     memset(&g_timing, 0, sizeof g_timing);
     g_timing.h2d_ms = h2d;
@@ -944,9 +868,8 @@ static int run_batch(jtk_lc_session_t *s, int skip_polish) {
     // Round 6: the variant filter takes its column statistics and the picked columns' entries straight from the row sums
     // (column_filter_fused_kernel, filter_kernels.hip), so a clustering pass never materialises the N x 14(L+1) table --
     // finalize_kernel runs only where the table itself is the product (window polishing keeps its final-pass call; the
-    // modification-table entry point has its own) or with JTK_FILTER_FUSED=0 (rounds 1-5, kept for differential runs).
-    static const bool filter_fused = !(getenv("JTK_FILTER_FUSED") && atoi(getenv("JTK_FILTER_FUSED")) == 0);
-    const bool need_tables = s->polish_only || !filter_fused || s->max_n > 65535u;  // (the fused filter counts in 16-bit fields)
+    // modification-table entry point has its own) or where a pile-up is too deep for the fused filter.
+    const bool need_tables = s->polish_only || s->max_n > 65535u;  // (the fused filter counts in 16-bit fields)
     const int max_rounds = skip_polish ? 1 : JTK_POLISH_MAX_ROUNDS + 1;
     for (int round = 0; round < max_rounds; round++) {
         const int only_active = round > 0;
@@ -1007,21 +930,11 @@ static int run_batch(jtk_lc_session_t *s, int skip_polish) {
                   s->d_sel.as<uint8_t>(), s->d_feat.as<double>(), s->d_vtype.as<uint32_t>(), s->d_pos.as<uint32_t>(),
                   s->max_tmpl, hmm2, s->d_rawG.as<int>(), s->d_lk.as<double>(), need_tables ? 0 : 1);
     tstop(s);
-    phase.release();   // everything that fills the device is queued: the next batch may start its rounds
     tstart(s, JTK_K_MCMC);
     int mcmc_rc = 0;
-    hipStream_t st_main = st;
-    if (s->chain_main) {   // (experiment) the chain on its CU-masked stream: fork here, join after the launches
-        HIP_TRY(hipEventRecord(s->ev_chain[2], st));
-        HIP_TRY(hipStreamWaitEvent(s->chain_main, s->ev_chain[2], 0));
-        st = s->chain_main;
-    }
-    // measurement only (scripts/overlap_probe_r6.sh): a pass without its chain kernels -- what the chain's share of the CUs' LDS
-    // and issue slots costs the pair-HMM family when slices overlap.  Labels / posteriors are then whatever the buffers held.
-    static const bool x_nochain = getenv("JTK_X_NOCHAIN") != nullptr;
     for (int j = 0; j < 2; j++) {
         const ChainClass &cc = s->chain_class[j];
-        if (cc.count == 0 || mcmc_rc != 0 || x_nochain) continue;
+        if (cc.count == 0 || mcmc_rc != 0) continue;
         // the class's own stretch of the split scratch: 2 + 2 * count words from 2 * first + 4 * j
         mcmc_rc = launch_mcmc(st, cc.count, chunks, state, s->d_params.as<jtk_lc_params_t>(), s->d_feat.as<double>(),
                               s->d_vtype.as<uint32_t>(), nullptr, 0, s->d_label.as<uint32_t>(), s->d_post.as<double>(),
@@ -1029,18 +942,13 @@ static int run_batch(jtk_lc_session_t *s, int skip_polish) {
                               s->resume_rng ? s->d_rng.as<uint64_t>() : nullptr, s->d_order.as<uint32_t>() + cc.first,
                               s->d_chain_split.as<uint32_t>() + 2 * cc.first + 4 * j, s->side, s->ev_chain[0], s->ev_chain[1]);
     }
-    if (s->chain_class[2].count && mcmc_rc == 0 && !x_nochain) {
+    if (s->chain_class[2].count && mcmc_rc == 0) {
         const ChainClass &cc = s->chain_class[2];
         mcmc_rc = launch_mcmc_huge(st, cc.count, chunks, state, s->d_params.as<jtk_lc_params_t>(), s->d_feat.as<double>(),
                                    s->d_vtype.as<uint32_t>(), nullptr, 0, s->d_label.as<uint32_t>(), s->d_post.as<double>(),
                                    s->post_stride, s->d_lg.as<double>(), s->d_lg_off.as<uint64_t>(), cc.lds_n, cc.lds_d, cc.lds_k,
                                    s->resume_rng ? s->d_rng.as<uint64_t>() : nullptr, s->d_order.as<uint32_t>() + cc.first,
                                    s->d_chain_ws.as<uint8_t>(), s->d_chain_ws_off.as<uint64_t>());
-    }
-    if (s->chain_main) {
-        HIP_TRY(hipEventRecord(s->ev_chain[3], s->chain_main));
-        HIP_TRY(hipStreamWaitEvent(st_main, s->ev_chain[3], 0));
-        st = st_main;
     }
     tstop(s);
     if (mcmc_rc != 0) {

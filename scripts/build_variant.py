@@ -3,7 +3,7 @@
 flags, every other object is the product build's (jtk_amd/_build/*.o), the result is jtk_amd/_build/exp_<name>/libjtk_lc_<name>.so
 (point JTK_LC_LIB at it).  Seconds instead of the minutes of build.build_experiment, which recompiles everything.
 
-    python3 scripts/build_variant.py wlane phmm_sweep.hip -DJTK_PHMM_X_WLANE
+    python3 scripts/build_variant.py marks phmm_sweep.hip -DJTK_PHMM_MARKS
 """
 import os
 import subprocess

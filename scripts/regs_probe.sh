@@ -1,6 +1,6 @@
 #!/bin/bash
 # GPU box: the default bench on experiment builds of the library (jtk_amd/_build/<name>.so [ENV=VALUE ...])
-# usage: regs_probe.sh "libA.so" "libB.so JTK_MCMC_JUMP_GLOBAL=1" ...
+# usage: regs_probe.sh "libA.so" "libB.so JTK_LC_SIDE_STREAM=0" ...
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 mkdir -p gpurun_out
 show() { python -c "

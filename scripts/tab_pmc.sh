@@ -14,7 +14,7 @@ n=0
 for G in "$G1" "$G2" "$G3"; do
   n=$((n+1))
   rm -rf $OUT/tpmc_${TAG}_g$n
-  timeout 300 rocprofv3 --kernel-trace --pmc $G --output-format csv -d $OUT/tpmc_${TAG}_g$n -- python3 $REPO/scripts/experiments/tab_event/chain_ms.py 1 > $OUT/tpmc_${TAG}_g$n.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --pmc $G --output-format csv -d $OUT/tpmc_${TAG}_g$n -- python3 $REPO/scripts/chain_ms.py 1 > $OUT/tpmc_${TAG}_g$n.log 2>&1
   echo "pass $n rc=$?"
 done
 cd $REPO && python3 - $OUT $TAG <<'PY'
