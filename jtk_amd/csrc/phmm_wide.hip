@@ -20,6 +20,10 @@
 // to radius 127; 512 up to JTK_WIDE_MAX_RADIUS = 255 -- round 6: CLR / None reads on chunks up to 10 kbp, ONT up to 17 kbp,
 // ReadType::band_width definitions/src/lib.rs:201-210).  A kernel argument: `WP` below is a local of each kernel.
 static uint32_t wide_wp(uint32_t max_radius) { return max_radius <= 127u ? 256u : 512u; }
+// Band cells per lane: NP = ceil((2 * radius + 1) / 64) <= WIDE_NP.  The per-lane arrays below hold WIDE_NP entries; with 4 they
+// overflowed from radius 128 on (NP = 5 .. 8) and the cells of the band's low edge read another array's values.
+constexpr int WIDE_NP = (2 * JTK_WIDE_MAX_RADIUS + 1 + 63) / 64;
+static_assert(WIDE_NP == 8, "phmm_wide: 8 band cells per lane at JTK_WIDE_MAX_RADIUS");
 
 namespace {
 
@@ -109,7 +113,7 @@ __global__ __launch_bounds__(64) void phmm_wide_kernel(uint32_t n_reads, const R
             const int E1 = t >= 1 ? s_EF[(t - 1) >> 6] : 0;
             const double s2 = (t >= 2 && Eprev2 != E1) ? pow2i_w(Eprev2 - E1) : 1.0;
             const int lo = (int)s_c[t] - r;
-            double fm[4], fi[4], fd[4];
+            double fm[WIDE_NP], fi[WIDE_NP], fd[WIDE_NP];
             double m = 0.0;
             for (int ps = 0; ps < NP; ps++) {
                 const int w = ps * 64 + lane, i = lo + w, j = t - i;
@@ -205,7 +209,7 @@ __global__ __launch_bounds__(64) void phmm_wide_kernel(uint32_t n_reads, const R
             const int Ecur0 = t < T ? s_EB[(t + 1) >> 6] : 0;
             const int E2 = t + 2 <= T ? s_EB[(t + 2) >> 6] : 0;
             const double s2 = (t + 2 <= T && E2 != Ecur0) ? pow2i_w(E2 - Ecur0) : 1.0;
-            double vm[4], vi[4], vd[4];
+            double vm[WIDE_NP], vi[WIDE_NP], vd[WIDE_NP];
             double m = 0.0;
             for (int ps = 0; ps < NP; ps++) {
                 const int w = ps * 64 + lane, i = lo + w, j = t - i;
@@ -246,7 +250,7 @@ __global__ __launch_bounds__(64) void phmm_wide_kernel(uint32_t n_reads, const R
             if (lane == 0) s_EB[t >> 6] = EB;  // (the block's value: set by its highest diagonal, kept by the others)
             __syncthreads();
             double *oHM = bHM + (t % 3) * WP, *oHI = bHI + (t % 3) * WP, *oBD = bBD + (t % 3) * WP;
-            double hm[4];
+            double hm[WIDE_NP];
             for (int ps = 0; ps < NP; ps++) {
                 const int w = ps * 64 + lane, i = lo + w, j = t - i;
                 double a = 0.0, b = 0.0;
@@ -403,7 +407,7 @@ __global__ __launch_bounds__(64) void phmm_counts_kernel(uint32_t n_reads, const
             const int E2 = t >= 2 ? s_EF[(t - 2) >> 6] : 0, E1 = t >= 1 ? s_EF[(t - 1) >> 6] : 0;
             const double s2 = (t >= 2 && E2 != E1) ? pow2i_w(E2 - E1) : 1.0;
             const int lo = (int)s_c[t] - r;
-            double fm[4], fi[4], fd[4];
+            double fm[WIDE_NP], fi[WIDE_NP], fd[WIDE_NP];
             double m = 0.0;
             for (int ps = 0; ps < NP; ps++) {
                 const int w = ps * 64 + lane, i = lo + w, j = t - i;
@@ -480,7 +484,7 @@ __global__ __launch_bounds__(64) void phmm_counts_kernel(uint32_t n_reads, const
             const double s2 = (t + 2 <= T && E2 != Ecur0) ? pow2i_w(E2 - Ecur0) : 1.0;
             const int EFt = s_EF[t >> 6];
             const double wt = pow2i_w(EFt + Ecur0 - ET) * inv;
-            double vm[4], vi[4], vd[4];
+            double vm[WIDE_NP], vi[WIDE_NP], vd[WIDE_NP];
             double m = 0.0;
             for (int ps = 0; ps < NP; ps++) {
                 const int w = ps * 64 + lane, i = lo + w, j = t - i;

@@ -4,6 +4,7 @@
 produce the same text, row for row.  CPU: the oracle's rows agree with the oracle's own results and with the Rust format strings.
 GPU: device text == oracle text."""
 import ctypes as C
+import functools
 import re
 
 import numpy as np
@@ -98,6 +99,46 @@ def test_oracle_rows_follow_the_rust_format_strings(oracle):
     assert sum(int(x) for x in counts[0].split("\t")[1].strip("[]").split(", ")) == len(lab)
 
 
+def homopolymer_lengths(tmpl):
+    """homopolymer_length (pseudo_mcmc.rs:195-211): the length of the run every template base is in"""
+    tl = len(tmpl)
+    homop = np.ones(tl, dtype=np.int64)
+    i = 0
+    while i < tl:
+        j = i
+        while j + 1 < tl and tmpl[j + 1] == tmpl[i]:
+            j += 1
+        homop[i:j + 1] = j - i + 1
+        i = j + 1
+    return homop
+
+
+def expected_gain(p, homop_len, row):
+    """Gains::expected, likelihood_gains.rs:79-87; difftype :168-178"""
+    g = p.gains
+    h = min(max(int(homop_len), 1), int(g.max_homopolymer_len))
+    tab = g.subst if row < 4 else (g.insertions if row < 8 + 3 else g.deletions)
+    return tab[h - 1].gain
+
+
+def cand_lk_count(prof, bp, row, homop, p, ks):
+    """a CAND row's lk and count (pseudo_mcmc.rs:457-461 + column_sum :577-588) from the per-read profiles prof = table - lk
+    [n, 14 (tl + 1)]: compress_small_gains, the sum and count of the gains above POS_THR, + max_k Poisson(count | k * coverage)"""
+    import math
+    tl = len(homop)
+    mr = expected_gain(p, homop[bp] if bp < tl else 1, row) * 0.5
+    col = prof[:, bp * 14 + row].copy()
+    col[np.abs(col) < mr] = 0.0
+    gain, count = 0.0, 0
+    for x in col:                                       # left to right, as the reference sums
+        if 0.00001 < x:
+            gain += float(x)
+            count += 1
+    cov = float(p.haploid_coverage)
+    pois = max(count * math.log(cov * k) - cov * k - sum(math.log(q) for q in range(1, count + 1)) for k in ks)
+    return pois + gain, count
+
+
 @pytest.mark.parametrize("config", ["ont_diploid", "ont_4copy"])
 def test_cand_and_dump_rows_against_a_numpy_restatement(oracle, config):
     """CAND's lk and count (pseudo_mcmc.rs:457-461 + column_sum :577-588) and DUMP's sum (:124) recomputed here in numpy from the
@@ -122,35 +163,14 @@ def test_cand_and_dump_rows_against_a_numpy_restatement(oracle, config):
         tab, lk = O.modification_table(hmm, tmpl, b.read(r), b.read_ops(r), radius)
         tabs.append(tab - lk)
     prof = np.array(tabs)                                   # n x 14 (tl + 1)
-    homop = np.ones(tl, dtype=np.int64)                     # homopolymer_length :195-211
-    i = 0
-    while i < tl:
-        j = i
-        while j + 1 < tl and tmpl[j + 1] == tmpl[i]:
-            j += 1
-        homop[i:j + 1] = j - i + 1
-        i = j + 1
-
-    def expected(homop_len, row):                           # Gains::expected, likelihood_gains.rs:79-87; difftype :168-178
-        g = p.gains
-        h = min(max(int(homop_len), 1), int(g.max_homopolymer_len))
-        tab = g.subst if row < 4 else (g.insertions if row < 8 + 3 else g.deletions)
-        return tab[h - 1].gain
-
+    homop = homopolymer_lengths(tmpl)
+    expected = functools.partial(expected_gain, p)
     cov = float(p.haploid_coverage)
     for c in cands:
         bp, row, lk_txt, count_txt = int(c[1]), int(c[2]), c[3], int(c[4])
-        mr = expected(homop[bp] if bp < tl else 1, row) * 0.5
-        col = prof[:, bp * 14 + row].copy()
-        col[np.abs(col) < mr] = 0.0
-        gain, count = 0.0, 0
-        for x in col:                                       # left to right, as the reference sums
-            if 0.00001 < x:
-                gain += float(x)
-                count += 1
+        lk, count = cand_lk_count(prof, bp, row, homop, p, ks)
         assert count == count_txt
-        pois = max(count * math.log(cov * k) - cov * k - sum(math.log(q) for q in range(1, count + 1)) for k in ks)
-        assert "%.1f" % (pois + gain) == lk_txt, (bp, row, pois + gain, lk_txt)
+        assert "%.1f" % lk == lk_txt, (bp, row, lk, lk_txt)
     for d in dumps:
         bp, row = int(d[2]), int(d[3])
         mr = expected(homop[bp] if bp < tl else 1, row) * 0.5
