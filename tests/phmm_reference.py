@@ -399,3 +399,150 @@ def _mp_forward_backward(mpmath, model, tmpl, read):
             if j >= 1:
                 cnt[25 + 4 * ctx(j) + y[j - 1]] += F[i][j][1] * B[i][j][1] / P
     return mpmath.log(P), cnt
+
+
+# ---- polishing, from the prose of DESIGN section 4 and the rule comment over select_edits in oracle/phmm.c
+#
+# Round t: column totals = sum over the first take_num reads of (table - lk); scan p = ignore_edge .. L - ignore_edge - 1 from the
+# left; at p take the best row; if its total exceeds MIN_GAIN apply it and jump over the bases it touches (d for a deletion of d
+# bases, one otherwise) plus inactive(t) = 5 + (5 t mod 21) further positions; a round that applies nothing is the last, and there
+# are at most MAX_POLISH_ROUNDS.  The ops of every read follow the template: see rethread().
+#
+# Two rows at one position whose edited templates are byte-identical (insert tmpl[p] before p = copy 1 at p) have equal totals
+# up to rounding and the same outcome, so rows are grouped by edited() and a decision is `decidable` when it does not hang on
+# rounding: |best - MIN_GAIN| > tol, and every row of another group is below best - tol.
+
+MIN_GAIN = 0.1
+MAX_POLISH_ROUNDS = 20
+DECISION_TOL = 1e-6
+
+
+def inactive(t):
+    return 5 + (5 * t) % 21
+
+
+def column_totals(fwd, rev, tmpl, reads, opss, strands, radius, take_num):
+    """[L, 14]: sum over the first min(take_num, n) reads of table - lk (strand != 0: forward model); an entry that is the
+    sentinel for any read stays the sentinel"""
+    L = len(tmpl)
+    tot = np.zeros((L + 1, NUM_ROW))
+    dead = np.zeros((L + 1, NUM_ROW), dtype=bool)
+    for r in range(min(take_num, len(reads))):
+        tab, lk = modification_table(fwd if strands[r] else rev, tmpl, reads[r], opss[r], radius)
+        assert np.isfinite(lk), "read %d has no path inside the band" % r
+        dead |= tab <= SENTINEL / 2
+        tot += np.where(tab <= SENTINEL / 2, 0.0, tab - lk)
+    return np.where(dead, SENTINEL, tot)[:L]
+
+
+def _edit_span(row):
+    return row - 10 if row >= 11 else 1
+
+
+def select_edits(totals, ignore_edge, round, tmpl):
+    """-> (edits [(pos, row)], log): the left-to-right scan of one round.  log holds one dict per scanned position: pos, row (the
+    first best row), best, applied, gain_margin = |best - MIN_GAIN|, row_margin = best - the largest total among rows whose edited
+    template differs from the best row's (inf when there is none), decidable"""
+    L = len(tmpl)
+    assert totals.shape == (L, NUM_ROW)
+    edits, log = [], []
+    pos = ignore_edge
+    while pos + ignore_edge < L:
+        t = totals[pos]
+        row = int(np.argmax(t))                       # the first of equal maxima
+        best = float(t[row])
+        mine = edited(tmpl, pos, row)
+        others = [float(t[q]) for q in range(NUM_ROW)
+                  if q != row and (mine is None or edited(tmpl, pos, q) is None
+                                   or bytes(edited(tmpl, pos, q)) != bytes(mine))]
+        row_margin = best - max(others) if others else np.inf
+        applied = best > MIN_GAIN
+        assert not (applied and mine is None), "an edit that does not exist was selected"
+        log.append(dict(round=round, pos=pos, row=row, best=best, applied=applied, gain_margin=abs(best - MIN_GAIN),
+                        row_margin=row_margin,
+                        decidable=abs(best - MIN_GAIN) > DECISION_TOL and row_margin > DECISION_TOL))
+        if applied:
+            edits.append((pos, row))
+            pos += _edit_span(row) + inactive(round)
+        else:
+            pos += 1
+    return edits, log
+
+
+def apply_edits(tmpl, edits):
+    """the template after every (pos, row) of one round, through edited(): applied from the right, so that the positions left of
+    an edit keep their meaning"""
+    out = np.asarray(tmpl, dtype=np.uint8)
+    for pos, row in sorted(edits, reverse=True):
+        out = edited(out, pos, row)
+        assert out is not None, (pos, row)
+    return out
+
+
+def rethread(ops, L, edits, new_tmpl, read):
+    """the ops of one read after the edits of one round.  The alignment is a list of columns (template index | None, read index |
+    None).  A deleted template base leaves its column (the column goes when it held no read base); the k bases of an insertion /
+    copy edit at pos are k read-less columns directly after the column of old base pos - 1 (at the very front for pos = 0);
+    template indices are then renumbered and Match / Mismatch is tagged from the new template and the read."""
+    cols, i, j = [], 0, 0
+    for op in np.asarray(ops).tolist():
+        if op == OP_INS:
+            cols.append((None, j))
+            j += 1
+        elif op == OP_DEL:
+            cols.append((i, None))
+            i += 1
+        else:
+            cols.append((i, j))
+            i, j = i + 1, j + 1
+    assert i == L and j == len(read)
+    gone, after = set(), {}
+    for pos, row in edits:
+        if row >= 11:
+            gone.update(range(pos, pos + row - 10))
+        elif row >= 8:
+            after[pos - 1] = after.get(pos - 1, 0) + (row - 7)
+        elif row >= 4:
+            after[pos - 1] = after.get(pos - 1, 0) + 1
+    new = [("new", None)] * after.pop(-1, 0)
+    for ti, rj in cols:
+        keep_t = ti is not None and ti not in gone
+        if keep_t or rj is not None:
+            new.append(("old" if keep_t else None, rj))
+        if ti is not None and ti in after:
+            assert ti not in gone
+            new += [("new", None)] * after.pop(ti)
+    assert not after, after
+    out, i = [], 0
+    for t, rj in new:
+        if t is None:
+            out.append(OP_INS)
+        elif rj is None:
+            out.append(OP_DEL)
+            i += 1
+        else:
+            out.append(OP_MATCH if new_tmpl[i] == read[rj] else OP_MISMATCH)
+            i += 1
+    assert i == len(new_tmpl) and sum(1 for _, rj in new if rj is not None) == len(read)
+    return np.array(out, dtype=np.uint8)
+
+
+def polish(fwd, rev, tmpl, reads, opss, strands, radius, take_num, ignore_edge):
+    """-> (consensus, ops of all reads, rounds, log).  rounds counts the round that applied nothing; log is the concatenation of
+    every round's select_edits log."""
+    cur = np.asarray(tmpl, dtype=np.uint8).copy()
+    opss = [np.asarray(o, dtype=np.uint8).copy() for o in opss]
+    log, rounds = [], 0
+    for t in range(MAX_POLISH_ROUNDS):
+        rounds = t + 1
+        if 2 * ignore_edge >= len(cur):
+            break                                      # nothing to scan: no need for the totals
+        tot = column_totals(fwd, rev, cur, reads, opss, strands, radius, take_num)
+        edits, lg = select_edits(tot, ignore_edge, t, cur)
+        log += lg
+        if not edits:
+            break
+        nxt = apply_edits(cur, edits)
+        opss = [rethread(o, len(cur), edits, nxt, rd) for o, rd in zip(opss, reads)]
+        cur = nxt
+    return cur, opss, rounds, log
