@@ -16,6 +16,11 @@ extern "C" {
 JTK_LC_API void jtk_lc_debug_cc_keep_sims(int on);
 /* Copy up to `cap` doubles of the kept matrix into `out`; returns its size. */
 JTK_LC_API size_t jtk_lc_debug_cc_first_sims(double *out, size_t cap);
+/* While the switch above is on, the raw matrix (before filter_similarity) of EVERY corrected chunk of the last call is kept, in
+ * the order the chunks are corrected (selected_chunks order) and across all device batches of the call: their number, and a copy
+ * of up to `cap` doubles of matrix `job` (returns its size, 0 for a job that does not exist).  Nothing is kept while it is off. */
+JTK_LC_API size_t jtk_lc_debug_cc_sims_count(void);
+JTK_LC_API size_t jtk_lc_debug_cc_sims(size_t job, double *out, size_t cap);
 
 /* Where the chain kernel's time went, per chunk of a session that has run: cycles[c] = shader-clock cycles the chunk's consumer
  * wave spent in the kernel (0 for a chunk without a variant column), events[c] = proposals of its table-driven chains that could

@@ -138,6 +138,32 @@ def correct_clustering(read_id, node_off, nodes, posteriors, chunks, selection, 
     return cluster, touched
 
 
+def correct_clustering_with_sims(*args, **kw):
+    """correct_clustering with the diagnostic switch of include/jtk_lc_debug.h on: returns (cluster, touched, sims), sims = the
+    raw similarity matrix (before filter_similarity) of every corrected chunk, in selected_chunks order.  A test hook: the
+    matrices are kept on the calling thread only while the switch is on, and it is off again when this returns."""
+    L = ffi.lib()
+    L.jtk_lc_debug_cc_keep_sims.argtypes = [C.c_int]
+    L.jtk_lc_debug_cc_keep_sims.restype = None
+    L.jtk_lc_debug_cc_sims_count.argtypes = []
+    L.jtk_lc_debug_cc_sims_count.restype = C.c_size_t
+    L.jtk_lc_debug_cc_sims.argtypes = [C.c_size_t, C.POINTER(C.c_double), C.c_size_t]
+    L.jtk_lc_debug_cc_sims.restype = C.c_size_t
+    L.jtk_lc_debug_cc_keep_sims(1)
+    try:
+        cluster, touched = correct_clustering(*args, **kw)
+        sims = []
+        for job in range(L.jtk_lc_debug_cc_sims_count()):
+            size = L.jtk_lc_debug_cc_sims(job, None, 0)
+            n = int(round(size ** 0.5))
+            m = np.zeros((n, n))
+            assert n * n == size and L.jtk_lc_debug_cc_sims(job, f64p(m), m.size) == size
+            sims.append(m)
+    finally:
+        L.jtk_lc_debug_cc_keep_sims(0)
+    return cluster, touched, sims
+
+
 def cluster_features(params, feature_chunks, variants, variant_type, post_stride, device=0,
                      raise_on_chunk_failure=True):
     """jtk_lc_cluster_features: cluster_filtered_variants + posterior on caller-supplied feature matrices."""

@@ -410,6 +410,7 @@ struct DevBuf {
 
 thread_local bool g_keep_sims = false;
 thread_local std::vector<double> g_first_sims;
+thread_local std::vector<std::vector<double>> g_all_sims;  // one per corrected chunk, in job order, across batches
 
 }  // namespace
 
@@ -420,6 +421,15 @@ extern "C" size_t jtk_lc_debug_cc_first_sims(double *out, size_t cap) {
     const size_t n = std::min(cap, g_first_sims.size());
     if (out && n) memcpy(out, g_first_sims.data(), n * sizeof(double));
     return g_first_sims.size();
+}
+// ... and of EVERY corrected chunk of the last call, in the order the chunks are corrected (selected_chunks order), whatever
+// batches JTK_CC_SIMS_BUDGET cut the call into; taken before filter_similarity rewrites them.  Nothing is kept while the switch is off.
+extern "C" size_t jtk_lc_debug_cc_sims_count(void) { return g_all_sims.size(); }
+extern "C" size_t jtk_lc_debug_cc_sims(size_t job, double *out, size_t cap) {
+    if (job >= g_all_sims.size()) return 0;
+    const size_t n = std::min(cap, g_all_sims[job].size());
+    if (out && n) memcpy(out, g_all_sims[job].data(), n * sizeof(double));
+    return g_all_sims[job].size();
 }
 
 extern "C" int jtk_lc_correct_clustering(size_t n_reads, const uint64_t *read_id, const uint64_t *node_off,
@@ -576,6 +586,7 @@ extern "C" int jtk_lc_correct_clustering(size_t n_reads, const uint64_t *read_id
         CC_HIP(hipStreamSynchronize(st));  // post_v goes out of scope
     }
     g_first_sims.clear();
+    g_all_sims.clear();
     // The reference corrects one chunk at a time under rayon (phmm_likelihood_correction.rs:37-43).  Here the jobs go through the
     // device in BATCHES bounded by the bytes of their similarity matrices (sum of n^2 doubles), so host and device memory stay
     // bounded on a genome-scale DataSet; a batch is: similarity fill on the device, then the spectral step on host threads.
@@ -667,6 +678,8 @@ extern "C" int jtk_lc_correct_clustering(size_t n_reads, const uint64_t *read_id
         if (dev_panic) return cc_fail(JTK_ERR_CHUNK_FAILED, "sim(): posterior lengths differ from cluster_num, or a log-probability above 0");
     }
     if (g_keep_sims && j0 == 0 && !pjobs.empty()) g_first_sims.assign(sims.begin(), sims.begin() + (size_t)pjobs[0].n * pjobs[0].n);
+    if (g_keep_sims)
+        for (const PairJob &pj : pjobs) g_all_sims.emplace_back(sims.begin() + pj.sims_off, sims.begin() + pj.sims_off + (size_t)pj.n * pj.n);
     // ---- spectral clustering of every chunk (clustering :290-337), one chunk per host thread
     auto cluster_one = [&](size_t ji) {
         Job &j = jobs[ji];

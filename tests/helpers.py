@@ -261,3 +261,49 @@ def correction_problem(seed, n_chunks=6, n_reads=40, window=(3, 6), noise=1.2, f
     chunks["score"] = rng.uniform(0.0, 30.0, n_chunks)
     return dict(read_id=np.arange(n_reads, dtype=np.uint64) * 7 + 3, node_off=np.array(node_off, dtype=np.uint64), nodes=nodes,
                 posteriors=np.array(post, dtype=np.float64), chunks=chunks, hap=np.array(hap_of))
+
+
+def correction_dataset(seed, path, n_reads, k_of=None, copy_of=None, window=(3, 6), n_haps=2, noise=1.2, flat=0.1, strands="mixed",
+                       hard=False, coverage=10.0, chunk_order=None, read_id=None, skip=0.0, extra_reads=(), flat_chunks=()):
+    """A DataSet-like structure for tests/correction_reference.py (reads with nodes, chunks, haploid coverage), built the other
+    way round from correction_problem: `path` is the genome as a list of chunk ids IN ANY NUMBERING (sparse, unordered, an id
+    twice = a tandem repeat), every read is a window of it on one strand ("forward", "reverse" or "mixed"), optionally with
+    interior nodes missing (`skip`), and `extra_reads` = [(haplotype, is_forward, [chunk ids in genome order]), ...] are added
+    as given.  A node carries ln-posteriors over its chunk's k_of[id] clusters (default 2) that favour cluster
+    haplotype % k: soft (a softmax, every entry <= -1e-6), uninformative for a fraction `flat` of the nodes and on every chunk
+    of `flat_chunks`, or hard ([0, -10000, ...], what an earlier correction writes).  Chunks come in `chunk_order` (default: by
+    first appearance in the path) with copy_num copy_of[id] (default: the cluster count) and a random score; read r gets id
+    read_id(r) (default 7 r + 3)."""
+    rng = np.random.default_rng(seed)
+    k_of, copy_of = dict(k_of or {}), dict(copy_of or {})
+    specs = []
+    for r in range(n_reads):
+        hap = int(rng.integers(0, n_haps))
+        w = min(int(rng.integers(window[0], window[1] + 1)), len(path))
+        start = int(rng.integers(0, len(path) - w + 1))
+        fwd = {"forward": True, "reverse": False}.get(strands, bool(rng.integers(0, 2)))
+        pos = [q for i, q in enumerate(range(start, start + w)) if i in (0, w - 1) or rng.random() >= skip]
+        specs.append((hap, fwd, [path[q] for q in pos]))
+    specs += list(extra_reads)
+    reads = []
+    for r, (hap, fwd, ids) in enumerate(specs):
+        nodes = []
+        for cid in (ids if fwd else ids[::-1]):
+            k = k_of.get(cid, 2)
+            fav = hap % k
+            if hard:
+                lp = [-10000.0] * k
+                lp[fav] = 0.0
+            elif k == 1:
+                lp = [0.0]
+            else:
+                z = rng.normal(0.0, 0.05 if cid in flat_chunks else 0.7, k)
+                if cid not in flat_chunks and rng.random() >= flat:
+                    z[fav] += rng.normal(noise * 3.0, noise)
+                lp = np.minimum(z - np.log(np.exp(z).sum()), -1e-6).tolist()
+            nodes.append(dict(chunk=int(cid), cluster=int(np.argmax(lp)), is_forward=fwd, posterior=[float(x) for x in lp]))
+        reads.append(dict(id=int(read_id(r)) if read_id else 7 * r + 3, nodes=nodes))
+    order = list(chunk_order) if chunk_order is not None else list(dict.fromkeys(path))
+    chunks = [dict(id=int(c), cluster_num=int(k_of.get(c, 2)), copy_num=int(copy_of.get(c, k_of.get(c, 2))),
+                   score=float(rng.uniform(0.0, 30.0))) for c in order]
+    return dict(reads=reads, chunks=chunks, coverage=float(coverage))

@@ -1,5 +1,6 @@
 """jtk_lc_correct_clustering (device similarity fill + host spectral clustering) against oracle/correction.c:
-similarity matrices bit for bit, labels / cluster_num / touched flags equal (phmm_likelihood_correction.rs:32-97)."""
+similarity matrices bit for bit -- of EVERY corrected chunk, through the every-job hook of include/jtk_lc_debug.h and one oracle call
+per chunk with selection=[id] --, labels / cluster_num / touched flags equal (phmm_likelihood_correction.rs:32-97)."""
 import ctypes as C
 
 import numpy as np
@@ -36,6 +37,20 @@ def both(prob, selection=None, cov=20.0, min_gain=1e9, want_sims=0):
     return (orc, ocl, otouched, och, osims), (grc, gcl, gtouched, gch, gsims)
 
 
+def every_job_bit_for_bit(prob, cov=20.0):
+    """the raw similarity matrix of every corrected chunk of one device call against the oracle's (its copy numbers come from
+    all chunks whatever the selection, and it returns the first corrected chunk's matrix: one call per chunk)"""
+    ids = [int(c["id"]) for c in prob["chunks"] if c["cluster_num"] > 1]
+    _, _, sims = api.correct_clustering_with_sims(prob["read_id"], prob["node_off"], prob["nodes"], prob["posteriors"], prob["chunks"].copy(),
+                                                  np.array(ids, dtype=np.uint64), cov, 1e9)
+    assert len(sims) == len(ids) >= 2
+    for cid, got in zip(ids, sims):
+        n = int((prob["nodes"]["chunk"] == cid).sum())
+        _, _, _, _, want = O.correct_clustering(prob["read_id"], prob["node_off"], prob["nodes"], prob["posteriors"], prob["chunks"].copy(),
+                                                np.array([cid], dtype=np.uint64), cov, 1e9, n)
+        assert got.shape == (n, n) and np.array_equal(bits(want), bits(got)), cid
+
+
 @pytest.mark.parametrize("seed,kw", [(1, {}), (2, dict(wrong=0.05)), (3, dict(n_chunks=10, n_reads=120, window=(2, 9), wrong=0.03)),
                                      (4, dict(single=(1, 4), n_chunks=7)), (5, dict(flat=0.5, noise=0.5, wrong=0.1))])
 def test_correction_matches_oracle(seed, kw):
@@ -48,6 +63,7 @@ def test_correction_matches_oracle(seed, kw):
     assert np.array_equal(ot, gt)
     assert np.array_equal(ocl, gcl)
     assert np.array_equal(och, gch)
+    every_job_bit_for_bit(prob)
 
 
 @pytest.mark.changes_env
@@ -93,6 +109,7 @@ def test_correction_copy_number_three():
     assert orc == 0 and grc == 0
     assert np.array_equal(bits(osims), bits(gsims))
     assert np.array_equal(ot, gt) and np.array_equal(ocl, gcl) and np.array_equal(och, gch)
+    every_job_bit_for_bit(prob, cov=30.0)
 
 
 def test_correction_panics_match():
