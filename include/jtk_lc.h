@@ -51,7 +51,8 @@ typedef enum jtk_status {
     JTK_OK = 0,
     JTK_ERR_INVALID_ARG = -1,     /* null pointer, inconsistent offsets, non-ACGT base, bad op code    */
     JTK_ERR_NO_DEVICE = -2,       /* no usable MI355X / HIP runtime failure (message via last_error)   */
-    JTK_ERR_UNSUPPORTED = -3,     /* band radius > 255 (any read count is taken)                        */
+    JTK_ERR_UNSUPPORTED = -3,     /* band radius > 255 (any read count is taken); jtk_lc_align_reads:  */
+                                  /* a read farther from its template than max_dist, or > 32,000 bases */
     JTK_ERR_ALLOC = -4,           /* hipMalloc / host allocation failed                                */
     JTK_ERR_OPS_MISMATCH = -5,    /* ops do not consume exactly the template and the read              */
     JTK_ERR_CHUNK_FAILED = -6,    /* >=1 chunk hit a condition on which the reference panics; see      */
@@ -178,6 +179,24 @@ JTK_LC_API int jtk_lc_polish_chunks(const jtk_lc_params_t *params, size_t n_chun
                          const uint8_t *ops, const uint64_t *ops_off, const uint8_t *strand, uint32_t radius,
                          uint32_t take_num, uint32_t ignore_edge, uint8_t *cons_out, uint64_t *cons_off, uint64_t cons_cap,
                          uint8_t *ops_out, uint64_t *ops_out_off, uint64_t ops_cap, jtk_lc_result_t *result, int device);
+
+/* ---- making the ops: global read-to-template alignment -------------------------------------------------
+ * edlib Global / Alignment as the reference calls it (`global_align`, haplotyper/src/consensus/mod.rs:424-435, around the
+ * polish of `polish_seg` :437-443, :490-494; per node in `PolishChunk::consensus_chunk`, polish_chunks.rs:114-120): the
+ * unit-cost alignment ops of every read of every chunk against that chunk's template, which the entry points above take as
+ * input.  Among the optimal alignments the one of DESIGN.md section 4 is returned (walk from the end; diagonal, then Del,
+ * then Ins); parity with edlib's own tie-breaking is not pinned.  chunks / tmpl_bases / read_bases / read_off as in
+ * jtk_lc_polish_chunks; copy_num and chunk_id are ignored.
+ * ops_out     : ops of read r at ops_out_off[r] .. ops_out_off[r+1], capacity ops_cap bytes (sum(tmpl_len + read_len) over
+ *               the reads is always enough; JTK_ERR_INVALID_ARG rather than an overrun when it is too small).
+ * dist_out[r] : the edit distance of read r.
+ * max_dist    : 0 = unbounded (sequences up to 32,000 bases each are taken).  A read farther from its template than
+ *               max_dist, or longer than that cap, gets read_status[r] = JTK_ERR_UNSUPPORTED, dist_out[r] = UINT32_MAX and
+ *               an empty op slot; the call then returns JTK_ERR_CHUNK_FAILED and every other read is aligned. */
+JTK_LC_API int jtk_lc_align_reads(size_t n_chunks, const jtk_lc_chunk_t *chunks, const uint8_t *tmpl_bases,
+                       const uint8_t *read_bases, const uint64_t *read_off, uint32_t max_dist,
+                       uint8_t *ops_out, uint64_t *ops_out_off, uint64_t ops_cap,
+                       uint32_t *dist_out, int32_t *read_status, int device);
 
 /* ---- resident-batch form of the same call ----------------------------------------------------------
  * jtk_lc_cluster_chunks == session_create + session_run(0) + session_fetch + session_destroy.

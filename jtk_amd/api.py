@@ -74,6 +74,25 @@ def polish_chunks(params, batch, radius=0, take_num=0, ignore_edge=0, device=0, 
     return o
 
 
+def align_reads(batch, max_dist=0, device=0, raise_on_read_failure=True):
+    """jtk_lc_align_reads: global unit-cost alignment of every read of `batch` to its chunk's template (the batch's own ops
+    are not looked at).  -> dict(ops, ops_off, dist, status, rc); `batch.with_ops(out["ops"], out["ops_off"])` carries them
+    into polish_chunks / cluster_chunks."""
+    L = ffi.lib()
+    n = batch.n_reads
+    cap = int(len(batch.read_bases)) + int((batch.chunks["tmpl_len"] * batch.chunks["n_reads"]).sum()) + 64
+    ops = np.zeros(cap, dtype=np.uint8)
+    ops_off = np.zeros(n + 1, dtype=np.uint64)
+    dist = np.zeros(n, dtype=np.uint32)
+    status = np.zeros(n, dtype=np.int32)
+    rc = L.jtk_lc_align_reads(batch.n_chunks, batch.chunks.ctypes.data, u8p(batch.tmpl_bases), u8p(batch.read_bases),
+                              u64p(batch.read_off), int(max_dist), u8p(ops), u64p(ops_off), cap, u32p(dist),
+                              status.ctypes.data_as(C.POINTER(C.c_int32)), device)
+    if rc != 0 and (raise_on_read_failure or rc != -6):
+        check(rc)
+    return dict(ops=ops[:int(ops_off[n])] if rc in (0, -6) else ops[:0], ops_off=ops_off, dist=dist, status=status, rc=rc)
+
+
 def modification_table(params, tmpl, reads, ops, strands, device=0):
     """jtk_lc_modification_table for one pile-up -> (table [n, 14*(L+1)] minus lk, lk [n])."""
     L = ffi.lib()

@@ -71,6 +71,15 @@ class Batch:
     def read_ops(self, r):
         return self.ops[int(self.ops_off[r]):int(self.ops_off[r + 1])]
 
+    def with_ops(self, ops, ops_off):
+        """A copy of the batch that carries other alignment ops (those of api.align_reads)."""
+        ops_off = np.ascontiguousarray(ops_off, dtype=np.uint64)
+        if len(ops_off) != self.n_reads + 1:
+            raise ValueError("with_ops: ops_off must have n_reads + 1 entries")
+        return Batch(chunks=self.chunks.copy(), tmpl_bases=self.tmpl_bases, read_bases=self.read_bases, read_off=self.read_off,
+                     ops=np.ascontiguousarray(ops, dtype=np.uint8)[:int(ops_off[-1])].copy(), ops_off=ops_off,
+                     strand=self.strand, truth=self.truth)
+
     def subset(self, idx):
         """Batch made of the chunks `idx` (re-packed)."""
         return pack([(int(self.chunks[c]["chunk_id"]), int(self.chunks[c]["copy_num"]), self.template(c),

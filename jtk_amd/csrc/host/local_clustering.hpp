@@ -140,6 +140,33 @@ inline Ops kiley_op_to_ops(const uint8_t *k, size_t n) {
     return ops;
 }
 
+// `global_align` (consensus/mod.rs:424-435; per node in polish_chunks.rs:114-120) for one pile-up: the cigar of every read
+// against `tmpl`, through one jtk_lc_align_reads call.
+inline std::vector<Ops> global_align(const std::string &tmpl, const std::vector<std::string> &reads, int device = 0) {
+    jtk_lc_chunk_t ch{};
+    ch.n_reads = (uint32_t)reads.size();
+    ch.tmpl_len = tmpl.size();
+    std::vector<uint8_t> bases;
+    std::vector<uint64_t> off(reads.size() + 1, 0);
+    for (size_t r = 0; r < reads.size(); r++) {
+        bases.insert(bases.end(), reads[r].begin(), reads[r].end());
+        off[r + 1] = bases.size();
+    }
+    bases.push_back(0);  // keeps data() non-null for a pile-up of empty reads
+    const uint64_t cap = bases.size() + tmpl.size() * reads.size() + 1;
+    std::vector<uint8_t> ops(cap);
+    std::vector<uint64_t> ops_off(reads.size() + 1);
+    std::vector<uint32_t> dist(reads.size() + 1);
+    std::vector<int32_t> status(reads.size() + 1);
+    const std::string t = tmpl.empty() ? std::string(1, '\0') : tmpl;
+    const int rc = jtk_lc_align_reads(1, &ch, (const uint8_t *)t.data(), bases.data(), off.data(), 0, ops.data(), ops_off.data(), cap,
+                                      dist.data(), status.data(), device);
+    if (rc != 0) throw std::runtime_error(std::string("global_align: ") + jtk_lc_strerror(rc) + ": " + jtk_lc_last_error());
+    std::vector<Ops> out;
+    for (size_t r = 0; r < reads.size(); r++) out.push_back(kiley_op_to_ops(ops.data() + ops_off[r], (size_t)(ops_off[r + 1] - ops_off[r])));
+    return out;
+}
+
 // misc.rs:394-407
 inline void update_coverage(DataSet &ds) {
     if (ds.coverage.is_protected()) return;

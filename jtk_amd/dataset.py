@@ -303,6 +303,29 @@ def local_clustering_selected(ds, selection, gains=None, device=0, failed=None, 
     return ds
 
 
+def realign_selected(ds, selection, device=0):
+    """What PolishChunk::consensus_chunk does per node once a chunk has its sequence (polish_chunks.rs:114-120): every node of
+    the selected chunks is aligned globally to chunk.seq (jtk_lc_align_reads) and its cigar replaced.  For a file whose
+    cigars no longer fit their chunks (a chunk was re-polished, a consensus written back)."""
+    validate(ds)
+    selection = set(selection)
+    chunk_of = {c["id"]: c for c in ds["selected_chunks"] if c["id"] in selection}
+    piles = {cid: [] for cid in chunk_of}
+    for read in ds["encoded_reads"]:
+        for node in read["nodes"]:
+            if node["chunk"] in piles:
+                piles[node["chunk"]].append(node)
+    order = sorted(cid for cid, nodes in piles.items() if nodes)
+    none = np.zeros(0, dtype=np.uint8)
+    batch = pack([(cid, int(chunk_of[cid]["copy_num"]), _seq(chunk_of[cid]["seq"]), [_seq(n["seq"]) for n in piles[cid]],
+                   [none] * len(piles[cid]), [1 if n["is_forward"] else 0 for n in piles[cid]], None) for cid in order])
+    out = api.align_reads(batch, device=device)
+    for c, cid in enumerate(order):
+        for r, node in zip(batch.chunk_reads(c), piles[cid]):
+            node["cigar"] = ops_to_cigar(out["ops"][int(out["ops_off"][r]):int(out["ops_off"][r + 1])])
+    return ds
+
+
 def local_clustering(ds, gains=None, device=0, failed=None, refit=True, record=None, trace=None):
     """mod.rs:23-26: every selected chunk."""
     validate(ds)
@@ -423,8 +446,9 @@ def correct_clustering(ds, device=0, min_gain=None):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--stage", default="local_clustering", choices=("local_clustering", "correct_clustering"),
-                    help="which JTK stage to run on the file (jtk local_clustering / jtk correct_clustering)")
+    ap.add_argument("--stage", default="local_clustering", choices=("local_clustering", "correct_clustering", "realign"),
+                    help="which JTK stage to run on the file (jtk local_clustering / jtk correct_clustering); realign: "
+                         "replace every node's cigar by its global alignment to the chunk sequence")
     ap.add_argument("input", help="DataSet JSON ('-' = stdin)")
     ap.add_argument("output", help="DataSet JSON ('-' = stdout)")
     ap.add_argument("--chunks", default="", help="comma-separated chunk ids (local_clustering_selected); default: all")
@@ -450,6 +474,10 @@ def main(argv=None):
             correct_clustering_selected(ds, [int(x) for x in args.chunks.split(",")], device=args.device)
         else:
             correct_clustering(ds, device=args.device)
+    elif args.stage == "realign":
+        validate(ds)
+        realign_selected(ds, [int(x) for x in args.chunks.split(",")] if args.chunks else [c["id"] for c in ds["selected_chunks"]],
+                         device=args.device)
     elif args.chunks:
         local_clustering_selected(ds, [int(x) for x in args.chunks.split(",")], device=args.device, failed=failed,
                                   refit=not args.no_refit, record=record, trace=trace)

@@ -77,6 +77,11 @@ extern "C" {
         ops: *const u8, ops_off: *const u64, strand: *const u8, radius: u32, take_num: u32, ignore_edge: u32,
         cons_out: *mut u8, cons_off: *mut u64, cons_cap: u64,
         ops_out: *mut u8, ops_out_off: *mut u64, ops_cap: u64, result: *mut JtkLcResult, device: c_int) -> c_int;
+    // edlib Global / Alignment of every read to its chunk's template (consensus/mod.rs:424-435, polish_chunks.rs:114-120)
+    pub fn jtk_lc_align_reads(
+        n_chunks: usize, chunks: *const JtkLcChunk, tmpl_bases: *const u8, read_bases: *const u8, read_off: *const u64,
+        max_dist: u32, ops_out: *mut u8, ops_out_off: *mut u64, ops_cap: u64,
+        dist_out: *mut u32, read_status: *mut i32, device: c_int) -> c_int;
     // AlignmentCorrection::correct_clustering_selected (phmm_likelihood_correction.rs:32-97)
     pub fn jtk_lc_correct_clustering(
         n_reads: usize, read_id: *const u64, node_off: *const u64, nodes: *const JtkCcNode, posteriors: *const f64,
