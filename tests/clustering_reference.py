@@ -1,0 +1,1049 @@
+"""An independent restatement of the read clustering itself, in plain Python (test infrastructure).
+
+Written from the Rust alone -- haplotyper/src/local_clustering/pseudo_mcmc.rs (clustering :77-107, cluster_filtered_variants
+:213-274, min_gain :276-284, expected_gains :286-306, count_improved_reads :308-312, is_explainable_by_strandedness :314-339,
+to_posterior_probability :342-347, get_likelihood_gain :353-379, get_read_lk_gains :381-408, filter_profiles :426-474,
+has_small_pvalue :476-495, is_in_short_homopolymer :497-514, mcmc_clustering :649-670, use_highest_gain :673-693, mcmc_with_filter
+:704-762, flip :764-783, get_lk :785-795, LKCount :797-845, get_used_columns :847-869), misc.rs (logsumexp :84-92, kmeans
+:229-341), likelihood_gains.rs (Gains::expected :79-87, pvalues :88-137) and mod.rs:97 (the chunk's seed) -- and NOT from
+oracle/pseudo_mcmc.c, oracle/local_clustering.c, oracle/misc.c or jtk_amd/csrc/mcmc_kernels.hip, none of which was open while
+this was written: they were written by one hand from one reading, and this is the second reading.  No text of the reference is
+copied; it is a restatement in another language, shaped differently wherever the Rust allows (parallel lists for LKCount, one
+prefix table for ln c!, integers for the generator).
+
+Every floating-point operation and its ORDER is the Rust's: sums run left to right from 0.0 in explicit loops (never Python's
+sum(), never numpy reductions), x.powi(2) is x * x, f64::max ignores a NaN operand.  (An EMPTY f64 sum is taken as +0.0, the
+value of the toolchains the reference was written with; since Rust 1.83 it is -0.0, which is visible only as the sign of a zero
+log-posterior of a single-cluster result.)  exp and ln are a parameter:
+    LibmMath      math.exp / math.log, what a Rust build calls on this platform
+    ProjectMath   include/jtk_math.h through the oracle's jo_exp / jo_log (pinned within one ulp of libm by
+                  tests/test_oracle_pinning.py).  With it the oracle and the kernels are expected to agree with this file bit for
+                  bit and draw for draw.
+With libm an acceptance can flip on a last-bit difference, so every run records in its log the smallest distance of any decision
+from its threshold (`margin`: |diff| of a proposal, |u - p| of a gen_bool, |max - lk|, the restarts' and the k = 2
+alternative's score comparisons, the stop rule, the tail's + 0.001 comparison; exact ties, which no rounding separates when
+both sides are computed from equal operands, are counted apart as `exact_ties`).
+
+The generator: rand_xoshiro 0.6.0 Xoshiro256StarStar (seed_from_u64 = four SplitMix64 outputs; next_u64 = rotl(s1 * 5, 7) * 9
+with the xoshiro256 state step; next_u32 = the HIGH half of next_u64) under correction_reference.Rand085, which states rand 0.8.5's
+gen_bool / gen_range / gen_index / choose / choose_weighted over any core and, for this file, IteratorRandom::choose on a Filter
+(size_hint (0, Some(k)): the reservoir path, one gen_index(consumed) per surviving element -- gen_index(1) still draws, and rejects
+half of its draws).  The crates themselves are not on the build machine: parity with them stays pinned by the published
+xoshiro256** known-answer vector only (tests/test_clustering_reference.py::test_generator_known_answers).
+
+A reference panic (assert!, unwrap on None / Err, partial_cmp on a NaN, Bernoulli::new outside [0, 1]) raises ReferencePanic.
+"""
+import math
+
+import numpy as np
+
+from correction_reference import M64, Rand085, ReferencePanic, _require, _rotl
+
+MASK_LENGTH, MAX_HOMOP_LENGTH, POS_THR = 7, 2, 0.00001   # pseudo_mcmc.rs:3-5
+NUM_ROW, COPY_SIZE = 14, 3                                # kiley::hmm (pseudo_mcmc.rs:7,172,447)
+SUBST, DEL, INS = 0, 1, 2                                 # likelihood_gains.rs:194-199, declaration order
+NAN, INF = float("nan"), float("inf")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# generator
+# ---------------------------------------------------------------------------------------------------------------------------
+class Xoshiro256StarStar:
+    def __init__(self, s):
+        self.s0, self.s1, self.s2, self.s3 = s
+        self.draws = 0   # next_u64 calls so far
+
+    @classmethod
+    def seed_from_u64(cls, seed):
+        out, x = [], seed & M64
+        for _ in range(4):   # SplitMix64
+            x = (x + 0x9E3779B97F4A7C15) & M64
+            z = x
+            z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
+            z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
+            out.append(z ^ (z >> 31))
+        return cls(out)
+
+    def next_u64(self):
+        s0, s1, s2, s3 = self.s0, self.s1, self.s2, self.s3
+        x = (s1 * 5) & M64
+        r = ((((x << 7) | (x >> 57)) & M64) * 9) & M64
+        t = (s1 << 17) & M64
+        s2 ^= s0
+        s3 ^= s1
+        s1 ^= s2
+        s0 ^= s3
+        s2 ^= t
+        self.s0, self.s1, self.s2, self.s3 = s0, s1, s2, _rotl(s3, 45)
+        self.draws += 1
+        return r
+
+    def next_u32(self):
+        return self.next_u64() >> 32
+
+    def state(self):
+        return (self.s0, self.s1, self.s2, self.s3)
+
+
+def chunk_rng(chunk_id):
+    """mod.rs:97: SeedableRng::seed_from_u64(ref_chunk.id * 3490)"""
+    return Rand085(Xoshiro256StarStar.seed_from_u64((chunk_id * 3490) & M64))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# exp / ln back ends
+# ---------------------------------------------------------------------------------------------------------------------------
+class LibmMath:
+    name = "libm"
+
+    @staticmethod
+    def exp(x):
+        try:
+            return math.exp(x)
+        except OverflowError:
+            return INF
+
+    @staticmethod
+    def log(x):
+        if x != x or x < 0.0:
+            return NAN
+        return -INF if x == 0.0 else math.log(x)
+
+
+class ProjectMath:
+    """include/jtk_math.h as the oracle exports it"""
+    name = "project"
+
+    def __init__(self):
+        import oracle_ffi
+        L = oracle_ffi.lib()
+        self.exp, self.log = L.jo_exp, L.jo_log
+
+
+def _fmax(a, b):
+    """f64::max: a NaN operand is ignored"""
+    if b != b:
+        return a
+    if a != a:
+        return b
+    return a if a > b else b
+
+
+def _cmp_ok(*xs):
+    for x in xs:
+        _require(x == x, "partial_cmp(..).unwrap() on a NaN")
+
+
+class Gains:
+    """likelihood_gains.rs:55-61 with expected :79-87; tables are [(gain, prob), ...] per homopolymer length"""
+
+    def __init__(self, subst, deletions, insertions):
+        self.tab = {SUBST: list(subst), DEL: list(deletions), INS: list(insertions)}
+        self.max_homopolymer_len = len(self.tab[SUBST])
+
+    @classmethod
+    def from_params(cls, p):
+        m = int(p.gains.max_homopolymer_len)
+        f = lambda arr: [(float(arr[i].gain), float(arr[i].prob)) for i in range(m)]
+        return cls(f(p.gains.subst), f(p.gains.deletions), f(p.gains.insertions))
+
+    def expected(self, homop_len, diff_type):
+        _require(0 < homop_len, "Gains::expected: assert 0 < homop_len")
+        return self.tab[diff_type][min(homop_len, self.max_homopolymer_len) - 1][0]
+
+
+class Log:
+    """what a run leaves behind besides its results"""
+
+    def __init__(self):
+        self.margin, self.exact_ties = INF, 0
+        self.tried = []          # per tried k: dict(k, score, expected_gain, improved, used_columns, sizes, accepted, source, ...)
+        self.range = None
+        self.last_restarts = None   # of the latest mcmc_clustering: scores, the restart kept, ties
+        self.early_return = None
+        self.chain = dict(proposals=0, zero_diff=0, uphill=0, downhill_taken=0, rejected=0, best_not_last=0, emptied=0, chains=0,
+                          dataless_moves=0)
+        self.kmeans = dict(random_start=0, seeded_start=0, zero_weights=0, rounds=0)
+        self.tail = dict(changed=0, within_margin=0)
+        self.draws = 0
+
+    def decide(self, lhs, rhs):
+        d = abs(lhs - rhs)
+        if d == 0.0:
+            self.exact_ties += 1
+        elif d < self.margin:
+            self.margin = d
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# misc.rs
+# ---------------------------------------------------------------------------------------------------------------------------
+def logsumexp(xs, B):
+    """misc::logsumexp :84-92"""
+    if len(xs) == 0:
+        return 0.0
+    _cmp_ok(*xs)
+    m = max(xs)
+    s = 0.0
+    for x in xs:
+        s += B.exp(x - m)
+    s = B.log(s)
+    _require(s >= 0.0, "logsumexp: assert sum >= 0")
+    return m + s
+
+
+def _dist(xs, ys):
+    """misc::dist :308-313"""
+    s = 0.0
+    for x, y in zip(xs, ys):
+        d = x - y
+        s += d * d
+    return s
+
+
+def _update_assignments(data, centers, asn):
+    """:261-276; min_by keeps the FIRST minimum"""
+    for i, xs in enumerate(data):
+        best, best_d = 0, None
+        for c, cs in enumerate(centers):
+            d = _dist(xs, cs)
+            if best_d is None:
+                best, best_d = c, d
+            else:
+                _cmp_ok(d, best_d)
+                if d < best_d:
+                    best, best_d = c, d
+        asn[i] = best
+
+
+def _get_dist(data, centers, asn):
+    """:298-307"""
+    s = 0.0
+    for xs, a in zip(data, asn):
+        s += _dist(xs, centers[a])
+    return s
+
+
+UPDATE_THR = 0.00000001
+
+
+def kmeans(data, k, rng, log=None):
+    """misc::kmeans :229-259 with suggest_first :315-341 and update_centers :277-297; data is a list of equally long lists"""
+    _require(1 <= k, "kmeans: assert 1 <= k")
+    n, dim = len(data), len(data[0])
+    _require(0 < dim, "kmeans: assert 0 < dim")
+    if rng.gen_bool(0.5):
+        asn = [rng.gen_range(k) for _ in range(n)]
+        if log:
+            log.kmeans["random_start"] += 1
+    else:
+        _require(k <= n, "suggest_first: assert k <= len")
+        centers = [data[rng.choose(n)]]
+        for _ in range(k - 1):
+            dists = []
+            for xs in data:
+                best = None
+                for cs in centers:
+                    d = _dist(xs, cs)
+                    if best is None:
+                        best = d
+                    else:
+                        _cmp_ok(d, best)
+                        if d < best:
+                            best = d
+                dists.append(best)
+            idx = rng.choose_weighted(dists)
+            _require(idx is not None, "choose_weighted(..).unwrap(): WeightedError")
+            if log and any(d == 0.0 for d in dists):
+                log.kmeans["zero_weights"] += 1
+            centers.append(data[idx])
+        asn = [0] * n
+        _update_assignments(data, centers, asn)
+        if log:
+            log.kmeans["seeded_start"] += 1
+    centers = [[0.0] * dim for _ in range(k)]
+    dist = _get_dist(data, centers, asn)
+    while True:
+        counts = [0] * k
+        for cs in centers:
+            for d in range(dim):
+                cs[d] = 0.0
+        for a, xs in zip(asn, data):
+            cs = centers[a]
+            for d in range(dim):
+                cs[d] += xs[d]
+            counts[a] += 1
+        for cs, c in zip(centers, counts):
+            if 0 < c:
+                for d in range(dim):
+                    cs[d] /= float(c)
+        _update_assignments(data, centers, asn)
+        new_dist = _get_dist(data, centers, asn)
+        if log:
+            log.kmeans["rounds"] += 1
+        _require(new_dist < dist + UPDATE_THR, "kmeans: assert new_dist < dist + UPDATE_THR")
+        if dist - new_dist < UPDATE_THR:
+            break
+        dist = new_dist
+    return dist, asn
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# pseudo_mcmc.rs: the counts
+# ---------------------------------------------------------------------------------------------------------------------------
+class Counts:
+    """k x dim LKCount (:797-845) as parallel lists, and the cluster sizes"""
+
+    def __init__(self, k, dim):
+        self.k, self.dim = k, dim
+        self.gain = [[0.0] * dim for _ in range(k)]
+        self.pos = [[0] * dim for _ in range(k)]
+        self.neg = [[0] * dim for _ in range(k)]
+        self.zero = [[0] * dim for _ in range(k)]
+        self.size = [0] * k
+
+    def add(self, c, xs):
+        g, p, m, z = self.gain[c], self.pos[c], self.neg[c], self.zero[c]
+        for d, x in enumerate(xs):
+            g[d] += x
+            if POS_THR < x:
+                p[d] += 1
+            elif x < -POS_THR:
+                m[d] += 1
+            else:
+                _require(abs(x) < POS_THR, "LKCount::add: assert x.abs() < POS_THR")
+                z[d] += 1
+
+    def sub(self, c, xs):
+        g, p, m, z = self.gain[c], self.pos[c], self.neg[c], self.zero[c]
+        for d, x in enumerate(xs):
+            g[d] -= x
+            if POS_THR < x:
+                p[d] -= 1
+            elif x < -POS_THR:
+                m[d] -= 1
+            else:
+                _require(abs(x) < POS_THR, "LKCount::sub: assert x.abs() < POS_THR")
+                z[d] -= 1
+
+    @classmethod
+    def of(cls, data, asn, k):
+        self = cls(k, len(data[0]))
+        for xs, a in zip(data, asn):
+            self.size[a] += 1
+            self.add(a, xs)
+        return self
+
+
+POS_FRAC, IN_POS_RATIO = 0.70, 2.0
+
+
+def get_used_columns(cn):
+    """:847-869 with LKCount::is_informative :818-822"""
+    used = []
+    for d in range(cn.dim):
+        use, in_use, in_neg = False, 0, 0
+        for c in range(cn.k):
+            g, p = cn.gain[c][d], cn.pos[c][d]
+            cov = float(p + cn.neg[c][d]) + 0.0000001
+            if 0.0 < g and POS_FRAC < float(p) / cov:
+                use = True
+            if 0.0 < g:
+                in_use += p
+            if g <= 0.0:
+                in_neg += p
+        used.append(use and float(in_neg) * IN_POS_RATIO < float(in_use))
+    return used
+
+
+def get_lk(cn, size_to_lk):
+    """:785-795"""
+    used = get_used_columns(cn)
+    lk = 0.0
+    for s in cn.size:
+        lk += size_to_lk[s]
+    for c in range(cn.k):
+        g = cn.gain[c]
+        for d in range(cn.dim):
+            if used[d]:
+                lk += _fmax(g[d], 0.0)
+    return lk
+
+
+def poisson_lk(x, lam, B, lnfact):
+    """:636-638; lnfact[x] = ln 1 + ... + ln x summed left to right"""
+    return float(x) * B.log(lam) - lam - lnfact[x]
+
+
+def ln_factorials(n, B):
+    out, s = [0.0], 0.0
+    for c in range(1, n + 1):
+        s += B.log(float(c))
+        out.append(s)
+    return out
+
+
+def max_poisson_lk(x, lam, c_start, c_end, B, lnfact):
+    """:641-645"""
+    best = -INF
+    for c in range(max(c_start, 1), c_end + 1):
+        best = _fmax(best, poisson_lk(x, lam * float(c), B, lnfact))
+    return best
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the chain
+# ---------------------------------------------------------------------------------------------------------------------------
+def mcmc_with_filter_plain(data, asn, k, cov, rng, B):
+    """:704-762 once more, through the helpers of this file (Rand085, Counts, get_lk) and as the Rust is laid out.  The loop of
+    mcmc_with_filter below is the same computation with everything written out for speed;
+    tests/test_clustering_reference.py::test_inlined_chain_is_the_plain_one holds the two together."""
+    n = len(data)
+    lnfact = ln_factorials(n, B)
+    size_to_lk = [max_poisson_lk(x, cov, 1, k, B, lnfact) for x in range(n + 1)]
+    _require(all(x == x for x in size_to_lk), "mcmc_with_filter: assert is_valid_lk")
+    cn = Counts.of(data, asn, k)
+    lk = get_lk(cn, size_to_lk)
+    best, argmax = lk, list(asn)
+    for _ in range(2000 * n):
+        idx = rng.gen_range(n)
+        old = asn[idx]
+        new = rng.choose_iter(c for c in range(k) if c != old)
+        _require(new is not None, "choose(..).unwrap() on no element")
+        for frm, to in ((old, new),):
+            cn.size[frm] -= 1
+            cn.sub(frm, data[idx])
+            asn[idx] = to
+            cn.size[to] += 1
+            cn.add(to, data[idx])
+        proposed = get_lk(cn, size_to_lk)
+        diff = proposed - lk
+        if 0.0 < diff or rng.gen_bool(B.exp(diff)):
+            lk = proposed
+            if best < lk:
+                best, argmax = proposed, list(asn)
+        else:
+            cn.size[new] -= 1
+            cn.sub(new, data[idx])
+            asn[idx] = old
+            cn.size[old] += 1
+            cn.add(old, data[idx])
+    asn[:] = argmax
+    _require(abs(best - get_lk(Counts.of(data, asn, k), size_to_lk)) < 0.0001, "mcmc_with_filter: assert (max - lk).abs() < 0.0001")
+    return best
+
+
+def mcmc_with_filter(data, asn, k, cov, rng, B, log=None):
+    """:704-762 with flip :764-783 and get_lk :785-795 written out in the loop (this is where the time goes: the generator's
+    state, the counts and the decision margins are locals); `asn` is updated in place, the maximum is returned.  The zero-band
+    assert of LKCount::add fires, if at all, while the counts are first built: every row is added there once."""
+    log = log or Log()
+    n, dim = len(data), len(data[0])
+    lnfact = ln_factorials(n, B)
+    size_to_lk = [max_poisson_lk(x, cov, 1, k, B, lnfact) for x in range(n + 1)]
+    _require(all(x == x for x in size_to_lk), "mcmc_with_filter: assert is_valid_lk")
+    cn = Counts.of(data, asn, k)
+    lk = get_lk(cn, size_to_lk)
+    best, argmax = lk, list(asn)
+    gain, pos, neg, size = cn.gain, cn.pos, cn.neg, cn.size
+    sign = [[1 if POS_THR < x else (-1 if x < -POS_THR else 0) for x in xs] for xs in data]
+    others = [[c for c in range(k) if c != old] for old in range(k)]
+    core, exp = rng.core, B.exp
+    s0, s1, s2, s3 = core.s0, core.s1, core.s2, core.s3
+    draws = 0
+    zone = ((n << (64 - n.bit_length())) - 1) & M64                       # gen_range(0..n) on usize
+    zones32 = [0] + [((m << (32 - m.bit_length())) - 1) & 0xFFFFFFFF for m in range(1, k)]   # gen_index(m), m = 1 .. k - 1
+    cols, clusters = range(dim), range(k)
+    margin, ties = INF, 0
+    zero_diff = uphill = downhill = rejected = emptied = 0
+    for _ in range(2000 * n):
+        while True:                                                         # idx = rng.gen_range(0..n)
+            x = (s1 * 5) & M64
+            r = ((((x << 7) | (x >> 57)) & M64) * 9) & M64
+            t = (s1 << 17) & M64
+            s2 ^= s0
+            s3 ^= s1
+            s1 ^= s2
+            s0 ^= s3
+            s2 ^= t
+            s3 = ((s3 << 45) | (s3 >> 19)) & M64
+            draws += 1
+            m = r * n
+            if (m & M64) <= zone:
+                idx = m >> 64
+                break
+        old = asn[idx]
+        new, consumed = None, 0                                             # (0..k).filter(|&c| c != old).choose(rng)
+        for elem in others[old]:
+            consumed += 1
+            z32 = zones32[consumed]
+            while True:
+                x = (s1 * 5) & M64
+                r = ((((x << 7) | (x >> 57)) & M64) * 9) & M64
+                t = (s1 << 17) & M64
+                s2 ^= s0
+                s3 ^= s1
+                s1 ^= s2
+                s0 ^= s3
+                s2 ^= t
+                s3 = ((s3 << 45) | (s3 >> 19)) & M64
+                draws += 1
+                m = (r >> 32) * consumed
+                if (m & 0xFFFFFFFF) <= z32:
+                    break
+            if (m >> 32) == 0:
+                new = elem
+        _require(new is not None, "choose(..).unwrap() on no element")
+        xs, sg = data[idx], sign[idx]
+        go, gn, po, pn, no, nn = gain[old], gain[new], pos[old], pos[new], neg[old], neg[new]
+        size[old] -= 1
+        size[new] += 1
+        for d in cols:
+            x = xs[d]
+            go[d] -= x
+            gn[d] += x
+            c = sg[d]
+            if c > 0:
+                po[d] -= 1
+                pn[d] += 1
+            elif c < 0:
+                no[d] -= 1
+                nn[d] += 1
+        proposed = 0.0                                                      # get_lk
+        for s in size:
+            proposed += size_to_lk[s]
+        used = []
+        for d in cols:
+            use, in_use, in_neg = False, 0, 0
+            for c in clusters:
+                g, p = gain[c][d], pos[c][d]
+                if 0.0 < g:
+                    in_use += p
+                    if POS_FRAC < float(p) / (float(p + neg[c][d]) + 0.0000001):
+                        use = True
+                elif g <= 0.0:
+                    in_neg += p
+            used.append(use and float(in_neg) * IN_POS_RATIO < float(in_use))
+        for c in clusters:
+            gc = gain[c]
+            for d in cols:
+                if used[d]:
+                    g = gc[d]
+                    proposed += g if g > 0.0 else 0.0                       # total_gain.max(0.0); no NaN past Counts.of
+        diff = proposed - lk
+        if diff != 0.0:
+            a = diff if diff > 0.0 else -diff
+            if a < margin:
+                margin = a
+        if 0.0 < diff:
+            take = True
+            uphill += 1
+        else:
+            p = exp(diff)
+            if p == 1.0:
+                take = True                                                 # gen_bool(1.0) draws nothing
+                zero_diff += 1
+            else:
+                _require(0.0 <= p < 1.0, "gen_bool: Bernoulli::new(p).unwrap() with p outside [0, 1]")
+                p_int = int(p * 18446744073709551616.0)
+                x = (s1 * 5) & M64
+                r = ((((x << 7) | (x >> 57)) & M64) * 9) & M64
+                t = (s1 << 17) & M64
+                s2 ^= s0
+                s3 ^= s1
+                s1 ^= s2
+                s0 ^= s3
+                s2 ^= t
+                s3 = ((s3 << 45) | (s3 >> 19)) & M64
+                draws += 1
+                take = r < p_int
+                a = abs(r - p_int) / 18446744073709551616.0
+                if a == 0.0:
+                    ties += 1
+                elif a < margin:
+                    margin = a
+                if take:
+                    downhill += 1
+                else:
+                    rejected += 1
+        if take:
+            lk = proposed
+            if size[old] == 0:
+                emptied += 1
+            if best != lk:
+                a = abs(best - lk)
+                if a < margin:
+                    margin = a
+            if best < lk:
+                best = proposed
+                argmax[:] = asn
+                argmax[idx] = new
+            asn[idx] = new
+        else:
+            size[new] -= 1
+            size[old] += 1
+            for d in cols:
+                x = xs[d]
+                gn[d] -= x
+                go[d] += x
+                c = sg[d]
+                if c > 0:
+                    pn[d] -= 1
+                    po[d] += 1
+                elif c < 0:
+                    nn[d] -= 1
+                    no[d] += 1
+    core.s0, core.s1, core.s2, core.s3 = s0, s1, s2, s3
+    core.draws += draws
+    st = log.chain
+    st["chains"] += 1
+    st["proposals"] += 2000 * n
+    for key, v in (("zero_diff", zero_diff), ("uphill", uphill), ("downhill_taken", downhill), ("rejected", rejected), ("emptied", emptied)):
+        st[key] += v
+    log.exact_ties += ties
+    if margin < log.margin:
+        log.margin = margin
+    if argmax != asn:
+        st["best_not_last"] += 1
+    asn[:] = argmax
+    lk = get_lk(Counts.of(data, asn, k), size_to_lk)
+    _require(abs(best - lk) < 0.0001, "mcmc_with_filter: assert (max - lk).abs() < 0.0001")
+    return best
+
+
+def get_read_lk_gains(data, asn, k):
+    """:381-408"""
+    cn = Counts.of(data, asn, k)
+    used = get_used_columns(cn)
+    gains = []
+    for xs, a in zip(data, asn):
+        s, g = 0.0, cn.gain[a]
+        for d, x in enumerate(xs):
+            if used[d] and POS_THR < g[d]:
+                s += x
+        gains.append(s)
+    return used, gains
+
+
+def get_likelihood_gain(data, asn, k):
+    """:353-379"""
+    cn = Counts.of(data, asn, k)
+    used = get_used_columns(cn)
+    out = []
+    for xs in data:
+        row = []
+        for c in range(k):
+            s, g = 0.0, cn.gain[c]
+            for d, x in enumerate(xs):
+                if used[d] and POS_THR < g[d]:
+                    s += x
+            row.append(s)
+        out.append(row)
+    return out
+
+
+def mcmc_clustering(data, k, cov, rng, B, log=None):
+    """:649-670: 20 restarts, max_by keeps the LAST maximum; returns (assignment, score, read gains, used columns)"""
+    log = log or Log()
+    runs = []
+    for _ in range(20):
+        asn = kmeans(data, k, rng, log)[1]
+        lk = mcmc_with_filter(data, asn, k, cov, rng, B, log)
+        runs.append((asn, lk))
+    pick = 0
+    for r in range(1, 20):
+        _cmp_ok(runs[r][1], runs[pick][1])
+        if runs[r][1] >= runs[pick][1]:
+            pick = r
+    for r in range(20):
+        if r != pick:
+            log.decide(runs[r][1], runs[pick][1])
+    asn, score = runs[pick]
+    used, gains = get_read_lk_gains(data, asn, k)
+    counts = [0] * k
+    for a in asn:
+        counts[a] += 1
+    lnfact = ln_factorials(len(data), B)
+    cluster_lk = 0.0
+    for c in counts:
+        cluster_lk += max_poisson_lk(c, cov, 1, k, B, lnfact)
+    log.last_restarts = dict(scores=[r[1] for r in runs], pick=pick,
+                                 first_max=min(r for r in range(20) if runs[r][1] == runs[pick][1]),
+                                 distinct_at_max=len({tuple(r[0]) for r in runs if r[1] == runs[pick][1]}),
+                                 first_max_differs=next(list(r[0]) for r in runs if r[1] == runs[pick][1]) != list(runs[pick][0]))
+    return asn, score - cluster_lk, gains, used
+
+
+def use_highest_gain(data):
+    """:673-693"""
+    dim = len(data[0])
+    gains = [0.0] * dim
+    for xs in data:
+        for d, x in enumerate(xs):
+            gains[d] += _fmax(x, 0.0)
+    _cmp_ok(*gains)
+    top = 0
+    for d in range(1, dim):
+        if gains[d] >= gains[top]:   # max_by: the last maximum
+            top = d
+    asn = [1 if 0.0 < xs[top] else 0 for xs in data]
+    used, lk_gains = get_read_lk_gains(data, asn, 2)
+    score = 0.0
+    for g in lk_gains:
+        score += g
+    return asn, score, lk_gains, used
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the choice of the cluster count
+# ---------------------------------------------------------------------------------------------------------------------------
+def min_gain(gains, variant_type, used):
+    """:276-284"""
+    best = None
+    for (homop, dt), u in zip(variant_type, used):
+        if u:
+            g = gains.expected(homop, dt) / 3.0
+            if best is None:
+                best = g
+            else:
+                _cmp_ok(g, best)
+                if g < best:
+                    best = g
+    return 1.0 if best is None else best
+
+
+EXPT_GAIN_FACTOR = 0.8
+
+
+def expected_gains(gains, variant_type, prev, used):
+    """:286-306"""
+    _require(len(variant_type) == len(used), "expected_gains: assert_eq lengths")
+    no_new = list(prev) == list(used)
+    best = None
+    for (homop, dt), p, c in zip(variant_type, prev, used):
+        g = gains.expected(homop, dt) if ((not p and c) or no_new) else 0.0000001
+        if best is None:
+            best = g
+        else:
+            _cmp_ok(g, best)
+            if g >= best:
+                best = g
+    return _fmax(EXPT_GAIN_FACTOR * (0.0 if best is None else best), 0.1)
+
+
+def count_improved_reads(new, old, mg):
+    """:308-312"""
+    return sum(1 for a, b in zip(new, old) if b + mg < a)
+
+
+def cluster_filtered_variants(variants, variant_type, copy_num, coverage, local_coverage, gains, rng, B, log=None):
+    """:213-274; returns (assignments, likelihood gains n x max_k, score, max_k)"""
+    log = log or Log()
+    n = len(variants)
+    if copy_num <= 1 or all(len(xs) == 0 for xs in variants) or n <= copy_num:
+        log.early_return = True
+        return [0] * n, [[0.0] for _ in range(n)], 0.0, 1
+    log.early_return = False
+    asn, best, best_k, read_gains = [0] * n, 0.0, 1, [0.0] * n
+    prev_used = [False] * len(variants[0])
+    end = min(copy_num, 1 + 2 * len(variant_type))
+    start = max(end, 5) - 3
+    log.range = (start, end)
+    for k in range(start, end + 1):
+        got = mcmc_clustering(variants, k, coverage, rng, B, log)
+        source = "chain"
+        chain_score = got[1]
+        other_score = None
+        if k == 2:
+            alt = use_highest_gain(variants)
+            _cmp_ok(got[1], alt[1])
+            log.decide(got[1], alt[1])
+            other_score = alt[1]
+            if got[1] < alt[1]:
+                got, source = alt, "highest_gain"
+        new_asn, score, new_gains, used = got
+        mg = min_gain(gains, variant_type, used)
+        improved = count_improved_reads(new_gains, read_gains, mg)
+        per_read = expected_gains(gains, variant_type, prev_used, used)
+        expected = per_read * local_coverage + 0.1
+        accepted = expected < score - best
+        if expected == expected:
+            log.decide(expected, score - best)
+        sizes = [0] * k
+        for a in new_asn:
+            sizes[a] += 1
+        log.tried.append(dict(k=k, score=score, expected_gain=expected, improved=improved, used_columns=list(used), sizes=sizes,
+                              accepted=accepted, source=source, chain_score=chain_score, highest_gain_score=other_score,
+                              min_gain=mg, no_new_variants=list(prev_used) == list(used),
+                              newly_used=[(not p) and c for p, c in zip(prev_used, used)], restarts=log.last_restarts))
+        if not accepted:
+            break
+        asn, best, best_k, read_gains, prev_used = new_asn, score, k, new_gains, used
+    return asn, get_likelihood_gain(variants, asn, best_k), best, best_k
+
+
+def reassign_and_posterior(asn, lk_gains, B, log=None):
+    """the tail of clustering :98-105 with to_posterior_probability :342-347; new lists"""
+    log = log or Log()
+    asn, post = list(asn), []
+    for i, lks in enumerate(lk_gains):
+        _cmp_ok(*lks)
+        top = 0
+        for c in range(1, len(lks)):
+            if lks[c] >= lks[top]:   # max_by: the last maximum
+                top = c
+        log.decide(lks[asn[i]] + 0.001, lks[top])
+        if lks[asn[i]] + 0.001 < lks[top]:
+            asn[i] = top
+            log.tail["changed"] += 1
+        elif lks[asn[i]] < lks[top]:
+            log.tail["within_margin"] += 1
+        total = logsumexp(lks, B)
+        post.append([x - total for x in lks])
+    return asn, post
+
+
+def cluster_features(variants, variant_type, copy_num, coverage, local_coverage, gains, chunk_id, B):
+    """pseudo_mcmc::clustering (:77-107) from the feature matrix on, with the chunk's own generator (mod.rs:97).  Returns a dict:
+    status 0 with label / cluster_num / score / post / log, or status -6 with `panic` = the reason."""
+    log = Log()
+    rng = chunk_rng(chunk_id)
+    variants = [[float(x) for x in row] for row in variants]
+    variant_type = [(int(h), int(t)) for h, t in variant_type]
+    try:
+        if copy_num < 2:
+            log.early_return = True
+            asn, post, score, k = [0] * len(variants), [[0.0] for _ in variants], 0.0, 1
+        else:
+            asn, lk_gains, score, k = cluster_filtered_variants(variants, variant_type, copy_num, coverage, local_coverage, gains,
+                                                                rng, B, log)
+            asn, post = reassign_and_posterior(asn, lk_gains, B, log)
+    except ReferencePanic as exc:
+        return dict(status=-6, panic=str(exc), log=log)
+    log.draws = rng.core.draws
+    return dict(status=0, panic=None, label=asn, cluster_num=k, score=score, post=post, log=log, state=rng.core.state())
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# which columns become candidates: filter_profiles :426-466 up to the TOTAL / CAND rows
+# ---------------------------------------------------------------------------------------------------------------------------
+def homopolymer_lengths(tmpl):
+    """homopolymer_length (pseudo_mcmc.rs:195-211): the length of the run every template base is in"""
+    tl = len(tmpl)
+    homop = np.ones(tl, dtype=np.int64)
+    i = 0
+    while i < tl:
+        j = i
+        while j + 1 < tl and tmpl[j + 1] == tmpl[i]:
+            j += 1
+        homop[i:j + 1] = j - i + 1
+        i = j + 1
+    return homop
+
+
+def expected_gain(p, homop_len, row):
+    """Gains::expected, likelihood_gains.rs:79-87; difftype :168-178"""
+    g = p.gains
+    h = min(max(int(homop_len), 1), int(g.max_homopolymer_len))
+    tab = g.subst if row < 4 else (g.insertions if row < 8 + 3 else g.deletions)
+    return tab[h - 1].gain
+
+
+def cand_lk_count(prof, bp, row, homop, p, ks):
+    """a CAND row's lk and count (pseudo_mcmc.rs:457-461 + column_sum :577-588) from the per-read profiles prof = table - lk
+    [n, 14 (tl + 1)]: compress_small_gains, the sum and count of the gains above POS_THR, + max_k Poisson(count | k * coverage)"""
+    tl = len(homop)
+    mr = expected_gain(p, homop[bp] if bp < tl else 1, row) * 0.5
+    col = prof[:, bp * 14 + row].copy()
+    col[np.abs(col) < mr] = 0.0
+    gain, count = 0.0, 0
+    for x in col:                                       # left to right, as the reference sums
+        if 0.00001 < x:
+            gain += float(x)
+            count += 1
+    cov = float(p.haploid_coverage)
+    pois = max(count * math.log(cov * k) - cov * k - sum(math.log(q) for q in range(1, count + 1)) for k in ks)
+    return pois + gain, count
+
+
+def diff_type_of(row):
+    """pos_to_bp_and_difftype :168-178"""
+    return SUBST if row < 4 else (INS if row < 8 + COPY_SIZE else DEL)
+
+
+def compress_small_gains(prof, tmpl, gains):
+    """:141-165 on prof [n, 14 (tl + 1)]; a new array"""
+    homop = homopolymer_lengths(tmpl)
+    tl = len(tmpl)
+    out = np.array(prof, dtype=np.float64)
+    for pos in range(out.shape[1]):
+        bp, row = divmod(pos, NUM_ROW)
+        mr = gains.expected(int(homop[bp]) if bp < tl else 1, diff_type_of(row)) * 0.5
+        col = out[:, pos]
+        col[np.abs(col) < mr] = 0.0
+    return out
+
+
+def pvalues(prob, n, B=LibmMath):
+    """likelihood_gains.rs:115-137: i -> P(i <= X | n, prob)"""
+    ln, in_ln = B.log(prob), B.log(1.0 - prob)
+    logp = [in_ln * float(n)]
+    for k in range(n):
+        logp.append(logp[-1] + (ln + B.log(float(n - k)) - in_ln - B.log(float(k + 1))))
+    for k in range(n - 1, -1, -1):
+        x, y = logp[k + 1], logp[k]
+        logp[k] = x + B.log(1.0 + B.exp(y - x)) if y < x else y + B.log(1.0 + B.exp(x - y))
+    return [B.exp(x) for x in logp]
+
+
+PVALUE = 0.05
+
+
+def filter_candidates(prof, tmpl, strands, gains, copy_num, coverage, B=LibmMath):
+    """filter_profiles :426-466 on the COMPRESSED profiles: returns (candidates [(pos, total_lk, count)] in column order,
+    dropped {pos: name of the first filter that dropped it} for every column with at least one gain above POS_THR)"""
+    n, width = prof.shape
+    tl = len(tmpl)
+    homop = [int(h) for h in homopolymer_lengths(tmpl)]
+    temp_len = width // NUM_ROW
+    pv = {(dt, h): pvalues(gains.tab[dt][h - 1][1], n, B) for dt in (SUBST, DEL, INS) for h in range(1, gains.max_homopolymer_len + 1)}
+    lnfact = ln_factorials(n, B)
+    cands, dropped = [], {}
+    for pos in range(width):
+        col = prof[:, pos]
+        gain, count = 0.0, 0
+        for x in col:   # column_sum :577-588
+            if POS_THR < x:
+                gain += float(x)
+                count += 1
+        bp, row = divmod(pos, NUM_ROW)
+        dt = diff_type_of(row)
+        why = None
+        if not (MASK_LENGTH <= bp <= temp_len - MASK_LENGTH):
+            why = "edge"
+        elif not (row < 8 or row == 8 + COPY_SIZE):
+            why = "row"
+        else:
+            ok = True   # is_in_short_homopolymer :497-514
+            if dt == INS:
+                base = b"ACGT"[row - 4] if row - 4 < 4 else 0
+                _require(0 < bp, "is_in_short_homopolymer: template[x - 1] with x == 0")
+                prev_len = homop[bp - 1] + (1 if tmpl[bp - 1] == base else 0)
+                _require(bp < tl, "is_in_short_homopolymer: template[x] out of bounds")
+                next_len = homop[bp] + (1 if tmpl[bp] == base else 0)
+                ok = prev_len <= MAX_HOMOP_LENGTH and next_len <= MAX_HOMOP_LENGTH
+            elif dt == DEL and bp < tl:
+                ok = homop[bp] <= MAX_HOMOP_LENGTH
+            if not ok:
+                why = "homopolymer"
+        if why is None:   # has_small_pvalue :476-495
+            h = homop[bp] if bp < tl else 0
+            _require(0 < h, "Pvalues::pvalue: assert 0 < homop_len")
+            _require(count <= n, "Pvalues::pvalue: assert count <= total")
+            p = float(temp_len) * pv[(dt, min(h, gains.max_homopolymer_len))][count]
+            expt = gains.expected(h, dt) * EXPT_GAIN_FACTOR
+            _require(1 <= bp and bp + 1 < tl, "has_small_pvalue: homopolymer_length[pos - 1..=pos + 1] out of bounds")
+            small = p < PVALUE / float(temp_len)
+            enough = float(count) * expt < gain
+            if not small:
+                why = "pvalue"
+            elif not enough:
+                why = "gain_per_count"
+        if why is None:   # is_explainable_by_strandedness :314-339
+            strand_count, sign_count, obs = [0, 0], [0, 0], [[0, 0], [0, 0]]
+            for x, s in zip(col, strands):
+                if abs(x) > 0.0001:
+                    s, sg = (1 if s else 0), (0 if math.copysign(1.0, x) < 0 else 1)
+                    strand_count[s] += 1
+                    sign_count[sg] += 1
+                    obs[s][sg] += 1
+            total = strand_count[0] + strand_count[1]
+            if total == 0:
+                why = "strand"
+            else:
+                chisq = 0.0
+                for s in range(2):
+                    inner = 0.0
+                    for sg in range(2):
+                        e = float(strand_count[s] * sign_count[sg]) / float(total)
+                        d = float(obs[s][sg]) - e
+                        inner += (d * d / e) if e != 0.0 else (NAN if d == 0.0 else INF)
+                    chisq += inner
+                if not chisq < 10.0:
+                    why = "strand"
+        if why is None:
+            best = None
+            for k in range(1, copy_num + 1):
+                v = poisson_lk(count, coverage * float(k), B, lnfact)
+                _cmp_ok(v)
+                if best is None or v >= best:
+                    best = v
+            _require(best is not None, "filter_profiles: no cluster count")
+            total_lk = best + gain
+            if 0.0 < total_lk:
+                cands.append((pos, total_lk, count))
+            else:
+                why = "total_lk"
+        if why is not None and count > 0:
+            dropped[pos] = why
+    return cands, dropped
+
+
+def _sokal_michener(prof, i, j):
+    """:618-633"""
+    x, y = prof[:, i], prof[:, j]
+    both = (np.abs(x) > POS_THR) & (np.abs(y) > POS_THR)
+    mat, tot = int(((x * y > 0) & both).sum()), int(both.sum())
+    return 0.0 if tot == 0 else max(mat, tot - mat) / tot
+
+
+def _cosine_similarity(prof, i, j):
+    """:602-615"""
+    ip = isq = jsq = 0.0
+    for x, y in zip(prof[:, i], prof[:, j]):
+        if POS_THR < abs(x) and POS_THR < abs(y):
+            ip, isq, jsq = ip + float(x * y), isq + float(x * x), jsq + float(y * y)
+    return 0.0 if isq == 0.0 else ip / math.sqrt(isq) / math.sqrt(jsq)
+
+
+ROUND = 3
+
+
+def pick_filtered_profiles(cands, prof, copy_num):
+    """:516-575 with find_next_variants :590-600 (max_by: the last maximum); returns the selected (pos, lk) in column order"""
+    sel = [0] * len(cands)
+    for _ in range(ROUND):
+        sel = [0 if f == 3 else f for f in sel]
+        for _ in range(max(copy_num, 2)):
+            nx = None
+            for i, f in enumerate(sel):
+                if f == 0 and (nx is None or cands[i][1] >= cands[nx][1]):
+                    nx = i
+            if nx is None:
+                break
+            sel[nx] = 1
+            picked = cands[nx][0]
+            for i, f in enumerate(sel):
+                if f not in (0, 3):
+                    continue
+                if abs(cands[i][0] // NUM_ROW - picked // NUM_ROW) < MASK_LENGTH:
+                    sel[i] = 2
+                elif 0.8 < _sokal_michener(prof, picked, cands[i][0]) or 0.8 < abs(_cosine_similarity(prof, picked, cands[i][0])):
+                    sel[i] = 3
+    return [(c[0], c[1]) for c, f in zip(cands, sel) if f == 1]
+
+
+def cluster_profiles(prof, tmpl, strands, gains, copy_num, coverage, local_coverage, chunk_id, B):
+    """pseudo_mcmc::clustering (:77-107) from the per-read profiles (table - lk) on: compress, filter, pick, cluster.  Returns
+    cluster_features' dict with `cands` and `dropped` of filter_candidates and `probes` added."""
+    if copy_num < 2:
+        return dict(cluster_features([[] for _ in prof], [], copy_num, coverage, local_coverage, gains, chunk_id, B), cands=[], dropped={},
+                    probes=[])
+    comp = compress_small_gains(prof, tmpl, gains)
+    cands, dropped = filter_candidates(comp, tmpl, strands, gains, copy_num, coverage, B)
+    probes = pick_filtered_profiles(cands, comp, copy_num)
+    homop = homopolymer_lengths(tmpl)
+    vt = [(int(homop[pos // NUM_ROW]) if pos // NUM_ROW < len(tmpl) else 0, diff_type_of(pos % NUM_ROW)) for pos, _ in probes]
+    variants = [[float(row[pos]) for pos, _ in probes] for row in comp]
+    out = cluster_features(variants, vt, copy_num, coverage, local_coverage, gains, chunk_id, B)
+    return dict(out, cands=cands, dropped=dropped, probes=probes)

@@ -111,7 +111,18 @@ class Rand085:
     def gen_bool(self, p):
         if p == 1.0:
             return True
+        _require(0.0 <= p < 1.0, "gen_bool: Bernoulli::new(p).unwrap() with p outside [0, 1]")  # a NaN included
         return self.core.next_u64() < int(p * 18446744073709551616.0)
+
+    def choose_iter(self, items):
+        """IteratorRandom::choose on an iterator whose size_hint is (0, Some(_)), such as a Filter: the reservoir path, one
+        gen_index(consumed) per element, an element replacing the result when the index is 0.  None for no element."""
+        result, consumed = None, 0
+        for elem in items:
+            consumed += 1
+            if self.gen_index(consumed) == 0:
+                result = elem
+        return result
 
     def _range(self, n, bits, draw):
         zone = ((n << (bits - n.bit_length())) - 1) & ((1 << bits) - 1)

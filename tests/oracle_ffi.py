@@ -186,6 +186,12 @@ def lib():
         u32, p, C.c_int)
     sig("jo_modification_table", C.c_int, C.POINTER(Params), PU8, u64, u32, PU8, C.POINTER(u64), PU8,
         C.POINTER(u64), PU8, PD, PD)
+    sig("jo_mcmc_clustering", C.c_int, PD, sz, sz, sz, d, C.POINTER(Rng), PSZ, PD, PD, PU8)
+    sig("jo_cluster_filtered_variants", C.c_int, PD, sz, sz, PSZ, C.POINTER(C.c_int), C.POINTER(ClusterConfig), C.POINTER(Rng),
+        PSZ, PD, PD, PSZ)
+    sig("jo_reassign_and_posterior", None, sz, sz, PSZ, PD)
+    sig("jo_filter_profiles", sz, PU8, sz, PD, sz, PU8, C.POINTER(ClusterConfig), PSZ, PD)
+    sig("jo_trace_set", None, C.POINTER(Trace))
     sig("jo_exp", d, d)
     sig("jo_log", d, d)
     _lib = L
@@ -260,8 +266,6 @@ def trace_chunk(params, batch, chunk, skip_polish=False):
     """the reference's trace! rows of one chunk's clustering as the oracle logs them (oracle/pseudo_mcmc.c: TOTAL / CAND / PICK /
     DUMP / RANGE / LK / COUNTS): the chunk alone through jo_cluster_chunks on one thread while the sink is set; a list of rows"""
     L = lib()
-    L.jo_trace_set.restype = None
-    L.jo_trace_set.argtypes = [C.POINTER(Trace)]
     sub = batch.subset([int(chunk)])
     buf = C.create_string_buffer(1 << 20)
     t = Trace(C.cast(buf, C.c_void_p), len(buf), 0)

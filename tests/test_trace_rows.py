@@ -12,6 +12,7 @@ import pytest
 
 import helpers
 import oracle_ffi as O
+from clustering_reference import cand_lk_count, expected_gain, homopolymer_lengths
 from jtk_amd import api, batch as jb, ffi, synth
 
 
@@ -97,46 +98,6 @@ def test_oracle_rows_follow_the_rust_format_strings(oracle):
     lab = out["label"]
     # the COUNTS row is the k = 2 clustering BEFORE the re-assignment of clustering()'s tail (:98-105); the sizes still add up
     assert sum(int(x) for x in counts[0].split("\t")[1].strip("[]").split(", ")) == len(lab)
-
-
-def homopolymer_lengths(tmpl):
-    """homopolymer_length (pseudo_mcmc.rs:195-211): the length of the run every template base is in"""
-    tl = len(tmpl)
-    homop = np.ones(tl, dtype=np.int64)
-    i = 0
-    while i < tl:
-        j = i
-        while j + 1 < tl and tmpl[j + 1] == tmpl[i]:
-            j += 1
-        homop[i:j + 1] = j - i + 1
-        i = j + 1
-    return homop
-
-
-def expected_gain(p, homop_len, row):
-    """Gains::expected, likelihood_gains.rs:79-87; difftype :168-178"""
-    g = p.gains
-    h = min(max(int(homop_len), 1), int(g.max_homopolymer_len))
-    tab = g.subst if row < 4 else (g.insertions if row < 8 + 3 else g.deletions)
-    return tab[h - 1].gain
-
-
-def cand_lk_count(prof, bp, row, homop, p, ks):
-    """a CAND row's lk and count (pseudo_mcmc.rs:457-461 + column_sum :577-588) from the per-read profiles prof = table - lk
-    [n, 14 (tl + 1)]: compress_small_gains, the sum and count of the gains above POS_THR, + max_k Poisson(count | k * coverage)"""
-    import math
-    tl = len(homop)
-    mr = expected_gain(p, homop[bp] if bp < tl else 1, row) * 0.5
-    col = prof[:, bp * 14 + row].copy()
-    col[np.abs(col) < mr] = 0.0
-    gain, count = 0.0, 0
-    for x in col:                                       # left to right, as the reference sums
-        if 0.00001 < x:
-            gain += float(x)
-            count += 1
-    cov = float(p.haploid_coverage)
-    pois = max(count * math.log(cov * k) - cov * k - sum(math.log(q) for q in range(1, count + 1)) for k in ks)
-    return pois + gain, count
 
 
 @pytest.mark.parametrize("config", ["ont_diploid", "ont_4copy"])
