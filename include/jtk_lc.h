@@ -53,6 +53,7 @@ typedef enum jtk_status {
     JTK_ERR_NO_DEVICE = -2,       /* no usable MI355X / HIP runtime failure (message via last_error)   */
     JTK_ERR_UNSUPPORTED = -3,     /* band radius > 255 (any read count is taken); jtk_lc_align_reads:  */
                                   /* a read farther from its template than max_dist, or > 32,000 bases */
+                                  /* (jtk_lc_align_reads_mode: or a band > JTK_ALIGN_MODE_MAX_BAND)    */
     JTK_ERR_ALLOC = -4,           /* hipMalloc / host allocation failed                                */
     JTK_ERR_OPS_MISMATCH = -5,    /* ops do not consume exactly the template and the read              */
     JTK_ERR_CHUNK_FAILED = -6,    /* >=1 chunk hit a condition on which the reference panics; see      */
@@ -197,6 +198,37 @@ JTK_LC_API int jtk_lc_align_reads(size_t n_chunks, const jtk_lc_chunk_t *chunks,
                        const uint8_t *read_bases, const uint64_t *read_off, uint32_t max_dist,
                        uint8_t *ops_out, uint64_t *ops_out_off, uint64_t ops_cap,
                        uint32_t *dist_out, int32_t *read_status, int device);
+
+/* ---- the same with one sequence's ends free: edlib Infix / Prefix with AlignTask::Alignment -------------------
+ * What the reference calls wherever it places one sequence inside a slightly longer window of another: `semiglobal`
+ * (haplotyper/src/encode/mod.rs:227-246, the tips of every encoded node), the chunk laid into a read window
+ * (encode/deletion_fill.rs:544-554), dense_encoding.rs:728-757, determine_chunks.rs:520-538, and `align_infix` /
+ * `align_leading` / `align_trailing` (consensus/mod.rs:563-614), with which `fix_alignment` re-anchors every read after a
+ * round of window polishing (`polish`, :300-371).  One sequence of a pair is whole (edlib's query) and is consumed
+ * entirely; the other is free (edlib's target), `free_seq` says which, and only its stretch [start, end) is consumed:
+ *   JTK_ALIGN_INFIX  : both ends of the free sequence are free; the distance is the smallest over all its substrings.
+ *   JTK_ALIGN_PREFIX : its start is pinned to 0, its end is free; the smallest over all its prefixes.
+ *   JTK_ALIGN_GLOBAL : jtk_lc_align_reads (same ops and distances); free_seq is ignored, start = 0, end = tmpl_len.
+ * Among equally good placements the smallest end is returned, and for it the path of DESIGN.md section 4 (walk from the end
+ * cell; diagonal, then Del, then Ins -- in either orientation; infix: the walk stops at the first cell on the free
+ * boundary, which gives start).  Parity with edlib's own choice among equally good placements and paths is not pinned.
+ * The op meanings do not change with free_seq: Del consumes a template base, Ins a read base.  An empty whole sequence
+ * gives distance 0, no ops and start = end = 0; an empty free sequence gives whole-length x Ins (the read is whole) or
+ * x Del (the template is whole) and start = end = 0.
+ * Batch layout, validation, ops_out / ops_cap, dist_out, read_status, the per-read failure rule and max_dist are those of
+ * jtk_lc_align_reads; start_out[r] / end_out[r] are 0 for a failed read.  Limits (JTK_ERR_UNSUPPORTED for the read, the rest
+ * of the batch is aligned): 32,000 bases per sequence, and JTK_ALIGN_MODE_MAX_BAND diagonals in the band that certifies
+ * the largest distance the call allows -- min(max_dist, whole length), see DESIGN.md section 4 for the band -- which is
+ * decided per read before anything is launched (the kernel keeps 3 bytes of LDS per diagonal).  With max_dist = 0 that is
+ * every pair with tmpl_len + read_len < 32,768; longer pairs need a max_dist.
+ * mode / free_seq outside the enums: JTK_ERR_INVALID_ARG. */
+enum jtk_align_mode { JTK_ALIGN_GLOBAL = 0, JTK_ALIGN_INFIX = 1, JTK_ALIGN_PREFIX = 2 };
+enum jtk_align_free { JTK_ALIGN_FREE_TEMPLATE = 0, JTK_ALIGN_FREE_READ = 1 };
+#define JTK_ALIGN_MODE_MAX_BAND 32768
+JTK_LC_API int jtk_lc_align_reads_mode(size_t n_chunks, const jtk_lc_chunk_t *chunks, const uint8_t *tmpl_bases,
+                            const uint8_t *read_bases, const uint64_t *read_off, int mode, int free_seq, uint32_t max_dist,
+                            uint8_t *ops_out, uint64_t *ops_out_off, uint64_t ops_cap,
+                            uint32_t *dist_out, uint32_t *start_out, uint32_t *end_out, int32_t *read_status, int device);
 
 /* ---- resident-batch form of the same call ----------------------------------------------------------
  * jtk_lc_cluster_chunks == session_create + session_run(0) + session_fetch + session_destroy.

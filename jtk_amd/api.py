@@ -74,10 +74,16 @@ def polish_chunks(params, batch, radius=0, take_num=0, ignore_edge=0, device=0, 
     return o
 
 
-def align_reads(batch, max_dist=0, device=0, raise_on_read_failure=True):
+ALIGN_MODES = {"global": 0, "infix": 1, "prefix": 2}     # enum jtk_align_mode
+ALIGN_FREE = {"template": 0, "read": 1}                  # enum jtk_align_free
+
+
+def align_reads(batch, max_dist=0, device=0, raise_on_read_failure=True, mode="global", free="template"):
     """jtk_lc_align_reads: global unit-cost alignment of every read of `batch` to its chunk's template (the batch's own ops
     are not looked at).  -> dict(ops, ops_off, dist, status, rc); `batch.with_ops(out["ops"], out["ops_off"])` carries them
-    into polish_chunks / cluster_chunks."""
+    into polish_chunks / cluster_chunks.
+    mode="infix" / "prefix": jtk_lc_align_reads_mode with the `free` sequence ("template" or "read") consumed only on
+    [start, end); the dict gains `start` and `end` (see `semiglobal` for ops that consume both sequences whole)."""
     L = ffi.lib()
     n = batch.n_reads
     cap = int(len(batch.read_bases)) + int((batch.chunks["tmpl_len"] * batch.chunks["n_reads"]).sum()) + 64
@@ -85,12 +91,41 @@ def align_reads(batch, max_dist=0, device=0, raise_on_read_failure=True):
     ops_off = np.zeros(n + 1, dtype=np.uint64)
     dist = np.zeros(n, dtype=np.uint32)
     status = np.zeros(n, dtype=np.int32)
-    rc = L.jtk_lc_align_reads(batch.n_chunks, batch.chunks.ctypes.data, u8p(batch.tmpl_bases), u8p(batch.read_bases),
-                              u64p(batch.read_off), int(max_dist), u8p(ops), u64p(ops_off), cap, u32p(dist),
-                              status.ctypes.data_as(C.POINTER(C.c_int32)), device)
+    if mode not in ALIGN_MODES or free not in ALIGN_FREE:
+        raise ValueError("mode is one of %s, free one of %s" % (sorted(ALIGN_MODES), sorted(ALIGN_FREE)))
+    extra = {}
+    if mode == "global":
+        rc = L.jtk_lc_align_reads(batch.n_chunks, batch.chunks.ctypes.data, u8p(batch.tmpl_bases), u8p(batch.read_bases),
+                                  u64p(batch.read_off), int(max_dist), u8p(ops), u64p(ops_off), cap, u32p(dist),
+                                  status.ctypes.data_as(C.POINTER(C.c_int32)), device)
+    else:
+        extra = dict(start=np.zeros(n, dtype=np.uint32), end=np.zeros(n, dtype=np.uint32))
+        rc = L.jtk_lc_align_reads_mode(batch.n_chunks, batch.chunks.ctypes.data, u8p(batch.tmpl_bases), u8p(batch.read_bases),
+                                       u64p(batch.read_off), ALIGN_MODES[mode], ALIGN_FREE[free], int(max_dist), u8p(ops),
+                                       u64p(ops_off), cap, u32p(dist), u32p(extra["start"]), u32p(extra["end"]),
+                                       status.ctypes.data_as(C.POINTER(C.c_int32)), device)
     if rc != 0 and (raise_on_read_failure or rc != -6):
         check(rc)
-    return dict(ops=ops[:int(ops_off[n])] if rc in (0, -6) else ops[:0], ops_off=ops_off, dist=dist, status=status, rc=rc)
+    return dict(ops=ops[:int(ops_off[n])] if rc in (0, -6) else ops[:0], ops_off=ops_off, dist=dist, status=status, rc=rc, **extra)
+
+
+def semiglobal(batch, max_dist=0, device=0):
+    """`semiglobal` (encode/mod.rs:227-246) for every read of `batch`: the template is placed inside the read (infix, the read
+    free) and the read's bases in front of `start` and behind `end` become Ins, so the ops consume both sequences whole.
+    -> dict(ops, ops_off, dist, start, end, status, rc), ready for `batch.with_ops(out["ops"], out["ops_off"])`."""
+    o = align_reads(batch, max_dist=max_dist, device=device, mode="infix", free="read")
+    rl = np.diff(batch.read_off.astype(np.int64))
+    n_in = np.diff(o["ops_off"].astype(np.int64))
+    lead = o["start"].astype(np.int64)
+    trail = rl - o["end"].astype(np.int64)
+    # the reference's guards come out of the same sums: an empty template gives the read as Ins (no ops, start = end = 0)
+    off = np.zeros(batch.n_reads + 1, dtype=np.uint64)
+    off[1:] = np.cumsum(lead + n_in + trail)
+    ops = np.full(int(off[-1]), 2, dtype=np.uint8)                       # JTK_OP_INS; the aligned stretches are copied in
+    for r in range(batch.n_reads):
+        a = int(off[r]) + int(lead[r])
+        ops[a:a + int(n_in[r])] = o["ops"][int(o["ops_off"][r]):int(o["ops_off"][r + 1])]
+    return dict(ops=ops, ops_off=off, dist=o["dist"], start=o["start"], end=o["end"], status=o["status"], rc=o["rc"])
 
 
 def modification_table(params, tmpl, reads, ops, strands, device=0):

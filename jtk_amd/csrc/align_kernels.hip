@@ -1,5 +1,7 @@
 // align_kernels.hip -- jtk_lc_align_reads: batched global unit-cost alignment of reads to their templates (the reference's
-// edlib Global / Alignment calls: consensus/mod.rs:424-435, polish_chunks.rs:114-120).  Specification: DESIGN.md section 4.
+// edlib Global / Alignment calls: consensus/mod.rs:424-435, polish_chunks.rs:114-120), and jtk_lc_align_reads_mode: the same
+// with one sequence's ends free (edlib Infix / Prefix: encode/mod.rs:227-246, encode/deletion_fill.rs:544-554,
+// dense_encoding.rs:728-757, determine_chunks.rs:520-538, consensus/mod.rs:563-614).  Specification: DESIGN.md section 4.
 //
 // One (template, read) pair per workgroup, restricted to the diagonals k = j - i of a band that is certain to hold every
 // optimal path when the distance is <= t; the host doubles t for the pairs that come back above it.
@@ -10,6 +12,10 @@
 //         write) and produces their 2-bit move codes (16 bits); 8 anti-diagonals of them leave as one 16-byte store.
 //   walk: wave 0 pulls an 8-block (64 anti-diagonal) x 11-group tile of move codes into LDS with two coalesced 16-byte loads
 //         per lane, follows the path through the tile, and stores that stretch of ops, reversed, with one store per lane.
+// Mode and free side are compile-time parameters of the one body: infix forces the free boundary to 0 in the fill; infix and
+// prefix take the end cell as the minimum over the last row / column (the last value of the diagonals that close there, read
+// from the LDS arrays; smallest index wins) and infix stops the walk at the free boundary.  The global instantiation
+// compiles none of this (align_kernel<THREADS> is instruction for instruction what it was before the modes existed).
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -25,6 +31,7 @@ extern "C" void jtk_internal_set_error(const char *msg);
 #define ALIGN_WALK_LOST 0xFFFFFFFEu  // dist marker: the walk left the band (an internal error, reported as such)
 #define ALIGN_TILE_GROUPS 11
 #define ALIGN_TILE_BLOCKS 8
+#define ALIGN_MODE_MAX_BAND JTK_ALIGN_MODE_MAX_BAND  // widest band an infix / prefix pair may need: 96 KB of LDS (jtk_lc.h)
 
 namespace {
 
@@ -39,6 +46,8 @@ struct AlignPair {
 };
 
 enum { MV_MATCH = 0, MV_MISMATCH = 1, MV_DEL = 2, MV_INS = 3 };
+enum { AM_GLOBAL = JTK_ALIGN_GLOBAL, AM_INFIX = JTK_ALIGN_INFIX, AM_PREFIX = JTK_ALIGN_PREFIX };
+enum { AF_TEMPLATE = JTK_ALIGN_FREE_TEMPLATE, AF_READ = JTK_ALIGN_FREE_READ };
 
 __device__ __forceinline__ uint64_t load_u64_unaligned(const uint8_t *p) {
     uint64_t v;
@@ -53,9 +62,18 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <int THREADS>
+// the walk goes on: infix stops at the first cell on the free boundary (j == 0 or i == 0; d + k = 2j, d - k = 2i), the
+// other modes at (0, 0)
+template <int MODE, int FREE>
+__device__ __forceinline__ bool walk_on(int d, int k) {
+    if constexpr (MODE == AM_INFIX) return (FREE == AF_TEMPLATE ? d + k : d - k) != 0;
+    return d > 0;
+}
+
+// bounds[2 * out], [2 * out + 1] = start, end (MODE != AM_GLOBAL only; the global instantiation never looks at the pointer)
+template <int THREADS, int MODE, int FREE>
 __global__ __launch_bounds__(THREADS) void align_kernel(const AlignPair *pairs, const uint8_t *bases, uint4 *scratch,
-                                                        uint8_t *ops_all, uint32_t *dist, uint32_t *n_ops) {
+                                                        uint8_t *ops_all, uint32_t *dist, uint32_t *n_ops, uint32_t *bounds) {
     extern __shared__ uint4 lds4[];
     __shared__ uint4 tile[ALIGN_TILE_BLOCKS * ALIGN_TILE_GROUPS];
     __shared__ uint8_t opbuf[64];
@@ -117,6 +135,9 @@ __global__ __launch_bounds__(THREADS) void align_kernel(const AlignPair *pairs, 
                     m = m < c ? m : c;
                     m = m < ALIGN_INF ? m : ALIGN_INF;
                     const uint32_t code = a == m ? mm : (b == m ? (uint32_t)MV_DEL : (uint32_t)MV_INS);
+                    if constexpr (MODE == AM_INFIX) {  // the free boundary; the walk stops there, so its code is never read
+                        if ((FREE == AF_TEMPLATE ? j0 + e : i0 - e) == 0) m = 0;
+                    }
                     if (e >= e_lo && e <= e_hi) {
                         codes |= code << (2 * e);
                         nw[e >> 1] = (nw[e >> 1] & ~(0xFFFFu << (16 * (e & 1)))) | (m << (16 * (e & 1)));
@@ -135,8 +156,31 @@ __global__ __launch_bounds__(THREADS) void align_kernel(const AlignPair *pairs, 
         __syncthreads();
     }
 
-    const int s_end = rl - tl - klo;
-    const uint32_t D = val[(s_end & 1) * stride + 8 + (s_end >> 1)];
+    int s_end = rl - tl - klo, d_end = dmax;
+    uint32_t D, end = 0;
+    if constexpr (MODE == AM_GLOBAL) {
+        D = val[(s_end & 1) * stride + 8 + (s_end >> 1)];
+    } else {
+        // the diagonals that close in the last row (template free: cell (i, rl) closes k = rl - i) or the last column (read
+        // free: (tl, j) closes k = j - tl) still hold that cell; value << 16 | index orders by value, then by smallest index
+        __shared__ uint32_t best;
+        if (tid == 0) best = 0xFFFFFFFFu;
+        __syncthreads();
+        const int k_a = FREE == AF_TEMPLATE ? (klo > rl - tl ? klo : rl - tl) : klo;
+        const int k_b = FREE == AF_TEMPLATE ? khi : (khi < rl - tl ? khi : rl - tl);
+        uint32_t mine = 0xFFFFFFFFu;
+        for (int k = k_a + tid; k <= k_b; k += THREADS) {
+            const int s = k - klo;
+            const uint32_t key = ((uint32_t)val[(s & 1) * stride + 8 + (s >> 1)] << 16) | (uint32_t)(FREE == AF_TEMPLATE ? rl - k : k + tl);
+            mine = key < mine ? key : mine;
+        }
+        if (mine != 0xFFFFFFFFu) atomicMin(&best, mine);
+        __syncthreads();
+        D = best >> 16;
+        end = best & 0xFFFFu;
+        s_end = (FREE == AF_TEMPLATE ? rl - (int)end : (int)end - tl) - klo;
+        d_end = (FREE == AF_TEMPLATE ? rl : tl) + (int)end;
+    }
     if (D > pr.t) {  // the band certifies nothing: the host widens it
         if (tid == 0) {
             dist[pr.out] = 0xFFFFFFFFu;
@@ -150,9 +194,9 @@ __global__ __launch_bounds__(THREADS) void align_kernel(const AlignPair *pairs, 
     // ---- walk from (tl, rl) to (0, 0); every lane of wave 0 follows the same path, lane L stores op L of each stretch
     uint8_t *slot_end = ops_all + pr.ops_off + (uint64_t)(tl + rl);
     const uint16_t *tile16 = (const uint16_t *)tile;
-    int d = dmax, s = s_end;
+    int d = d_end, s = s_end;
     uint32_t n = 0;
-    while (d > 0) {
+    while (walk_on<MODE, FREE>(d, klo + s)) {
         const int db_hi = d >> 3, db_lo = db_hi - (ALIGN_TILE_BLOCKS - 1);
         int g_lo = ((s >> 1) >> 3) - ALIGN_TILE_GROUPS / 2;
         if (g_lo < 0) g_lo = 0;
@@ -162,7 +206,7 @@ __global__ __launch_bounds__(THREADS) void align_kernel(const AlignPair *pairs, 
         }
         wave_sync();
         uint32_t nl = 0;
-        while (d > 0 && nl < 64) {
+        while (walk_on<MODE, FREE>(d, klo + s) && nl < 64) {
             const int db = (d >> 3) - db_lo, c = s >> 1, g = (c >> 3) - g_lo;
             if (db < 0 || g < 0 || g >= ALIGN_TILE_GROUPS) break;
             const uint32_t w = tile16[(db * ALIGN_TILE_GROUPS + g) * 8 + (d & 7)];
@@ -183,8 +227,12 @@ __global__ __launch_bounds__(THREADS) void align_kernel(const AlignPair *pairs, 
         if (nl == 0) break;  // cannot happen with the codes the fill wrote; never spin on anything else
     }
     if (tid == 0) {
-        dist[pr.out] = d == 0 ? D : ALIGN_WALK_LOST;
+        dist[pr.out] = (MODE == AM_INFIX ? !walk_on<MODE, FREE>(d, klo + s) : d == 0) ? D : ALIGN_WALK_LOST;
         n_ops[pr.out] = n;
+        if constexpr (MODE != AM_GLOBAL) {  // at an infix stop the free index is d (the other one is 0)
+            bounds[2 * pr.out] = MODE == AM_INFIX ? (uint32_t)d : 0u;
+            bounds[2 * pr.out + 1] = end;
+        }
     }
 }
 
@@ -230,25 +278,52 @@ void band_of(uint32_t tl, uint32_t rl, uint32_t t, int32_t &klo, int32_t &khi) {
     khi = std::min(khi, (int32_t)rl);
 }
 
-template <int THREADS>
+// The band of DESIGN section 4 for infix / prefix and a distance bound t >= max(0, whole length - free length), clipped to
+// the matrix: the free end may lie anywhere, so no halving as in band_of.
+void mode_band_of(int mode, int free_seq, uint32_t tl, uint32_t rl, uint32_t t, int32_t &klo, int32_t &khi) {
+    const int32_t delta = (int32_t)rl - (int32_t)tl, ti = (int32_t)t;
+    klo = free_seq == AF_TEMPLATE ? delta - ti : -ti;
+    khi = free_seq == AF_TEMPLATE ? ti : delta + ti;
+    if (mode == AM_PREFIX) {  // the start is pinned to diagonal 0
+        klo = std::max(klo, -ti);
+        khi = std::min(khi, ti);
+    }
+    klo = std::max(klo, -(int32_t)tl);
+    khi = std::min(khi, (int32_t)rl);
+}
+
+template <int THREADS, int MODE, int FREE>
 int launch_align(size_t n, size_t lds, const AlignPair *d_pairs, const uint8_t *d_bases, uint4 *d_scratch, uint8_t *d_ops,
-                 uint32_t *d_dist, uint32_t *d_nops) {
+                 uint32_t *d_dist, uint32_t *d_nops, uint32_t *d_bounds) {
     if (lds > 48 * 1024)
-        ALIGN_HIP(hipFuncSetAttribute((const void *)align_kernel<THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(align_kernel<THREADS>, dim3((unsigned)n), dim3(THREADS), lds, 0, d_pairs, d_bases, d_scratch, d_ops, d_dist,
-                       d_nops);
+        ALIGN_HIP(hipFuncSetAttribute((const void *)align_kernel<THREADS, MODE, FREE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((align_kernel<THREADS, MODE, FREE>), dim3((unsigned)n), dim3(THREADS), lds, 0, d_pairs, d_bases, d_scratch, d_ops,
+                       d_dist, d_nops, d_bounds);
     ALIGN_HIP(hipGetLastError());
     return 0;
 }
 
-}  // namespace
+template <int THREADS>
+int launch_align_any(int mode, int free_seq, size_t n, size_t lds, const AlignPair *d_pairs, const uint8_t *d_bases, uint4 *d_scratch,
+                     uint8_t *d_ops, uint32_t *d_dist, uint32_t *d_nops, uint32_t *d_bounds) {
+    if (mode == AM_GLOBAL) return launch_align<THREADS, AM_GLOBAL, AF_TEMPLATE>(n, lds, d_pairs, d_bases, d_scratch, d_ops, d_dist, d_nops, d_bounds);
+    if (mode == AM_INFIX)
+        return free_seq == AF_TEMPLATE
+                   ? launch_align<THREADS, AM_INFIX, AF_TEMPLATE>(n, lds, d_pairs, d_bases, d_scratch, d_ops, d_dist, d_nops, d_bounds)
+                   : launch_align<THREADS, AM_INFIX, AF_READ>(n, lds, d_pairs, d_bases, d_scratch, d_ops, d_dist, d_nops, d_bounds);
+    return free_seq == AF_TEMPLATE
+               ? launch_align<THREADS, AM_PREFIX, AF_TEMPLATE>(n, lds, d_pairs, d_bases, d_scratch, d_ops, d_dist, d_nops, d_bounds)
+               : launch_align<THREADS, AM_PREFIX, AF_READ>(n, lds, d_pairs, d_bases, d_scratch, d_ops, d_dist, d_nops, d_bounds);
+}
 
-extern "C" int jtk_lc_align_reads(size_t n_chunks, const jtk_lc_chunk_t *chunks, const uint8_t *tmpl_bases,
-                                  const uint8_t *read_bases, const uint64_t *read_off, uint32_t max_dist, uint8_t *ops_out,
-                                  uint64_t *ops_out_off, uint64_t ops_cap, uint32_t *dist_out, int32_t *read_status, int device) {
+// Both entry points.  mode == AM_GLOBAL: start_out / end_out may be null and free_seq is not looked at.
+int align_impl(size_t n_chunks, const jtk_lc_chunk_t *chunks, const uint8_t *tmpl_bases, const uint8_t *read_bases,
+               const uint64_t *read_off, int mode, int free_seq, uint32_t max_dist, uint8_t *ops_out, uint64_t *ops_out_off,
+               uint64_t ops_cap, uint32_t *dist_out, uint32_t *start_out, uint32_t *end_out, int32_t *read_status, int device) {
     jtk_internal_set_error("");
     if (n_chunks && (!chunks || !tmpl_bases || !read_bases || !read_off)) return afail(JTK_ERR_INVALID_ARG, "null input");
     if (!ops_out || !ops_out_off || !dist_out || !read_status) return afail(JTK_ERR_INVALID_ARG, "null output");
+    if (mode != AM_GLOBAL && (!start_out || !end_out)) return afail(JTK_ERR_INVALID_ARG, "null output");
     uint64_t n_reads = 0;
     for (size_t c = 0; c < n_chunks; c++) {
         if (chunks[c].read_first != n_reads) return afail(JTK_ERR_INVALID_ARG, "chunks must list their reads contiguously in order");
@@ -278,6 +353,7 @@ extern "C" int jtk_lc_align_reads(size_t n_chunks, const jtk_lc_chunk_t *chunks,
     std::vector<uint32_t> n_ops(n_reads, 0);
     std::vector<uint64_t> slot_end(n_reads, 0);
     std::vector<uint32_t> pending;
+    std::vector<uint32_t> settled;  // infix / prefix reads with an empty side: decided here
     {
         uint64_t need = ALIGN_PAD;
         for (size_t c = 0; c < n_chunks; c++) need += chunks[c].tmpl_len + ALIGN_PAD;
@@ -299,6 +375,7 @@ extern "C" int jtk_lc_align_reads(size_t n_chunks, const jtk_lc_chunk_t *chunks,
             bo += rl + ALIGN_PAD;
             read_status[r] = 0;
             dist_out[r] = 0xFFFFFFFFu;
+            if (mode != AM_GLOBAL) start_out[r] = end_out[r] = 0;
             if (tl > ALIGN_MAX_LEN || rl > ALIGN_MAX_LEN) {
                 read_status[r] = JTK_ERR_UNSUPPORTED;
                 continue;
@@ -308,6 +385,26 @@ extern "C" int jtk_lc_align_reads(size_t n_chunks, const jtk_lc_chunk_t *chunks,
             it.ops_off = slot;
             slot += tl + rl;
             slot_end[r] = slot;
+            if (mode != AM_GLOBAL) {
+                const uint64_t wl = free_seq == AF_TEMPLATE ? rl : tl, fl = free_seq == AF_TEMPLATE ? tl : rl;
+                if (wl == 0 || fl == 0) {  // nothing to place, or nowhere to place it: the whole sequence as Ins (Del)
+                    it.t = (uint32_t)wl;  // its distance and its op count
+                    settled.push_back((uint32_t)r);
+                    continue;
+                }
+                const uint32_t low = (uint32_t)(wl > fl ? wl - fl : 0);  // the whole sequence cannot lose fewer bases
+                it.bound = max_dist && max_dist < wl ? max_dist : (uint32_t)wl;  // the distance never exceeds the whole sequence
+                int32_t klo, khi;
+                mode_band_of(mode, free_seq, it.tl, it.rl, it.bound, klo, khi);
+                if (low > it.bound || khi - klo + 1 > ALIGN_MODE_MAX_BAND) {
+                    read_status[r] = JTK_ERR_UNSUPPORTED;
+                    continue;
+                }
+                // first try: a sixth of the whole sequence, as the global schedule's twelfth of two equal lengths
+                it.t = std::min<uint32_t>(it.bound, low + std::max<uint32_t>(32u, (uint32_t)(wl / 6)));
+                pending.push_back((uint32_t)r);
+                continue;
+            }
             const uint32_t delta = (uint32_t)(tl > rl ? tl - rl : rl - tl), longest = (uint32_t)std::max(tl, rl);
             it.bound = max_dist && max_dist < longest ? max_dist : longest;  // the distance never exceeds the longer sequence
             if (delta > it.bound) {
@@ -320,7 +417,7 @@ extern "C" int jtk_lc_align_reads(size_t n_chunks, const jtk_lc_chunk_t *chunks,
         }
     }
 
-    DevMem d_bases, d_ops, d_dist, d_nops, d_pairs, d_scratch;
+    DevMem d_bases, d_ops, d_dist, d_nops, d_pairs, d_scratch, d_bounds;
     ALIGN_HIP(hipMalloc(&d_bases.p, h_bases.size()));
     ALIGN_HIP(hipMemcpy(d_bases.p, h_bases.data(), h_bases.size(), hipMemcpyHostToDevice));
     ALIGN_HIP(hipMalloc(&d_ops.p, slot + 16));
@@ -328,6 +425,13 @@ extern "C" int jtk_lc_align_reads(size_t n_chunks, const jtk_lc_chunk_t *chunks,
     ALIGN_HIP(hipMalloc(&d_nops.p, (n_reads + 1) * 4));
     ALIGN_HIP(hipMemset(d_nops.p, 0, (n_reads + 1) * 4));
     ALIGN_HIP(hipMemset(d_dist.p, 0xFF, (n_reads + 1) * 4));
+    if (mode != AM_GLOBAL) {
+        ALIGN_HIP(hipMalloc(&d_bounds.p, (n_reads + 1) * 8));
+        ALIGN_HIP(hipMemset(d_bounds.p, 0, (n_reads + 1) * 8));
+        for (uint32_t r : settled)  // with the free side empty the slot of tl + rl bytes is the whole sequence's
+            if (items[r].t)
+                ALIGN_HIP(hipMemset((uint8_t *)d_ops.p + items[r].ops_off, free_seq == AF_TEMPLATE ? JTK_OP_INS : JTK_OP_DEL, items[r].t));
+    }
 
     // ---- rounds: every pending pair with its current t; those that come back above it double t
     const uint64_t budget16 = (uint64_t)4 << (30 - 4);  // move-code scratch per launch: 4 GiB, in 16-byte units
@@ -347,7 +451,10 @@ extern "C" int jtk_lc_align_reads(size_t n_chunks, const jtk_lc_chunk_t *chunks,
             p.read_len = it.rl;
             p.t = it.t;
             p.out = pending[a];
-            band_of(it.tl, it.rl, it.t, p.klo, p.khi);
+            if (mode == AM_GLOBAL)
+                band_of(it.tl, it.rl, it.t, p.klo, p.khi);
+            else
+                mode_band_of(mode, free_seq, it.tl, it.rl, it.t, p.klo, p.khi);
         }
         std::stable_sort(prs.begin(), prs.end(), [](const AlignPair &a, const AlignPair &b) { return a.khi - a.klo > b.khi - b.klo; });
         if (prs.size() > pairs_have) {
@@ -382,14 +489,14 @@ extern "C" int jtk_lc_align_reads(size_t n_chunks, const jtk_lc_chunk_t *chunks,
             const size_t lds = lds_bytes_of(G0);  // the launch's widest band comes first
             int rc;
             if (threads == 64)
-                rc = launch_align<64>(b - a, lds, (AlignPair *)d_pairs.p + a, (uint8_t *)d_bases.p, (uint4 *)d_scratch.p, (uint8_t *)d_ops.p,
-                                      (uint32_t *)d_dist.p, (uint32_t *)d_nops.p);
+                rc = launch_align_any<64>(mode, free_seq, b - a, lds, (AlignPair *)d_pairs.p + a, (uint8_t *)d_bases.p, (uint4 *)d_scratch.p,
+                                          (uint8_t *)d_ops.p, (uint32_t *)d_dist.p, (uint32_t *)d_nops.p, (uint32_t *)d_bounds.p);
             else if (threads == 256)
-                rc = launch_align<256>(b - a, lds, (AlignPair *)d_pairs.p + a, (uint8_t *)d_bases.p, (uint4 *)d_scratch.p, (uint8_t *)d_ops.p,
-                                       (uint32_t *)d_dist.p, (uint32_t *)d_nops.p);
+                rc = launch_align_any<256>(mode, free_seq, b - a, lds, (AlignPair *)d_pairs.p + a, (uint8_t *)d_bases.p, (uint4 *)d_scratch.p,
+                                           (uint8_t *)d_ops.p, (uint32_t *)d_dist.p, (uint32_t *)d_nops.p, (uint32_t *)d_bounds.p);
             else
-                rc = launch_align<1024>(b - a, lds, (AlignPair *)d_pairs.p + a, (uint8_t *)d_bases.p, (uint4 *)d_scratch.p, (uint8_t *)d_ops.p,
-                                        (uint32_t *)d_dist.p, (uint32_t *)d_nops.p);
+                rc = launch_align_any<1024>(mode, free_seq, b - a, lds, (AlignPair *)d_pairs.p + a, (uint8_t *)d_bases.p, (uint4 *)d_scratch.p,
+                                            (uint8_t *)d_ops.p, (uint32_t *)d_dist.p, (uint32_t *)d_nops.p, (uint32_t *)d_bounds.p);
             if (rc) return rc;
             ALIGN_HIP(hipDeviceSynchronize());  // the next launch reuses the scratch
             a = b;
@@ -413,6 +520,16 @@ extern "C" int jtk_lc_align_reads(size_t n_chunks, const jtk_lc_chunk_t *chunks,
     // ---- pack the ops of every read behind each other and fetch them with one copy
     ALIGN_HIP(hipMemcpy(n_ops.data(), d_nops.p, n_reads * 4, hipMemcpyDeviceToHost));
     ALIGN_HIP(hipMemcpy(h_dist.data(), d_dist.p, n_reads * 4, hipMemcpyDeviceToHost));
+    for (uint32_t r : settled) n_ops[r] = h_dist[r] = items[r].t;
+    if (mode != AM_GLOBAL) {
+        std::vector<uint32_t> h_bounds(2 * n_reads + 2);
+        ALIGN_HIP(hipMemcpy(h_bounds.data(), d_bounds.p, n_reads * 8, hipMemcpyDeviceToHost));
+        for (uint64_t r = 0; r < n_reads; r++)
+            if (!read_status[r]) {
+                start_out[r] = h_bounds[2 * r];
+                end_out[r] = h_bounds[2 * r + 1];
+            }
+    }
     int rc = 0;
     uint64_t total = 0;
     for (uint64_t r = 0; r < n_reads; r++) {
@@ -439,6 +556,39 @@ extern "C" int jtk_lc_align_reads(size_t n_chunks, const jtk_lc_chunk_t *chunks,
         ALIGN_HIP(hipGetLastError());
         ALIGN_HIP(hipMemcpy(ops_out, d_out.p, total, hipMemcpyDeviceToHost));
     }
-    if (rc) jtk_internal_set_error("a read lies farther from its template than max_dist (or is longer than 32,000 bases)");
+    if (rc)
+        jtk_internal_set_error(mode == AM_GLOBAL
+                                   ? "a read lies farther from its template than max_dist (or is longer than 32,000 bases)"
+                                   : "a pair lies farther apart than max_dist (or is longer than 32,000 bases, or its band at the "
+                                     "largest distance allowed is wider than 32,768 diagonals: give max_dist)");
+    return rc;
+}
+
+}  // namespace
+
+extern "C" int jtk_lc_align_reads(size_t n_chunks, const jtk_lc_chunk_t *chunks, const uint8_t *tmpl_bases,
+                                  const uint8_t *read_bases, const uint64_t *read_off, uint32_t max_dist, uint8_t *ops_out,
+                                  uint64_t *ops_out_off, uint64_t ops_cap, uint32_t *dist_out, int32_t *read_status, int device) {
+    return align_impl(n_chunks, chunks, tmpl_bases, read_bases, read_off, AM_GLOBAL, AF_TEMPLATE, max_dist, ops_out, ops_out_off,
+                      ops_cap, dist_out, nullptr, nullptr, read_status, device);
+}
+
+extern "C" int jtk_lc_align_reads_mode(size_t n_chunks, const jtk_lc_chunk_t *chunks, const uint8_t *tmpl_bases,
+                                       const uint8_t *read_bases, const uint64_t *read_off, int mode, int free_seq,
+                                       uint32_t max_dist, uint8_t *ops_out, uint64_t *ops_out_off, uint64_t ops_cap,
+                                       uint32_t *dist_out, uint32_t *start_out, uint32_t *end_out, int32_t *read_status, int device) {
+    if (mode != JTK_ALIGN_GLOBAL && mode != JTK_ALIGN_INFIX && mode != JTK_ALIGN_PREFIX) return afail(JTK_ERR_INVALID_ARG, "unknown alignment mode");
+    if (mode != JTK_ALIGN_GLOBAL && free_seq != JTK_ALIGN_FREE_TEMPLATE && free_seq != JTK_ALIGN_FREE_READ)
+        return afail(JTK_ERR_INVALID_ARG, "unknown free sequence");
+    if (!start_out || !end_out) return afail(JTK_ERR_INVALID_ARG, "null output");
+    const int rc = align_impl(n_chunks, chunks, tmpl_bases, read_bases, read_off, mode, free_seq, max_dist, ops_out, ops_out_off, ops_cap,
+                              dist_out, start_out, end_out, read_status, device);
+    if (mode == JTK_ALIGN_GLOBAL && (rc == 0 || rc == JTK_ERR_CHUNK_FAILED))  // everything is consumed: [0, template length)
+        for (size_t c = 0; c < n_chunks; c++)
+            for (uint32_t q = 0; q < chunks[c].n_reads; q++) {
+                const uint64_t r = chunks[c].read_first + q;
+                start_out[r] = 0;
+                end_out[r] = read_status[r] ? 0 : (uint32_t)chunks[c].tmpl_len;
+            }
     return rc;
 }

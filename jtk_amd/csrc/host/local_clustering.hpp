@@ -167,6 +167,69 @@ inline std::vector<Ops> global_align(const std::string &tmpl, const std::vector<
     return out;
 }
 
+// One jtk_lc_align_reads_mode call for one pile-up.
+struct PlacedAlignment {
+    Ops ops;            // consume [start, end) of the free sequence and all of the whole one
+    uint32_t dist, start, end;
+    std::vector<uint8_t> kiley;  // the same ops, one byte per column
+};
+inline std::vector<PlacedAlignment> align_mode(const std::string &tmpl, const std::vector<std::string> &reads, int mode, int free_seq,
+                                               int device = 0) {
+    jtk_lc_chunk_t ch{};
+    ch.n_reads = (uint32_t)reads.size();
+    ch.tmpl_len = tmpl.size();
+    std::vector<uint8_t> bases;
+    std::vector<uint64_t> off(reads.size() + 1, 0);
+    for (size_t r = 0; r < reads.size(); r++) {
+        bases.insert(bases.end(), reads[r].begin(), reads[r].end());
+        off[r + 1] = bases.size();
+    }
+    bases.push_back(0);
+    const uint64_t cap = bases.size() + tmpl.size() * reads.size() + 1;
+    std::vector<uint8_t> ops(cap);
+    std::vector<uint64_t> ops_off(reads.size() + 1);
+    std::vector<uint32_t> dist(reads.size() + 1), start(reads.size() + 1), end(reads.size() + 1);
+    std::vector<int32_t> status(reads.size() + 1);
+    const std::string t = tmpl.empty() ? std::string(1, '\0') : tmpl;
+    const int rc = jtk_lc_align_reads_mode(1, &ch, (const uint8_t *)t.data(), bases.data(), off.data(), mode, free_seq, 0, ops.data(),
+                                           ops_off.data(), cap, dist.data(), start.data(), end.data(), status.data(), device);
+    if (rc != 0) throw std::runtime_error(std::string("align_mode: ") + jtk_lc_strerror(rc) + ": " + jtk_lc_last_error());
+    std::vector<PlacedAlignment> out;
+    for (size_t r = 0; r < reads.size(); r++) {
+        const uint8_t *k = ops.data() + ops_off[r];
+        const size_t n = (size_t)(ops_off[r + 1] - ops_off[r]);
+        out.push_back(PlacedAlignment{kiley_op_to_ops(k, n), dist[r], start[r], end[r], std::vector<uint8_t>(k, k + n)});
+    }
+    return out;
+}
+
+// edlib Infix / Alignment with `free_seq` the target (`align_infix`, consensus/mod.rs:563-572; encode/deletion_fill.rs:544-554,
+// dense_encoding.rs:728-757, determine_chunks.rs:520-538): every read against `tmpl`, both ends of the free sequence free.
+inline std::vector<PlacedAlignment> infix_align(const std::string &tmpl, const std::vector<std::string> &reads,
+                                                int free_seq = JTK_ALIGN_FREE_TEMPLATE, int device = 0) {
+    return align_mode(tmpl, reads, JTK_ALIGN_INFIX, free_seq, device);
+}
+
+// edlib Prefix / Alignment (`align_trailing`, consensus/mod.rs:599-614): the free sequence is consumed from its first base.
+inline std::vector<PlacedAlignment> prefix_align(const std::string &tmpl, const std::vector<std::string> &reads,
+                                                 int free_seq = JTK_ALIGN_FREE_TEMPLATE, int device = 0) {
+    return align_mode(tmpl, reads, JTK_ALIGN_PREFIX, free_seq, device);
+}
+
+// `semiglobal` (encode/mod.rs:227-246): refr placed inside every query; the query's bases in front of `start` and behind `end`
+// become Ins, so the ops consume both sequences whole (one byte per column, as kiley takes them).
+inline std::vector<std::vector<uint8_t>> semiglobal(const std::string &refr, const std::vector<std::string> &queries, int device = 0) {
+    std::vector<std::vector<uint8_t>> out;
+    const std::vector<PlacedAlignment> al = align_mode(refr, queries, JTK_ALIGN_INFIX, JTK_ALIGN_FREE_READ, device);
+    for (size_t r = 0; r < queries.size(); r++) {
+        std::vector<uint8_t> ops(al[r].start, (uint8_t)JTK_OP_INS);
+        ops.insert(ops.end(), al[r].kiley.begin(), al[r].kiley.end());
+        ops.insert(ops.end(), queries[r].size() - al[r].end, (uint8_t)JTK_OP_INS);
+        out.push_back(std::move(ops));
+    }
+    return out;
+}
+
 // misc.rs:394-407
 inline void update_coverage(DataSet &ds) {
     if (ds.coverage.is_protected()) return;

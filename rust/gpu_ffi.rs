@@ -82,6 +82,13 @@ extern "C" {
         n_chunks: usize, chunks: *const JtkLcChunk, tmpl_bases: *const u8, read_bases: *const u8, read_off: *const u64,
         max_dist: u32, ops_out: *mut u8, ops_out_off: *mut u64, ops_cap: u64,
         dist_out: *mut u32, read_status: *mut i32, device: c_int) -> c_int;
+    // edlib Infix / Prefix / Alignment (mode 1 / 2; 0 = the call above), free_seq 0 = the template is edlib's target, 1 = the read:
+    // encode/mod.rs:227-246, encode/deletion_fill.rs:544-554, dense_encoding.rs:728-757, determine_chunks.rs:520-538,
+    // consensus/mod.rs:563-614; the ops consume [start_out[r], end_out[r]) of the free sequence
+    pub fn jtk_lc_align_reads_mode(
+        n_chunks: usize, chunks: *const JtkLcChunk, tmpl_bases: *const u8, read_bases: *const u8, read_off: *const u64,
+        mode: c_int, free_seq: c_int, max_dist: u32, ops_out: *mut u8, ops_out_off: *mut u64, ops_cap: u64,
+        dist_out: *mut u32, start_out: *mut u32, end_out: *mut u32, read_status: *mut i32, device: c_int) -> c_int;
     // AlignmentCorrection::correct_clustering_selected (phmm_likelihood_correction.rs:32-97)
     pub fn jtk_lc_correct_clustering(
         n_reads: usize, read_id: *const u64, node_off: *const u64, nodes: *const JtkCcNode, posteriors: *const f64,

@@ -5,6 +5,10 @@ compares every function's instructions (labels normalised).  Used when a change 
 recording instantiations behind jtk_lc_session_trace: `same` for every product kernel, `NEW` for the added ones.  No GPU needed.
 
     python3 scripts/isa_same.py mcmc_kernels.hip filter_kernels.hip [--rev HEAD]
+
+A kernel whose mangled name changed without its code changing (template parameters added, a trailing argument) is paired by
+hand: `--renamed SUBSTRING_OF_OLD_NAME=SUBSTRING_OF_NEW_NAME` (repeatable) compares the one old function whose name contains
+the first with the one new function whose name contains the second and prints both names.
 """
 import argparse
 import os
@@ -53,6 +57,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("sources", nargs="+")
     ap.add_argument("--rev", default="HEAD")
+    ap.add_argument("--renamed", action="append", default=[], metavar="OLD=NEW")
     a = ap.parse_args()
     bad = 0
     with tempfile.TemporaryDirectory() as tmp:
@@ -66,10 +71,22 @@ def main():
             assemble(ROOT, src, sn)
             fo, fn = functions(so), functions(sn)
             print("== %s: working tree against %s" % (src, a.rev))
+            for pair in a.renamed:
+                o, n = pair.split("=")
+                ko, kn = [k for k in fo if o in k], [k for k in fn if n in k]
+                if len(ko) != 1 or len(kn) != 1:
+                    continue
+                same = fo[ko[0]] == fn[kn[0]]
+                print("%s %s %d\n  -> %s %d" % ("same (renamed)" if same else "DIFF (renamed)", ko[0][:120], len(fo[ko[0]]), kn[0][:120], len(fn[kn[0]])))
+                bad += 0 if same else 1
+                fn[ko[0]] = fo[ko[0]]                    # listed above: neither GONE ...
+                fo[kn[0]] = fn[kn[0]]                    # ... nor NEW below
             for k in sorted(fo):
                 if k not in fn:
                     print("GONE", k[:120], len(fo[k]))
                     bad += 1
+                elif fo[k] is fn[k]:
+                    continue
                 elif fo[k] != fn[k]:
                     print("DIFF", k[:120], len(fo[k]), len(fn[k]))
                     bad += 1
