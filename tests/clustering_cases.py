@@ -1,9 +1,10 @@
 """The feature-level problems of tests/test_clustering_reference.py and tests/test_gpu_clustering_reference.py: small read
 counts (the Python chain of tests/clustering_reference.py makes 2000 n proposals per restart, 20 restarts per tried cluster count),
 every case built for a branch of pseudo_mcmc.rs:213-408, 649-869 / misc.rs:231-341 and listed with the predicate on the
-reference's own log that shows the branch was entered (REACHES).  The device's dispatch decides the shapes: every case has
-n <= 63 reads, so the diploid ones run mcmc_chain_k2<D, 1> with D = the column count (1, 2, 3, 4, 5-8), copy numbers 3 and 4 run
-mcmc_chain_tab<3> / <4>, and diploid_nine_columns runs mcmc_chain_tab<2> (D > 8).
+reference's own log that shows the branch was entered (REACHES).  The device's dispatch decides the shapes: every case of CASES
+has n <= 63 reads, so the diploid ones run mcmc_chain_k2<D, 1> with D = the column count (1, 2, 3, 4, 5-8), copy numbers 3 and 4 run
+mcmc_chain_tab<3> / <4>, and diploid_nine_columns runs mcmc_chain_tab<2> (D > 8).  LARGE_CASES (64 to 256 reads) are the
+smallest shapes of every other path of that dispatch short of mcmc_kernel_huge and the recursive split.
 
 A case is dict(x = n x dim matrix, vt = dim x (homopolymer length, diff type), copy_num, coverage (haploid), local_coverage,
 chunk_id).  Values are drawn once from numpy's PCG64 with fixed seeds and rounded to 1/64, so a case is the same on every machine.
@@ -183,10 +184,126 @@ REACHED_SOMEWHERE = {
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# 64 reads and more: the device paths no case above reaches.  The dispatch (chain_split_kernel, mcmc_chain_dispatch):
+#   copy 2, n <= 127, D <= 2          mcmc_kernel_light, mcmc_chain_k2<1, 2> (D == 1) / <2, 2> (D == 2): two table registers,
+#                                     read and size indices 64 r + lane
+#   copy 2, n <= 127, 3 <= D <= 8     mcmc_kernel, mcmc_chain_k2<4, 2> (D = 3 AND 4) / <8, 2> (D = 5 .. 8)
+#   copy 2, n >= 128 or D >= 9        mcmc_kernel, mcmc_chain_tab<2> with SMALL false (n >= 64); its tables leave the registers
+#   copy 3, 4                         mcmc_chain_tab<3> / <4>, SMALL false                   for LDS beyond 255 reads (big)
+# The haploid coverage is about n / copy_num (the size prior of a real pile-up) and shared within a group, since it is a
+# parameter of the device call: 32 (n = 64 .. 70), 40 (n = 80 .. 88), 60 (n = 120 .. 128), 20 (copies 3 and 4), 128 (n = 255, 256).
+# Moving a read out of its cluster costs D amp (amp where it leaves, amp where it lands), so the columns of D >= 2 have an
+# amplitude of 7 / D: about one proposal in a thousand is taken and reversed, among them reads of index >= 64, while the
+# clusters stay the true ones (n D amp / 2 = 3.5 n is above the expected gain of 0.8 * 4.56 n / 2).
+# ---------------------------------------------------------------------------------------------------------------------------
+def _large_diploid(n, dim, seed, chunk_id, coverage, first=None):
+    """two clusters taking turns over the first 2 * min(first, n - first) reads, the rest of cluster 0 (`first` = its size)"""
+    first = (n + 1) // 2 if first is None else first
+    turns = 2 * min(first, n - first)
+    labels = [r % 2 for r in range(turns)] + [0 if first > n - first else 1] * (n - turns)
+    assert labels.count(0) == first
+    amp = 4.5 if dim == 1 else 7.0 / dim
+    return _case(_clean(seed, labels, [d % 2 for d in range(dim)], hi=amp, lo=-amp, spread=amp / 4), 2, chunk_id, coverage=coverage)
+
+
+def _copies(n, copy_num, seed, chunk_id, coverage):
+    """as many true clusters as copies, one column each: +4.5 in its own reads, -2.5 elsewhere (a move costs 7, a new cluster
+    gains 4.5 per read, above the 0.8 * 4.56 expected)"""
+    labels = [r % copy_num for r in range(n)]
+    return _case(_clean(seed, labels, list(range(copy_num)), hi=4.5, lo=-2.5), copy_num, chunk_id, coverage=coverage)
+
+
+LARGE_CASES = {
+    # mcmc_kernel_light, mcmc_chain_k2<1, 2>: read 64 is the first in the second table register
+    "light_64_reads_1_column": lambda: _large_diploid(64, 1, 601, 601, 32.0),
+    # mcmc_kernel_light, <2, 2>: both ends of its range
+    "light_65_reads_2_columns": lambda: _large_diploid(65, 2, 602, 602, 32.0),
+    "light_127_reads_2_columns": lambda: _large_diploid(127, 2, 603, 603, 60.0),
+    # mcmc_kernel, <4, 2> by D = 3 and by D = 4 (one instantiation, unlike <3, 1> and <4, 1>), <8, 2> by D = 6 and D = 8
+    "k2_64_reads_3_columns": lambda: _large_diploid(64, 3, 604, 604, 32.0),
+    "k2_88_reads_4_columns": lambda: _large_diploid(88, 4, 605, 605, 40.0),
+    "k2_80_reads_6_columns": lambda: _large_diploid(80, 6, 606, 606, 40.0),
+    "k2_127_reads_8_columns": lambda: _large_diploid(127, 8, 607, 607, 60.0),
+    # the headline read count, <4, 2>: a cluster of 70 reads, whose size prior is read from the size table's second register
+    "k2_120_reads_70_and_50": lambda: _large_diploid(120, 3, 608, 608, 60.0, first=70),
+    # <2, 2>, weak columns: most proposals are taken, so the walk over certainly-rejected proposals keeps restarting and the
+    # per-read flipped likelihoods are rebuilt after every move
+    "light_80_reads_weak_columns": lambda: _case(weak(609, n=80, dim=2, amp=0.2), 2, 609, coverage=40.0),
+    # <2, 2>, 13 all-zero rows at 68 .. 80: their moves change the sizes only; 41 against 40 (n is odd for that) a move swaps
+    # the sizes, diff == 0 and gen_bool(1.0) draws nothing
+    "light_81_reads_zero_rows": lambda: _case(np.vstack([_large_diploid(68, 2, 610, 0, 0.0)["x"], np.zeros((13, 2))]), 2, 610,
+                                              coverage=40.0),
+    # mcmc_chain_tab<2>, SMALL false: by the first n past the diploid chain, and by the column count
+    "tab2_128_reads_3_columns": lambda: _large_diploid(128, 3, 611, 611, 60.0),
+    "tab2_70_reads_9_columns": lambda: _large_diploid(70, 9, 612, 612, 32.0),
+    # mcmc_chain_tab<3> / <4>, SMALL false, for k = 3 (and 4); their k = 2 round is mcmc_chain_k2<4, 2> once more
+    "tab3_66_reads": lambda: _copies(66, 3, 613, 613, 20.0),
+    "tab4_68_reads": lambda: _copies(68, 4, 614, 614, 20.0),
+    # either side of big = n > 255: mcmc_chain_tab<2> with its tables in registers (255) and in LDS (256)
+    "tab2_255_reads": lambda: _large_diploid(255, 1, 615, 615, 128.0),
+    "tab2_256_reads": lambda: _large_diploid(256, 1, 616, 616, 128.0),
+}
+
+
+def device_path(case):
+    """(kernel, chain) that chain_split_kernel and mcmc_chain_dispatch send a case to, restated from their conditions; for a
+    copy number above 2 the chain of k = copy_num (the rounds of smaller k dispatch on k as a diploid case does on 2)"""
+    (n, dim), cp = case["x"].shape, case["copy_num"]
+    if cp == 2 and n <= 127 and 1 <= dim <= 8:
+        if n <= 63:
+            return ("mcmc_kernel_light" if dim <= 2 else "mcmc_kernel", "mcmc_chain_k2<%d, 1>" % (dim if dim <= 4 else 8))
+        return ("mcmc_kernel_light" if dim <= 2 else "mcmc_kernel", "mcmc_chain_k2<%d, 2>" % (dim if dim <= 2 else 4 if dim <= 4 else 8))
+    return ("mcmc_kernel", "mcmc_chain_tab<%d>%s" % (cp, " SMALL" if n <= 63 else " big" if n > 255 else ""))
+
+
+def _accepted(g):
+    return all(t["accepted"] for t in g.tried)
+
+
+_moves_a_high_read = lambda g: g.chain["high_read_moves"] > 0
+_crosses_64 = lambda g: g.chain["crossed_64"] > 0
+# case -> predicate on the reference's log
+LARGE_REACHES = {
+    "light_64_reads_1_column": lambda g: _accepted(g),   # (reads 0 .. 63: what it adds is the size 64 and the two-register chain)
+    "light_65_reads_2_columns": lambda g: _moves_a_high_read(g) and _accepted(g),
+    "light_127_reads_2_columns": lambda g: _moves_a_high_read(g) and _crosses_64(g) and _accepted(g),
+    "k2_64_reads_3_columns": lambda g: _accepted(g),
+    "k2_88_reads_4_columns": lambda g: _moves_a_high_read(g) and _accepted(g),
+    "k2_80_reads_6_columns": lambda g: _moves_a_high_read(g) and _accepted(g),
+    "k2_127_reads_8_columns": lambda g: _moves_a_high_read(g) and _crosses_64(g) and _accepted(g),
+    "k2_120_reads_70_and_50": lambda g: _moves_a_high_read(g) and sorted(g.tried[0]["sizes"]) == [50, 70] and _accepted(g),
+    # more than half of ALL proposals are taken, and more than half of those that go downhill (an uphill proposal is always
+    # taken and in equilibrium as many moves go up as down, so downhill_taken alone stays below half of all proposals)
+    "light_80_reads_weak_columns": lambda g: _moves_a_high_read(g)
+    and g.chain["downhill_taken"] + g.chain["zero_diff"] + g.chain["uphill"] > 0.5 * g.chain["proposals"]
+    and g.chain["downhill_taken"] > 0.5 * (g.chain["downhill_taken"] + g.chain["rejected"]),
+    "light_81_reads_zero_rows": lambda g: g.chain["zero_diff"] > 0 and _moves_a_high_read(g) and _accepted(g),
+    "tab2_128_reads_3_columns": lambda g: _moves_a_high_read(g) and _crosses_64(g) and _accepted(g),
+    "tab2_70_reads_9_columns": lambda g: _moves_a_high_read(g) and _accepted(g),
+    "tab3_66_reads": lambda g: g.range == (2, 3) and [t["k"] for t in g.tried] == [2, 3] and _moves_a_high_read(g) and _accepted(g),
+    "tab4_68_reads": lambda g: g.range == (2, 4) and [t["k"] for t in g.tried] == [2, 3, 4] and _moves_a_high_read(g) and _accepted(g),
+    "tab2_255_reads": lambda g: _moves_a_high_read(g) and min(g.tried[0]["sizes"]) > 63 and _accepted(g),
+    "tab2_256_reads": lambda g: _moves_a_high_read(g) and min(g.tried[0]["sizes"]) > 63 and _accepted(g),
+}
+LARGE_REACHED_SOMEWHERE = {
+    "a chain whose best state is not its last": lambda g: g.chain["best_not_last"] > 0,
+}
+# what the large cases cover between them: (copy number, reads, columns) classes of the dispatch -> (kernel, chain)
+LARGE_PATHS = {
+    ("mcmc_kernel_light", "mcmc_chain_k2<1, 2>"), ("mcmc_kernel_light", "mcmc_chain_k2<2, 2>"), ("mcmc_kernel", "mcmc_chain_k2<4, 2>"),
+    ("mcmc_kernel", "mcmc_chain_k2<8, 2>"), ("mcmc_kernel", "mcmc_chain_tab<2>"), ("mcmc_kernel", "mcmc_chain_tab<2> big"),
+    ("mcmc_kernel", "mcmc_chain_tab<3>"), ("mcmc_kernel", "mcmc_chain_tab<4>"),
+}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # pile-ups: reads, not feature matrices (the candidate filter, jtk_lc_cluster_polished, Session.trace)
 # ---------------------------------------------------------------------------------------------------------------------------
 PILEUPS = {"ont_diploid": {}, "hifi_diploid": {}, "ont_4copy": dict(reads_per_hap=8, tmpl_len=200, divergence=2e-2, min_variants=3),
-           "planted": None}
+           "planted": None,
+           # 80 reads through the session path, which classifies chains by their LDS need: ont_diploid at 40 reads per haplotype on
+           # 200 bp, diverged enough for five candidate columns, three of them picked; the haploid coverage is the reads per haplotype
+           "ont_diploid_80_reads": dict(base="ont_diploid", coverage=40.0, reads_per_hap=40, tmpl_len=200, divergence=3e-2, min_variants=3)}
 
 # planted(): the variants the reads carry, as (name, template position, row of the 14, the filter of filter_profiles :440-465 that
 # must drop the column, None = it must become a candidate)
@@ -248,10 +365,13 @@ def planted():
 
 def pileup(config):
     """(batch, params) of one pile-up; with fewer reads per haplotype the haploid coverage is 1.25 times that read count (above
-    n / copy_num, so that a copy number above 2 takes the coverage as its local coverage, mod.rs:110)"""
+    n / copy_num, so that a copy number above 2 takes the coverage as its local coverage, mod.rs:110) unless the entry names its own"""
     if config == "planted":
         return planted()[:2]
     from jtk_amd import batch as jb, synth
-    b, cfg = synth.make_batch(config, 1, **PILEUPS[config])
-    return b, jb.default_params((1.25 * PILEUPS[config]["reads_per_hap"] if "reads_per_hap" in PILEUPS[config] else cfg["coverage"]),
-                                cfg["band_frac"])
+    kw = dict(PILEUPS[config])
+    base, coverage = kw.pop("base", config), kw.pop("coverage", None)
+    b, cfg = synth.make_batch(base, 1, **kw)
+    if coverage is None:
+        coverage = 1.25 * kw["reads_per_hap"] if "reads_per_hap" in kw else cfg["coverage"]
+    return b, jb.default_params(coverage, cfg["band_frac"])

@@ -162,7 +162,7 @@ class Log:
         self.last_restarts = None   # of the latest mcmc_clustering: scores, the restart kept, ties
         self.early_return = None
         self.chain = dict(proposals=0, zero_diff=0, uphill=0, downhill_taken=0, rejected=0, best_not_last=0, emptied=0, chains=0,
-                          dataless_moves=0)
+                          dataless_moves=0, high_read_moves=0, crossed_64=0)
         self.kmeans = dict(random_start=0, seeded_start=0, zero_weights=0, rounds=0)
         self.tail = dict(changed=0, within_margin=0)
         self.draws = 0
@@ -455,7 +455,7 @@ def mcmc_with_filter(data, asn, k, cov, rng, B, log=None):
     zones32 = [0] + [((m << (32 - m.bit_length())) - 1) & 0xFFFFFFFF for m in range(1, k)]   # gen_index(m), m = 1 .. k - 1
     cols, clusters = range(dim), range(k)
     margin, ties = INF, 0
-    zero_diff = uphill = downhill = rejected = emptied = 0
+    zero_diff = uphill = downhill = rejected = emptied = high_read_moves = crossed_64 = 0
     for _ in range(2000 * n):
         while True:                                                         # idx = rng.gen_range(0..n)
             x = (s1 * 5) & M64
@@ -570,6 +570,10 @@ def mcmc_with_filter(data, asn, k, cov, rng, B, log=None):
             lk = proposed
             if size[old] == 0:
                 emptied += 1
+            if idx >= 64:                                                   # the device's second table register (read 64 r + lane)
+                high_read_moves += 1
+            if size[old] == 63 or size[new] == 64:                          # a cluster size went 64 -> 63 or 63 -> 64
+                crossed_64 += 1
             if best != lk:
                 a = abs(best - lk)
                 if a < margin:
@@ -598,7 +602,8 @@ def mcmc_with_filter(data, asn, k, cov, rng, B, log=None):
     st = log.chain
     st["chains"] += 1
     st["proposals"] += 2000 * n
-    for key, v in (("zero_diff", zero_diff), ("uphill", uphill), ("downhill_taken", downhill), ("rejected", rejected), ("emptied", emptied)):
+    for key, v in (("zero_diff", zero_diff), ("uphill", uphill), ("downhill_taken", downhill), ("rejected", rejected), ("emptied", emptied),
+                   ("high_read_moves", high_read_moves), ("crossed_64", crossed_64)):
         st[key] += v
     log.exact_ties += ties
     if margin < log.margin:

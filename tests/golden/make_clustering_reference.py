@@ -16,6 +16,7 @@ if __name__ == "__main__":
     import test_clustering_reference as T
     refs = T.references()
     out = dict(cases={name: T.as_fixture(refs[(name, "project")]) for name in T.NAMES},
+               large_cases={name: T.as_fixture(refs[(name, "project")]) for name in T.LARGE_NAMES},
                pileups={config: T.as_pileup_fixture(T.pileup_reference(config)) for config in T.PILEUPS})
     with open(T.GOLDEN, "w") as fh:
         json.dump(out, fh, indent=1, sort_keys=True)

@@ -21,11 +21,18 @@ labels and the cluster count must be equal and
                      libraries: 390 ulp of a size table below 256 in magnitude (asserted per case) is 2.2e-11.  A libm case may
                      differ in labels only if its log shows such a decision, and at most one case in ten may (asserted; share
                      measured: 0 of 24).
-Feature cases: none dropped for the reference's cost; read counts are 2 to 11.  Pile-ups (clustering_cases.PILEUPS): ont_diploid
+Feature cases: none dropped for the reference's cost; read counts are 2 to 11 (clustering_cases.CASES) and 64 to 256
+(LARGE_CASES: the smallest shape of every device path past 63 reads, each with a predicate on the reference's log,
+test_large_cases_reach_their_branches).  The large cases run with the project's exp / log ONLY.  The libm comparison is not
+extended to them: LIBM_TOLERANCE counts n + 1 <= 12 logarithms per size-table entry and DECISION_BOUND assumes a size table below
+256 in magnitude, and neither holds at 256 reads (257 logarithms; 256 ln 256 alone is 1420).  Not covered at any size:
+mcmc_kernel_huge's shapes (more than 1,023 reads: 41 M proposals per tried k) and the recursive split of copy numbers of 8 and
+more; both stay pinned to the oracle by tests/test_gpu_parity.py and tests/test_gpu_shapes.py.  Pile-ups (clustering_cases.PILEUPS): ont_diploid
 and hifi_diploid as synth makes them, ont_4copy reduced to 8 reads per haplotype on 200 bp (at 160 reads the Python chain took
-386 s), and `planted`, 24 hand-made reads whose variants fail one filter each (clustering_cases.planted); the same four run on the
+386 s), and `planted`, 24 hand-made reads whose variants fail one filter each (clustering_cases.planted); the same run on the
 device.  test_planted_columns_are_dropped_by_their_own_filter adds a profile matrix at the filter's interface for the columns no
-read can carry (copy rows, the positions just inside the mask, an insertion next to its own base).
+read can carry (copy rows, the positions just inside the mask, an insertion next to its own base).  A fifth pile-up,
+ont_diploid_80_reads (40 reads per haplotype on 200 bp, five candidate columns, three picked), is the only one above 63 reads.
 
 The references are computed once per process, in a pool of up to 8 worker processes, and compared with
 tests/golden/clustering_reference.json, the committed outputs the GPU module reads (tests/golden/make_clustering_reference.py
@@ -51,7 +58,10 @@ from helpers import bits, oracle_params
 from jtk_amd import batch as jb, ffi
 
 LIBM_TOLERANCE = 1024
-RUN_TIME = "about 180 s on 8 CPUs, 56 tests (measured: 279 s together with the CPU tests of tests/test_trace_rows.py, which take 100 s): 35 s for the feature references in the pool (both back ends, 300 CPU-seconds), 20 + 30 + 70 + 8 s of Python chain for the four pile-ups"
+RUN_TIME = ("about 320 to 390 s on 8 CPUs, 77 tests (two measured runs; the parent: about 180 s, 56 tests): 165 to 200 s for the feature references in the pool "
+            "(both back ends for the small cases, the project's for the 16 large ones: 1,400 CPU-seconds; the longest single job is tab4_68_reads, three "
+            "tried k, 161 s on its own, then tab2_256_reads, 109 s), 20 + 30 + 70 + 8 + 38 s of Python chain for the five pile-ups, 10 s for the three large "
+            "single chains")
 SEEDED_FAULTS = {   # one-line changes to an uncommitted copy of oracle/: the tests of this module that then fail
     "max_by keeps the first of the 20 restarts": "test_feature_chunk_against_the_reference[diploid_1_column, diploid_4_columns, "
                                                  "diploid_6_columns, diploid_nine_columns, three_copies, four_copies, one_column_four_copies, zero_rows]",
@@ -60,12 +70,21 @@ SEEDED_FAULTS = {   # one-line changes to an uncommitted copy of oracle/: the te
     "<= for < in the stop rule": "test_feature_chunk_against_the_reference[stop_rule_exact_tie]",
     "no_new_variants dropped from expected_gains": "test_feature_chunk_against_the_reference[no_new_variants_decides]",
     "chi-square threshold on the wrong side": "test_planted_columns_are_dropped_by_their_own_filter, test_candidate_columns_against_the_oracle",
+    # at 64 reads and more (the other large cases pass with either; so does every case of CASES and every small chain):
+    "the size prior read at size - 1 for sizes of 64 and more": "test_feature_chunk_against_the_reference[light_127_reads_2_columns, "
+                                                                "k2_127_reads_8_columns, k2_120_reads_70_and_50, tab2_128_reads_3_columns, tab2_255_reads, "
+                                                                "tab2_256_reads], test_one_chain_against_the_oracle[k2_120_reads_70_and_50]",
+    "an accepted move of a read of index 64 or more leaves the column counts as they were":
+        "test_feature_chunk_against_the_reference[every large case but light_64_reads_1_column and k2_64_reads_3_columns, which have no such read], "
+        "test_one_chain_against_the_oracle[k2_120_reads_70_and_50, light_81_reads_zero_rows, tab3_66_reads]",
     "POS_FRAC compared with <=": "none, and none can: num_pos / (num_pos + num_neg + 1e-7) equals the double 0.70 only if 0.7e-7 / "
                                  "(num_pos + num_neg) is below half an ulp of 0.7 (5.6e-17), i.e. beyond 1e9 reads in one cluster; at every "
                                  "reachable count `<` and `<=` agree (7 positives of 10 give 0.69999999, not informative either way)",
 }
 DECISION_BOUND = 1e-10
 NAMES = list(K.CASES)
+LARGE_NAMES = list(K.LARGE_CASES)   # 64 to 256 reads: the project's exp / log only
+ALL_CASES = dict(K.CASES, **K.LARGE_CASES)
 GOLDEN, PILEUPS, pileup = K.GOLDEN, K.PILEUPS, K.pileup
 
 
@@ -75,7 +94,7 @@ def params_of(case):
 
 def _reference(arg):
     name, backend = arg
-    c = K.CASES[name]()
+    c = ALL_CASES[name]()
     gains = R.Gains.from_params(params_of(c))
     B = R.ProjectMath() if backend == "project" else R.LibmMath
     return R.cluster_features(c["x"].tolist(), c["vt"].tolist(), c["copy_num"], c["coverage"], c["local_coverage"], gains, c["chunk_id"], B)
@@ -86,9 +105,11 @@ def references():
     """{(case, back end): clustering_reference.cluster_features' result}, all at once in worker processes"""
     import multiprocessing as mp
     O.lib()
-    jobs = [(n, b) for b in ("project", "libm") for n in NAMES]
-    cost = {n: K.CASES[n]()["x"].size * K.CASES[n]()["copy_num"] for n in NAMES}
-    jobs.sort(key=lambda j: -cost[j[0]])   # the longest first
+    jobs = [(n, b) for b in ("project", "libm") for n in NAMES] + [(n, "project") for n in LARGE_NAMES]
+    shape = {n: (ALL_CASES[n]()["x"].shape, ALL_CASES[n]()["copy_num"]) for n in ALL_CASES}
+    # proposals (2000 n per restart and tried k) times the work of one (the columns of k clusters, a fixed part): the longest first
+    cost = {n: rows * sum(4 + k * dim for k in range(2, max(cp, 2) + 1)) for n, ((rows, dim), cp) in shape.items()}
+    jobs.sort(key=lambda j: -cost[j[0]])
     with mp.get_context("fork").Pool(min(8, os.cpu_count() or 1)) as pool:
         return dict(zip(jobs, pool.map(_reference, jobs, chunksize=1)))
 
@@ -182,14 +203,17 @@ def test_kmeans_against_the_oracle(oracle, name):
         assert "panic" in paths   # two distinct rows, k = 3: every weight is zero
 
 
-@pytest.mark.parametrize("name", SMALL)
+LARGE_CHAINS = ["k2_120_reads_70_and_50", "light_81_reads_zero_rows", "tab3_66_reads"]   # one start each per k: 3 to 5 s a chain
+
+
+@pytest.mark.parametrize("name", SMALL + LARGE_CHAINS)
 def test_one_chain_against_the_oracle(oracle, name):
-    c = K.CASES[name]()
+    c = ALL_CASES[name]()
     x = c["x"]
     n, dim = x.shape
     B = R.ProjectMath()
     for k in range(2, min(c["copy_num"], 1 + 2 * dim) + 1):
-        for seed in range(3):
+        for seed in range(1 if name in LARGE_CHAINS else 3):
             mine, theirs = both_rngs(seed + 17 * k)
             start = [int(v) for v in np.random.default_rng(seed).integers(0, k, n)]
             asn = np.array(start, dtype=np.uintp)
@@ -269,10 +293,37 @@ def test_cases_reach_their_branches():
     assert panics == {"choose_weighted(..).unwrap()", "LKCount", "gen_bool"}   # (a NaN value reaches the weights first)
 
 
-@pytest.mark.parametrize("name", NAMES)
+def test_large_cases_reach_their_branches():
+    """every case of 64 reads and more: the predicate it is listed with holds on the reference's own log, and between them the
+    cases run every (kernel, chain) of the dispatch they were drawn for, as clustering_cases.device_path restates it"""
+    refs = references()
+    assert set(K.LARGE_REACHES) == set(LARGE_NAMES)
+    for name in LARGE_NAMES:
+        out = refs[(name, "project")]
+        assert out["status"] == 0, (name, out["panic"])
+        print(name, K.device_path(K.LARGE_CASES[name]()), out["log"].chain, [(t["k"], t["accepted"], t["sizes"]) for t in out["log"].tried])
+        assert K.LARGE_REACHES[name](out["log"]), name
+    logs = [refs[(name, "project")]["log"] for name in LARGE_NAMES]
+    for what, reached in K.LARGE_REACHED_SOMEWHERE.items():
+        assert any(reached(g) for g in logs), what
+    assert {K.device_path(K.LARGE_CASES[n]()) for n in LARGE_NAMES} == K.LARGE_PATHS
+    assert {K.device_path(K.CASES[n]())[1] for n in NAMES if K.CASES[n]()["x"].size and K.CASES[n]()["copy_num"] >= 2} == {
+        "mcmc_chain_k2<1, 1>", "mcmc_chain_k2<2, 1>", "mcmc_chain_k2<3, 1>", "mcmc_chain_k2<4, 1>", "mcmc_chain_k2<8, 1>",
+        "mcmc_chain_tab<2> SMALL", "mcmc_chain_tab<3> SMALL", "mcmc_chain_tab<4> SMALL"}
+    shapes = {(c["copy_num"], c["x"].shape[0], c["x"].shape[1]) for c in (K.LARGE_CASES[n]() for n in LARGE_NAMES)}
+    assert {(n, d) for cp, n, d in shapes if cp == 2} >= {(64, 1), (65, 2), (127, 2), (64, 3), (127, 8), (120, 3), (128, 3), (70, 9),
+                                                          (255, 1), (256, 1)}
+    assert {d for cp, n, d in shapes if cp == 2 and 64 <= n <= 127} >= {1, 2, 3, 4, 6, 8}
+    assert {(cp, n) for cp, n, d in shapes if cp > 2} == {(3, 66), (4, 68)}
+    for name in LARGE_NAMES:   # the haploid coverage is that of a pile-up of this many reads: within a fifth of n / copy_num
+        c = K.LARGE_CASES[name]()
+        assert abs(c["coverage"] * c["copy_num"] / len(c["x"]) - 1.0) <= 0.2, name
+
+
+@pytest.mark.parametrize("name", NAMES + LARGE_NAMES)
 def test_feature_chunk_against_the_reference(oracle, name):
     ref = references()[(name, "project")]
-    c = K.CASES[name]()
+    c = ALL_CASES[name]()
     rc, lab, post, res = oracle_features(c)
     if ref["status"] != 0:
         assert rc != 0 and res["status"] == -6, ref["panic"]
@@ -338,9 +389,11 @@ def test_committed_reference_outputs_are_the_live_ones():
     """tests/golden/clustering_reference.json (read by tests/test_gpu_clustering_reference.py) against the reference run here"""
     gold = json.load(open(GOLDEN))
     refs = references()
-    assert sorted(gold["cases"]) == sorted(NAMES)
+    assert sorted(gold["cases"]) == sorted(NAMES) and sorted(gold["large_cases"]) == sorted(LARGE_NAMES)
     for name in NAMES:
         assert gold["cases"][name] == as_fixture(refs[(name, "project")]), name
+    for name in LARGE_NAMES:
+        assert gold["large_cases"][name] == as_fixture(refs[(name, "project")]), name
     assert sorted(gold["pileups"]) == sorted(PILEUPS)
     for config in PILEUPS:
         assert gold["pileups"][config] == as_pileup_fixture(pileup_reference(config)), config
