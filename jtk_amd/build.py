@@ -13,7 +13,8 @@ SYNTH_OUT = os.path.join(OUT_DIR, "libjtk_synth.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 EXPORTS_MAP = os.path.join(CSRC, "exports.map")  # only jtk_lc_* leaves the library
 
-SOURCES = ["phmm_kernels.hip", "phmm_sweep.hip", "phmm_pair.hip", "phmm_wide.hip", "polish_kernels.hip", "filter_kernels.hip", "mcmc_kernels.hip", "session.hip", "gains.hip", "correction.hip",
+SOURCES = ["phmm_kernels.hip", "phmm_sweep.hip", "phmm_pair.hip", "phmm_wide.hip", "polish_kernels.hip", "filter_kernels.hip", "mcmc_kernels.hip", "session.hip",
+           "session_split.hip", "session_stages.hip", "session_refit.hip", "session_features.hip", "gains.hip", "correction.hip",
            "io_kernels.hip", "align_kernels.hip", "host_api.cpp"]
 SYNTH_SOURCES = ["synth.cpp"]
 # -ffp-contract=off: device f64 arithmetic must round exactly like the reference (no implicit fma);
@@ -86,7 +87,8 @@ def build_experiment(name, extra_flags):
 
 
 PROFILED_SOURCES = ["phmm_kernels.hip", "phmm_sweep.hip", "phmm_pair.hip", "phmm_wide.hip", "polish_kernels.hip", "filter_kernels.hip", "mcmc_kernels.hip",
-                    "session.hip", "io_kernels.hip", "device_common.h", "finalize_common.h"]
+                    "session.hip", "session_split.hip", "session_stages.hip", "session_refit.hip", "session_features.hip", "io_kernels.hip",
+                    "device_common.h", "host_common.h", "session_internal.h", "finalize_common.h"]
 
 
 def source_sha16():

@@ -22,8 +22,7 @@
 #include <vector>
 
 #include "device_common.h"
-
-extern "C" void jtk_internal_set_error(const char *msg);
+#include "host_common.h"
 
 #define ALIGN_MAX_LEN 32000u  // tl + rl stays below the 16-bit infinity
 #define ALIGN_INF 0xFFFFu
@@ -246,26 +245,6 @@ __global__ __launch_bounds__(256) void align_pack_kernel(const uint8_t *ops_all,
     for (uint64_t q = threadIdx.x; q < len; q += 256) ops_out[a + q] = src[q];
 }
 
-int afail(int rc, const std::string &msg) {
-    jtk_internal_set_error(msg.c_str());
-    return rc;
-}
-
-#define ALIGN_HIP(expr)                                                                                  \
-    do {                                                                                                 \
-        hipError_t e_ = (expr);                                                                          \
-        if (e_ != hipSuccess)                                                                            \
-            return afail(e_ == hipErrorOutOfMemory ? JTK_ERR_ALLOC : JTK_ERR_NO_DEVICE,                  \
-                         std::string(#expr) + ": " + hipGetErrorString(e_));                             \
-    } while (0)
-
-struct DevMem {
-    void *p = nullptr;
-    ~DevMem() {
-        if (p) (void)hipFree(p);
-    }
-};
-
 inline int groups_of(int W) { return ((W + 1) / 2 + 7) / 8; }
 inline size_t lds_bytes_of(int G) { return (size_t)(2 * (8 * G + 16) + 8 * G) * 2 + 16; }
 
@@ -296,10 +275,10 @@ template <int THREADS, int MODE, int FREE>
 int launch_align(size_t n, size_t lds, const AlignPair *d_pairs, const uint8_t *d_bases, uint4 *d_scratch, uint8_t *d_ops,
                  uint32_t *d_dist, uint32_t *d_nops, uint32_t *d_bounds) {
     if (lds > 48 * 1024)
-        ALIGN_HIP(hipFuncSetAttribute((const void *)align_kernel<THREADS, MODE, FREE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        JTK_HIP_TRY(hipFuncSetAttribute((const void *)align_kernel<THREADS, MODE, FREE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL((align_kernel<THREADS, MODE, FREE>), dim3((unsigned)n), dim3(THREADS), lds, 0, d_pairs, d_bases, d_scratch, d_ops,
                        d_dist, d_nops, d_bounds);
-    ALIGN_HIP(hipGetLastError());
+    JTK_HIP_TRY(hipGetLastError());
     return 0;
 }
 
@@ -320,28 +299,24 @@ int launch_align_any(int mode, int free_seq, size_t n, size_t lds, const AlignPa
 int align_impl(size_t n_chunks, const jtk_lc_chunk_t *chunks, const uint8_t *tmpl_bases, const uint8_t *read_bases,
                const uint64_t *read_off, int mode, int free_seq, uint32_t max_dist, uint8_t *ops_out, uint64_t *ops_out_off,
                uint64_t ops_cap, uint32_t *dist_out, uint32_t *start_out, uint32_t *end_out, int32_t *read_status, int device) {
-    jtk_internal_set_error("");
-    if (n_chunks && (!chunks || !tmpl_bases || !read_bases || !read_off)) return afail(JTK_ERR_INVALID_ARG, "null input");
-    if (!ops_out || !ops_out_off || !dist_out || !read_status) return afail(JTK_ERR_INVALID_ARG, "null output");
-    if (mode != AM_GLOBAL && (!start_out || !end_out)) return afail(JTK_ERR_INVALID_ARG, "null output");
+    g_last_error.clear();
+    if (n_chunks && (!chunks || !tmpl_bases || !read_bases || !read_off)) return jtk_fail(JTK_ERR_INVALID_ARG, "null input");
+    if (!ops_out || !ops_out_off || !dist_out || !read_status) return jtk_fail(JTK_ERR_INVALID_ARG, "null output");
+    if (mode != AM_GLOBAL && (!start_out || !end_out)) return jtk_fail(JTK_ERR_INVALID_ARG, "null output");
     uint64_t n_reads = 0;
-    for (size_t c = 0; c < n_chunks; c++) {
-        if (chunks[c].read_first != n_reads) return afail(JTK_ERR_INVALID_ARG, "chunks must list their reads contiguously in order");
-        n_reads += chunks[c].n_reads;
-    }
+    if (int bad = check_contiguous(chunks, n_chunks, &n_reads)) return bad;
     for (uint64_t r = 0; r < n_reads; r++)
-        if (read_off[r + 1] < read_off[r]) return afail(JTK_ERR_INVALID_ARG, "read_off is not ascending");
+        if (read_off[r + 1] < read_off[r]) return jtk_fail(JTK_ERR_INVALID_ARG, "read_off is not ascending");
     auto acgt = [](const uint8_t *b, uint64_t n) {
         for (uint64_t q = 0; q < n; q++)
             if (b[q] != 'A' && b[q] != 'C' && b[q] != 'G' && b[q] != 'T') return false;
         return true;
     };
     for (size_t c = 0; c < n_chunks; c++)
-        if (!acgt(tmpl_bases + chunks[c].tmpl_off, chunks[c].tmpl_len)) return afail(JTK_ERR_INVALID_ARG, "non-ACGT base in a template");
+        if (!acgt(tmpl_bases + chunks[c].tmpl_off, chunks[c].tmpl_len)) return jtk_fail(JTK_ERR_INVALID_ARG, "non-ACGT base in a template");
     if (n_reads && !acgt(read_bases + read_off[0], read_off[n_reads] - read_off[0]))
-        return afail(JTK_ERR_INVALID_ARG, "non-ACGT base in a read");
-    if (!jtk_lc_device_ok(device)) return afail(JTK_ERR_NO_DEVICE, "no gfx950 device (jtk_lc has no CPU fallback)");
-    ALIGN_HIP(hipSetDevice(device));
+        return jtk_fail(JTK_ERR_INVALID_ARG, "non-ACGT base in a read");
+    if (int bad = jtk_require_device(device)) return bad;
 
     // ---- padded base buffer and per-read work items
     struct Item {
@@ -417,20 +392,20 @@ int align_impl(size_t n_chunks, const jtk_lc_chunk_t *chunks, const uint8_t *tmp
         }
     }
 
-    DevMem d_bases, d_ops, d_dist, d_nops, d_pairs, d_scratch, d_bounds;
-    ALIGN_HIP(hipMalloc(&d_bases.p, h_bases.size()));
-    ALIGN_HIP(hipMemcpy(d_bases.p, h_bases.data(), h_bases.size(), hipMemcpyHostToDevice));
-    ALIGN_HIP(hipMalloc(&d_ops.p, slot + 16));
-    ALIGN_HIP(hipMalloc(&d_dist.p, (n_reads + 1) * 4));
-    ALIGN_HIP(hipMalloc(&d_nops.p, (n_reads + 1) * 4));
-    ALIGN_HIP(hipMemset(d_nops.p, 0, (n_reads + 1) * 4));
-    ALIGN_HIP(hipMemset(d_dist.p, 0xFF, (n_reads + 1) * 4));
+    DevBuf d_bases, d_ops, d_dist, d_nops, d_pairs, d_scratch, d_bounds;
+    JTK_HIP_TRY(d_bases.alloc(h_bases.size()));
+    JTK_HIP_TRY(hipMemcpy(d_bases.p, h_bases.data(), h_bases.size(), hipMemcpyHostToDevice));
+    JTK_HIP_TRY(d_ops.alloc(slot + 16));
+    JTK_HIP_TRY(d_dist.alloc((n_reads + 1) * 4));
+    JTK_HIP_TRY(d_nops.alloc((n_reads + 1) * 4));
+    JTK_HIP_TRY(hipMemset(d_nops.p, 0, (n_reads + 1) * 4));
+    JTK_HIP_TRY(hipMemset(d_dist.p, 0xFF, (n_reads + 1) * 4));
     if (mode != AM_GLOBAL) {
-        ALIGN_HIP(hipMalloc(&d_bounds.p, (n_reads + 1) * 8));
-        ALIGN_HIP(hipMemset(d_bounds.p, 0, (n_reads + 1) * 8));
+        JTK_HIP_TRY(d_bounds.alloc((n_reads + 1) * 8));
+        JTK_HIP_TRY(hipMemset(d_bounds.p, 0, (n_reads + 1) * 8));
         for (uint32_t r : settled)  // with the free side empty the slot of tl + rl bytes is the whole sequence's
             if (items[r].t)
-                ALIGN_HIP(hipMemset((uint8_t *)d_ops.p + items[r].ops_off, free_seq == AF_TEMPLATE ? JTK_OP_INS : JTK_OP_DEL, items[r].t));
+                JTK_HIP_TRY(hipMemset((uint8_t *)d_ops.p + items[r].ops_off, free_seq == AF_TEMPLATE ? JTK_OP_INS : JTK_OP_DEL, items[r].t));
     }
 
     // ---- rounds: every pending pair with its current t; those that come back above it double t
@@ -458,9 +433,7 @@ int align_impl(size_t n_chunks, const jtk_lc_chunk_t *chunks, const uint8_t *tmp
         }
         std::stable_sort(prs.begin(), prs.end(), [](const AlignPair &a, const AlignPair &b) { return a.khi - a.klo > b.khi - b.klo; });
         if (prs.size() > pairs_have) {
-            if (d_pairs.p) (void)hipFree(d_pairs.p);
-            d_pairs.p = nullptr;
-            ALIGN_HIP(hipMalloc(&d_pairs.p, prs.size() * sizeof(AlignPair)));
+            JTK_HIP_TRY(d_pairs.alloc(prs.size() * sizeof(AlignPair)));
             pairs_have = prs.size();
         }
         size_t a = 0;
@@ -479,13 +452,11 @@ int align_impl(size_t n_chunks, const jtk_lc_chunk_t *chunks, const uint8_t *tmp
                 b++;
             }
             if (used > scratch_have) {
-                if (d_scratch.p) (void)hipFree(d_scratch.p);
-                d_scratch.p = nullptr;
                 scratch_have = 0;
-                ALIGN_HIP(hipMalloc(&d_scratch.p, used * 16));
+                JTK_HIP_TRY(d_scratch.alloc(used * 16));
                 scratch_have = used;
             }
-            ALIGN_HIP(hipMemcpy((AlignPair *)d_pairs.p + a, prs.data() + a, (b - a) * sizeof(AlignPair), hipMemcpyHostToDevice));
+            JTK_HIP_TRY(hipMemcpy((AlignPair *)d_pairs.p + a, prs.data() + a, (b - a) * sizeof(AlignPair), hipMemcpyHostToDevice));
             const size_t lds = lds_bytes_of(G0);  // the launch's widest band comes first
             int rc;
             if (threads == 64)
@@ -498,14 +469,14 @@ int align_impl(size_t n_chunks, const jtk_lc_chunk_t *chunks, const uint8_t *tmp
                 rc = launch_align_any<1024>(mode, free_seq, b - a, lds, (AlignPair *)d_pairs.p + a, (uint8_t *)d_bases.p, (uint4 *)d_scratch.p,
                                             (uint8_t *)d_ops.p, (uint32_t *)d_dist.p, (uint32_t *)d_nops.p, (uint32_t *)d_bounds.p);
             if (rc) return rc;
-            ALIGN_HIP(hipDeviceSynchronize());  // the next launch reuses the scratch
+            JTK_HIP_TRY(hipDeviceSynchronize());  // the next launch reuses the scratch
             a = b;
         }
-        ALIGN_HIP(hipMemcpy(h_dist.data(), d_dist.p, n_reads * 4, hipMemcpyDeviceToHost));
+        JTK_HIP_TRY(hipMemcpy(h_dist.data(), d_dist.p, n_reads * 4, hipMemcpyDeviceToHost));
         std::vector<uint32_t> again;
         for (uint32_t r : pending) {
             Item &it = items[r];
-            if (h_dist[r] == ALIGN_WALK_LOST) return afail(JTK_ERR_INTERNAL, "align: the walk left the band");
+            if (h_dist[r] == ALIGN_WALK_LOST) return jtk_fail(JTK_ERR_INTERNAL, "align: the walk left the band");
             if (h_dist[r] != 0xFFFFFFFFu) continue;
             if (it.t >= it.bound) {
                 read_status[r] = JTK_ERR_UNSUPPORTED;  // farther than max_dist
@@ -518,12 +489,12 @@ int align_impl(size_t n_chunks, const jtk_lc_chunk_t *chunks, const uint8_t *tmp
     }
 
     // ---- pack the ops of every read behind each other and fetch them with one copy
-    ALIGN_HIP(hipMemcpy(n_ops.data(), d_nops.p, n_reads * 4, hipMemcpyDeviceToHost));
-    ALIGN_HIP(hipMemcpy(h_dist.data(), d_dist.p, n_reads * 4, hipMemcpyDeviceToHost));
+    JTK_HIP_TRY(hipMemcpy(n_ops.data(), d_nops.p, n_reads * 4, hipMemcpyDeviceToHost));
+    JTK_HIP_TRY(hipMemcpy(h_dist.data(), d_dist.p, n_reads * 4, hipMemcpyDeviceToHost));
     for (uint32_t r : settled) n_ops[r] = h_dist[r] = items[r].t;
     if (mode != AM_GLOBAL) {
         std::vector<uint32_t> h_bounds(2 * n_reads + 2);
-        ALIGN_HIP(hipMemcpy(h_bounds.data(), d_bounds.p, n_reads * 8, hipMemcpyDeviceToHost));
+        JTK_HIP_TRY(hipMemcpy(h_bounds.data(), d_bounds.p, n_reads * 8, hipMemcpyDeviceToHost));
         for (uint64_t r = 0; r < n_reads; r++)
             if (!read_status[r]) {
                 start_out[r] = h_bounds[2 * r];
@@ -543,25 +514,25 @@ int align_impl(size_t n_chunks, const jtk_lc_chunk_t *chunks, const uint8_t *tmp
         total += n_ops[r];
     }
     ops_out_off[n_reads] = total;
-    if (total > ops_cap) return afail(JTK_ERR_INVALID_ARG, "ops_cap is smaller than the ops of the batch");
+    if (total > ops_cap) return jtk_fail(JTK_ERR_INVALID_ARG, "ops_cap is smaller than the ops of the batch");
     if (total) {
-        DevMem d_off, d_end, d_out;
-        ALIGN_HIP(hipMalloc(&d_off.p, (n_reads + 1) * 8));
-        ALIGN_HIP(hipMalloc(&d_end.p, n_reads * 8));
-        ALIGN_HIP(hipMalloc(&d_out.p, total));
-        ALIGN_HIP(hipMemcpy(d_off.p, ops_out_off, (n_reads + 1) * 8, hipMemcpyHostToDevice));
-        ALIGN_HIP(hipMemcpy(d_end.p, slot_end.data(), n_reads * 8, hipMemcpyHostToDevice));
+        DevBuf d_off, d_end, d_out;
+        JTK_HIP_TRY(d_off.alloc((n_reads + 1) * 8));
+        JTK_HIP_TRY(d_end.alloc(n_reads * 8));
+        JTK_HIP_TRY(d_out.alloc(total));
+        JTK_HIP_TRY(hipMemcpy(d_off.p, ops_out_off, (n_reads + 1) * 8, hipMemcpyHostToDevice));
+        JTK_HIP_TRY(hipMemcpy(d_end.p, slot_end.data(), n_reads * 8, hipMemcpyHostToDevice));
         hipLaunchKernelGGL(align_pack_kernel, dim3((unsigned)n_reads), dim3(256), 0, 0, (const uint8_t *)d_ops.p, (const uint64_t *)d_end.p,
                            (const uint64_t *)d_off.p, (uint32_t)n_reads, (uint8_t *)d_out.p);
-        ALIGN_HIP(hipGetLastError());
-        ALIGN_HIP(hipMemcpy(ops_out, d_out.p, total, hipMemcpyDeviceToHost));
+        JTK_HIP_TRY(hipGetLastError());
+        JTK_HIP_TRY(hipMemcpy(ops_out, d_out.p, total, hipMemcpyDeviceToHost));
     }
     if (rc)
-        jtk_internal_set_error(mode == AM_GLOBAL
-                                   ? "a read lies farther from its template than max_dist (or is longer than 32,000 bases)"
-                                   : "a pair lies farther apart than max_dist (or is longer than 32,000 bases, or its band at the "
-                                     "largest distance allowed is wider than 32,768 diagonals: give max_dist)");
-    return rc;
+        return jtk_fail(rc, mode == AM_GLOBAL
+                                ? "a read lies farther from its template than max_dist (or is longer than 32,000 bases)"
+                                : "a pair lies farther apart than max_dist (or is longer than 32,000 bases, or its band at the "
+                                  "largest distance allowed is wider than 32,768 diagonals: give max_dist)");
+    return 0;
 }
 
 }  // namespace
@@ -577,10 +548,10 @@ extern "C" int jtk_lc_align_reads_mode(size_t n_chunks, const jtk_lc_chunk_t *ch
                                        const uint8_t *read_bases, const uint64_t *read_off, int mode, int free_seq,
                                        uint32_t max_dist, uint8_t *ops_out, uint64_t *ops_out_off, uint64_t ops_cap,
                                        uint32_t *dist_out, uint32_t *start_out, uint32_t *end_out, int32_t *read_status, int device) {
-    if (mode != JTK_ALIGN_GLOBAL && mode != JTK_ALIGN_INFIX && mode != JTK_ALIGN_PREFIX) return afail(JTK_ERR_INVALID_ARG, "unknown alignment mode");
+    if (mode != JTK_ALIGN_GLOBAL && mode != JTK_ALIGN_INFIX && mode != JTK_ALIGN_PREFIX) return jtk_fail(JTK_ERR_INVALID_ARG, "unknown alignment mode");
     if (mode != JTK_ALIGN_GLOBAL && free_seq != JTK_ALIGN_FREE_TEMPLATE && free_seq != JTK_ALIGN_FREE_READ)
-        return afail(JTK_ERR_INVALID_ARG, "unknown free sequence");
-    if (!start_out || !end_out) return afail(JTK_ERR_INVALID_ARG, "null output");
+        return jtk_fail(JTK_ERR_INVALID_ARG, "unknown free sequence");
+    if (!start_out || !end_out) return jtk_fail(JTK_ERR_INVALID_ARG, "null output");
     const int rc = align_impl(n_chunks, chunks, tmpl_bases, read_bases, read_off, mode, free_seq, max_dist, ops_out, ops_out_off, ops_cap,
                               dist_out, start_out, end_out, read_status, device);
     if (mode == JTK_ALIGN_GLOBAL && (rc == 0 || rc == JTK_ERR_CHUNK_FAILED))  // everything is consumed: [0, template length)

@@ -25,10 +25,9 @@
 #include <vector>
 
 #include "device_common.h"
+#include "host_common.h"
 #include "jtk_lc_debug.h"
 #include "jtk_eigen.h"
-
-extern "C" void jtk_internal_set_error(const char *msg);
 
 namespace {
 
@@ -382,32 +381,6 @@ double adjusted_rand_index(const std::vector<size_t> &label, const std::vector<s
     return (double)numer / (double)denom;
 }
 
-int cc_fail(int status, const std::string &msg) {
-    jtk_internal_set_error(msg.c_str());
-    return status;
-}
-#define CC_HIP(expr)                                                                                         \
-    do {                                                                                                     \
-        hipError_t _e = (expr);                                                                              \
-        if (_e != hipSuccess)                                                                                \
-            return cc_fail(_e == hipErrorOutOfMemory ? JTK_ERR_ALLOC : JTK_ERR_NO_DEVICE,                    \
-                           std::string(#expr) + ": " + hipGetErrorString(_e));                               \
-    } while (0)
-
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    template <typename T>
-    int upload(const std::vector<T> &v, hipStream_t st) {
-        if (hipMalloc(&p, std::max<size_t>(v.size(), 1) * sizeof(T)) != hipSuccess) return JTK_ERR_ALLOC;
-        if (!v.empty() && hipMemcpyAsync(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, st) != hipSuccess)
-            return JTK_ERR_NO_DEVICE;
-        return 0;
-    }
-};
-
 thread_local bool g_keep_sims = false;
 thread_local std::vector<double> g_first_sims;
 thread_local std::vector<std::vector<double>> g_all_sims;  // one per corrected chunk, in job order, across batches
@@ -437,32 +410,23 @@ extern "C" int jtk_lc_correct_clustering(size_t n_reads, const uint64_t *read_id
                                          jtk_cc_chunk_t *chunks, size_t n_selected, const uint64_t *selection,
                                          double haploid_coverage, double min_gain, uint64_t *cluster_out, uint8_t *touched,
                                          int device) {
-    jtk_internal_set_error("");
+    g_last_error.clear();
     (void)read_id;  // the reference keys its write-back by read id; positions in the flattened arrays are the same thing
     if (!node_off || (n_reads && !nodes) || !chunks || !cluster_out || !touched || (n_selected && !selection))
-        return cc_fail(JTK_ERR_INVALID_ARG, "null argument");
+        return jtk_fail(JTK_ERR_INVALID_ARG, "null argument");
     const size_t n_nodes = (size_t)node_off[n_reads];
     for (size_t e = 0; e < n_nodes; e++) {
         cluster_out[e] = nodes[e].cluster;
         touched[e] = 0;
     }
-    if (n_chunks == 0) return cc_fail(JTK_ERR_CHUNK_FAILED, "no chunk (the reference unwraps the largest chunk id)");
-    {
-        int count = 0;
-        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device < 0 || device >= count)
-            return cc_fail(JTK_ERR_NO_DEVICE, "no usable HIP device (jtk_lc has no CPU fallback)");
-        CC_HIP(hipSetDevice(device));
-        hipDeviceProp_t prop;
-        CC_HIP(hipGetDeviceProperties(&prop, device));
-        if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
-            return cc_fail(JTK_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", kernels are built for gfx950 only");
-    }
+    if (n_chunks == 0) return jtk_fail(JTK_ERR_CHUNK_FAILED, "no chunk (the reference unwraps the largest chunk id)");
+    if (int rc = jtk_require_device(device)) return rc;
     bool panic = false;
     // dense chunk index; the reference indexes plain vectors by chunk id (:131-137)
     std::unordered_map<uint64_t, uint32_t> dense;
     uint64_t max_id = 0;
     for (size_t c = 0; c < n_chunks; c++) {
-        if (!dense.emplace(chunks[c].id, (uint32_t)c).second) return cc_fail(JTK_ERR_INVALID_ARG, "chunk ids repeat");
+        if (!dense.emplace(chunks[c].id, (uint32_t)c).second) return jtk_fail(JTK_ERR_INVALID_ARG, "chunk ids repeat");
         max_id = std::max(max_id, chunks[c].id);
     }
     std::vector<uint32_t> node_chunk(n_nodes);
@@ -479,7 +443,7 @@ extern "C" int jtk_lc_correct_clustering(size_t n_reads, const uint64_t *read_id
             coverage[it->second]++;
         }
     }
-    if (panic) return cc_fail(JTK_ERR_CHUNK_FAILED, "a node refers to a chunk id beyond the selected chunks");
+    if (panic) return jtk_fail(JTK_ERR_CHUNK_FAILED, "a node refers to a chunk id beyond the selected chunks");
     // ---- estimate_copy_number_of_cluster :131-181
     std::vector<uint64_t> cn_off(n_chunks + 1, 0);
     std::vector<uint32_t> cn_len(n_chunks);
@@ -572,7 +536,7 @@ extern "C" int jtk_lc_correct_clustering(size_t n_reads, const uint64_t *read_id
     std::unique_ptr<void, void (*)(void *)> st_guard(nullptr, [](void *s) { if (s) (void)hipStreamDestroy((hipStream_t)s); });
     DevBuf d_post, d_cn, d_cnoff, d_cnlen, d_panic;
     if (!jobs.empty()) {
-        CC_HIP(hipStreamCreate(&st));
+        JTK_HIP_TRY(hipStreamCreate(&st));
         st_guard.reset(st);
         size_t n_post = 0;
         for (size_t e = 0; e < n_nodes; e++) n_post = std::max<size_t>(n_post, nodes[e].post_off + nodes[e].post_len);
@@ -580,10 +544,10 @@ extern "C" int jtk_lc_correct_clustering(size_t n_reads, const uint64_t *read_id
         int rc;
         if ((rc = d_post.upload(post_v, st)) || (rc = d_cn.upload(cn, st)) || (rc = d_cnoff.upload(d_cn_off, st)) ||
             (rc = d_cnlen.upload(d_cn_len, st)))
-            return cc_fail(rc, "device upload failed");
-        CC_HIP(hipMalloc(&d_panic.p, sizeof(int)));
-        CC_HIP(hipMemsetAsync(d_panic.p, 0, sizeof(int), st));
-        CC_HIP(hipStreamSynchronize(st));  // post_v goes out of scope
+            return jtk_fail(rc, "device upload failed");
+        JTK_HIP_TRY(d_panic.alloc(sizeof(int)));
+        JTK_HIP_TRY(hipMemsetAsync(d_panic.p, 0, sizeof(int), st));
+        JTK_HIP_TRY(hipStreamSynchronize(st));  // post_v goes out of scope
     }
     g_first_sims.clear();
     g_all_sims.clear();
@@ -660,22 +624,22 @@ extern "C" int jtk_lc_correct_clustering(size_t n_reads, const uint64_t *read_id
         DevBuf d_jobs, d_members, d_arms, d_sims, d_scratch;
         int rc;
         if ((rc = d_jobs.upload(pjobs, st)) || (rc = d_members.upload(members, st)) || (rc = d_arms.upload(arms, st)))
-            return cc_fail(rc, "device upload failed");
-        CC_HIP(hipMalloc(&d_sims.p, std::max<size_t>(sims_total, 1) * sizeof(double)));
+            return jtk_fail(rc, "device upload failed");
+        JTK_HIP_TRY(d_sims.alloc(std::max<size_t>(sims_total, 1) * sizeof(double)));
         const uint32_t row_doubles = 2 * 3 * (max_arm + 1);
         uint64_t threads = std::min<uint64_t>(n_pairs, 256ull * 1024);
         threads = (threads + 255) / 256 * 256;
-        CC_HIP(hipMalloc(&d_scratch.p, threads * row_doubles * sizeof(double)));
+        JTK_HIP_TRY(d_scratch.alloc(threads * row_doubles * sizeof(double)));
         similarity_kernel<<<(uint32_t)(threads / 256), 256, 0, st>>>(
             n_pairs, (uint32_t)pjobs.size(), (const PairJob *)d_jobs.p, (const Member *)d_members.p, (const ArmEnt *)d_arms.p,
             (const double *)d_post.p, (const double *)d_cn.p, (const uint64_t *)d_cnoff.p, (const uint32_t *)d_cnlen.p,
             (double *)d_sims.p, (double *)d_scratch.p, row_doubles, (int *)d_panic.p);
         int dev_panic = 0;
-        CC_HIP(hipMemcpyAsync(sims.data(), d_sims.p, sims_total * sizeof(double), hipMemcpyDeviceToHost, st));
-        CC_HIP(hipMemcpyAsync(&dev_panic, d_panic.p, sizeof(int), hipMemcpyDeviceToHost, st));
-        CC_HIP(hipStreamSynchronize(st));
-        CC_HIP(hipGetLastError());
-        if (dev_panic) return cc_fail(JTK_ERR_CHUNK_FAILED, "sim(): posterior lengths differ from cluster_num, or a log-probability above 0");
+        JTK_HIP_TRY(hipMemcpyAsync(sims.data(), d_sims.p, sims_total * sizeof(double), hipMemcpyDeviceToHost, st));
+        JTK_HIP_TRY(hipMemcpyAsync(&dev_panic, d_panic.p, sizeof(int), hipMemcpyDeviceToHost, st));
+        JTK_HIP_TRY(hipStreamSynchronize(st));
+        JTK_HIP_TRY(hipGetLastError());
+        if (dev_panic) return jtk_fail(JTK_ERR_CHUNK_FAILED, "sim(): posterior lengths differ from cluster_num, or a log-probability above 0");
     }
     if (g_keep_sims && j0 == 0 && !pjobs.empty()) g_first_sims.assign(sims.begin(), sims.begin() + (size_t)pjobs[0].n * pjobs[0].n);
     if (g_keep_sims)
@@ -799,7 +763,7 @@ extern "C" int jtk_lc_correct_clustering(size_t n_reads, const uint64_t *read_id
     }
     }  // batches
     for (const Job &j : jobs)
-        if (j.panic) return cc_fail(JTK_ERR_CHUNK_FAILED, "chunk " + std::to_string(chunks[j.chunk].id) + ": the reference panics on this pile-up");
+        if (j.panic) return jtk_fail(JTK_ERR_CHUNK_FAILED, "chunk " + std::to_string(chunks[j.chunk].id) + ": the reference panics on this pile-up");
     // ---- get_protected_clusterings :108-129, supress_threshold :100-105, write-back :46-96
     std::vector<uint8_t> prot(n_chunks, 0);
     for (size_t c = 0; c < n_chunks; c++) {
@@ -813,7 +777,7 @@ extern "C" int jtk_lc_correct_clustering(size_t n_reads, const uint64_t *read_id
     const size_t pick = (size_t)std::ceil((double)aris.size() * 0.05);
     const double supress_cluster = pick < aris.size() ? aris[pick] : 1.0;
     for (const Job &j : jobs)
-        if (!(j.k <= chunks[j.chunk].copy_num)) return cc_fail(JTK_ERR_CHUNK_FAILED, "cluster_num above copy_num");  // assert! :55
+        if (!(j.k <= chunks[j.chunk].copy_num)) return jtk_fail(JTK_ERR_CHUNK_FAILED, "cluster_num above copy_num");  // assert! :55
     for (const Job &j : jobs) {
         jtk_cc_chunk_t &chunk = chunks[j.chunk];
         const bool supress = j.k == 1 || j.ari < supress_cluster;

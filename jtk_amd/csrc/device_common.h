@@ -19,7 +19,7 @@
 #define JTK_MASK_LENGTH 7        // pseudo_mcmc.rs:3
 #define JTK_MAX_HOMOP_LENGTH 2   // pseudo_mcmc.rs:4
 #define JTK_MAX_COPY 7           // one clustering() call sees copy_num < 8 (UPPER_COPY_NUM, mod.rs:85); larger chunks
-                                 // go through clustering_recursive's split, which session.hip drives
+                                 // go through clustering_recursive's split, which session_split.hip drives
 #define JTK_TRACE_MAX_PICKS 64    // jtk_lc_session_trace: picks recorded per chunk (ROUND * max(copy_num, 2) <= 21 of them happen)
 #define JTK_MAX_DIM (3 * JTK_MAX_COPY)  // ROUND * max(copy_num, 2) picked columns (pseudo_mcmc.rs:421,527,532)
 #define JTK_MAX_PILEUP 1023      // reads per pile-up in the chain kernel: 10-bit read indices in its proposal records and hop
@@ -107,7 +107,7 @@ void launch_band_prep(hipStream_t s, uint32_t n_reads, const ReadMeta *reads, co
 // takes tickets until one is past the launch's last item, so a launch advances the counter by exactly n_items + n_waves;
 // `ticket_base` (host, owned by the session) is the counter's value when the launch starts and is advanced by the launcher.
 // The forward scratch of the lane-ring pair-HMM kernels: stripes of (template + read + guard) x 1 KiB, one per RESIDENT wave.
-// The set is shared by every session of a device (session.hip: StripePool): however many batches are in flight, no more
+// The set is shared by every session of a device (session_internal.h: StripePool): however many batches are in flight, no more
 // waves than the device holds are ever inside a sweep, so a wave takes a free stripe when it starts and gives it back when it
 // ends (owner[]: 0 = free).  Release / acquire at agent scope on the hand-over: a stripe may move between XCDs, whose L2s are
 // not coherent with each other -- nothing depends on where a wave runs.
@@ -197,3 +197,31 @@ void launch_polish_round(hipStream_t s, uint32_t n_chunks, uint32_t n_reads, con
                          const double *table, double *total, Edit *edits, uint32_t *new_len, uint32_t max_tmpl,
                          uint32_t ignore_edge, int final_pass, uint32_t *n_active_out, uint32_t *n_active_host);
                          // (`total` holds the round's column totals: launch_sum_final)
+// filter_kernels.hip: the variant search of a clustering pass, and one chunk's pick once more with its trace arrays
+void launch_filter(hipStream_t s, uint32_t n_chunks, const ReadMeta *reads, const ChunkMeta *chunks,
+                   ChunkState *state, DevBufs bufs, const jtk_lc_params_t *params, const double *table,
+                   uint16_t *homop, const uint64_t *homop_off, double *aux, const uint64_t *aux_off, double *cand,
+                   uint32_t *list, uint8_t *sel, double *feat, uint32_t *vtype, uint32_t *pos, uint32_t max_tmpl,
+                   const HmmDev *hmm2, const int *rawG, const double *lk, int fused);
+void launch_pick_trace(hipStream_t s, uint32_t ci, const ReadMeta *reads, const ChunkMeta *chunks, ChunkState *state,
+                       const jtk_lc_params_t *params, const double *table, const uint16_t *homop, const uint64_t *homop_off,
+                       const double *cand, uint32_t *list, uint8_t *sel, double *feat, uint32_t *vtype, uint32_t *pos,
+                       const HmmDev *hmm2, const int *rawG, const double *lk, int fused, uint32_t *tr, uint32_t *tr_count);
+// mcmc_kernels.hip: the chain.  Its work area lives in LDS (launch_mcmc, sized per launch by mcmc_lds_bytes) or, for pile-ups
+// beyond that, in global memory (launch_mcmc_huge, mcmc_ws_bytes); launch_mcmc_trace runs one chunk again with its records
+size_t mcmc_trace_doubles(uint32_t n_reads);
+int launch_mcmc_trace(hipStream_t s, const ChunkMeta *chunks, ChunkState *state, const jtk_lc_params_t *params, const double *feat,
+                      const uint32_t *vtype, uint32_t *label, double *post, uint32_t post_stride, double *lg, const uint64_t *lg_off,
+                      uint32_t n, uint32_t d, uint32_t k, const uint32_t *order, unsigned char *ws, const uint64_t *ws_off,
+                      double *trace);
+size_t mcmc_lds_bytes(uint32_t lds_n, uint32_t lds_d, uint32_t lds_k);
+size_t mcmc_ws_bytes(uint32_t n, uint32_t d, uint32_t k);
+int launch_mcmc_huge(hipStream_t s, uint32_t n_chunks, const ChunkMeta *chunks, ChunkState *state, const jtk_lc_params_t *params,
+                     const double *feat, const uint32_t *vtype, const uint64_t *vt_off, uint32_t vt_stride_mode, uint32_t *label,
+                     double *post, uint32_t post_stride, double *lg, const uint64_t *lg_off, uint32_t max_n, uint32_t max_d,
+                     uint32_t max_k, const uint64_t *rng_resume, const uint32_t *order, unsigned char *ws, const uint64_t *ws_off);
+int launch_mcmc(hipStream_t s, uint32_t n_chunks, const ChunkMeta *chunks, ChunkState *state,
+                const jtk_lc_params_t *params, const double *feat, const uint32_t *vtype, const uint64_t *vt_off,
+                uint32_t vt_stride_mode, uint32_t *label, double *post, uint32_t post_stride, double *lg,
+                const uint64_t *lg_off, uint32_t lds_n, uint32_t lds_d, uint32_t lds_k, const uint64_t *rng_resume,
+                const uint32_t *order, uint32_t *split, hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join);

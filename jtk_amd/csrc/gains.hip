@@ -9,7 +9,7 @@
 //           Xoshiro256StarStar per simulation -- byte work, ~30 M draws in all;
 //   device  edit_ops_kernel: the bootstrap alignment (global unit-cost DP + traceback), one wavefront per
 //           (template, read) pair, the (len+1)^2 byte matrix in LDS;
-//   device  band_prep + phmm_kernel's forward sweep (jtk_internal_likelihoods in session.hip): log P(read | template)
+//   device  band_prep + phmm_kernel's forward sweep (jtk_internal_likelihoods in session_refit.hip): log P(read | template)
 //           inside the band the alignment gives -- the same kernel the clustering path runs;
 //   host    medians / percentiles of 100 numbers (likelihood_gains.rs:300-314).
 //
@@ -23,12 +23,7 @@
 #include <vector>
 
 #include "device_common.h"
-
-extern "C" int jtk_internal_likelihoods(const jtk_lc_params_t *params, size_t n_chunks, const jtk_lc_chunk_t *chunks,
-                                        const uint8_t *tmpl_bases, const uint8_t *read_bases, const uint64_t *read_off,
-                                        const uint8_t *ops, const uint64_t *ops_off, const uint8_t *strand,
-                                        uint32_t radius, int device, double *lk_out);
-extern "C" void jtk_internal_set_error(const char *msg);
+#include "host_common.h"
 
 namespace {
 
@@ -198,42 +193,26 @@ __global__ __launch_bounds__(64) void edit_ops_kernel(const PairMeta *pairs, uin
     }
 }
 
-#define HIP_OK(expr)                                                                          \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                               \
-            jtk_internal_set_error((std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
-            return e_ == hipErrorOutOfMemory ? JTK_ERR_ALLOC : JTK_ERR_NO_DEVICE;             \
-        }                                                                                     \
-    } while (0)
-
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-};
-
 // ops of every (template, read) pair, EDIT_OPS_STRIDE bytes apart
 int device_edit_ops(const std::vector<PairMeta> &pairs, const std::vector<uint8_t> &tmpl, const std::vector<uint8_t> &reads,
                     uint32_t max_len, std::vector<uint8_t> &ops, std::vector<uint32_t> &ops_len) {
     const uint32_t n = (uint32_t)pairs.size(), W = max_len + 1;
     DevBuf d_pairs, d_tmpl, d_reads, d_ops, d_len;
-    HIP_OK(hipMalloc(&d_pairs.p, pairs.size() * sizeof(PairMeta)));
-    HIP_OK(hipMalloc(&d_tmpl.p, tmpl.size()));
-    HIP_OK(hipMalloc(&d_reads.p, reads.size()));
-    HIP_OK(hipMalloc(&d_ops.p, (size_t)n * EDIT_OPS_STRIDE));
-    HIP_OK(hipMalloc(&d_len.p, (size_t)n * 4));
-    HIP_OK(hipMemcpy(d_pairs.p, pairs.data(), pairs.size() * sizeof(PairMeta), hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_tmpl.p, tmpl.data(), tmpl.size(), hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_reads.p, reads.data(), reads.size(), hipMemcpyHostToDevice));
+    JTK_HIP_TRY(d_pairs.alloc(pairs.size() * sizeof(PairMeta)));
+    JTK_HIP_TRY(d_tmpl.alloc(tmpl.size()));
+    JTK_HIP_TRY(d_reads.alloc(reads.size()));
+    JTK_HIP_TRY(d_ops.alloc((size_t)n * EDIT_OPS_STRIDE));
+    JTK_HIP_TRY(d_len.alloc((size_t)n * 4));
+    JTK_HIP_TRY(hipMemcpy(d_pairs.p, pairs.data(), pairs.size() * sizeof(PairMeta), hipMemcpyHostToDevice));
+    JTK_HIP_TRY(hipMemcpy(d_tmpl.p, tmpl.data(), tmpl.size(), hipMemcpyHostToDevice));
+    JTK_HIP_TRY(hipMemcpy(d_reads.p, reads.data(), reads.size(), hipMemcpyHostToDevice));
     edit_ops_kernel<<<n, 64, (size_t)W * W, 0>>>((const PairMeta *)d_pairs.p, n, (const uint8_t *)d_tmpl.p,
                                                  (const uint8_t *)d_reads.p, (uint8_t *)d_ops.p, (uint32_t *)d_len.p, W);
-    HIP_OK(hipGetLastError());
+    JTK_HIP_TRY(hipGetLastError());
     ops.resize((size_t)n * EDIT_OPS_STRIDE);
     ops_len.resize(n);
-    HIP_OK(hipMemcpy(ops.data(), d_ops.p, ops.size(), hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(ops_len.data(), d_len.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    JTK_HIP_TRY(hipMemcpy(ops.data(), d_ops.p, ops.size(), hipMemcpyDeviceToHost));
+    JTK_HIP_TRY(hipMemcpy(ops_len.data(), d_len.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -292,10 +271,7 @@ int gains_of(const jtk_lc_params_t &params, uint64_t seed, uint32_t seq_len, uin
     }
     uint32_t max_len = 0;
     for (const GainJob &job : jobs) max_len = std::max(max_len, job.max_len);
-    if (max_len > EDIT_MAX_LEN) {
-        jtk_internal_set_error("estimate_gain: simulated sequence longer than 250 bases");
-        return JTK_ERR_UNSUPPORTED;
-    }
+    if (max_len > EDIT_MAX_LEN) return jtk_fail(JTK_ERR_UNSUPPORTED, "estimate_gain: simulated sequence longer than 250 bases");
     // ---- the batch: per profile, chunk 2i = (tmpl_i, its 100 reads), chunk 2i+1 = (diff_i, the same reads)
     const size_t chunks_per_job = (size_t)2 * SAMPLE_NUM, per = (size_t)2 * SEQ_NUM, n_chunks = chunks_per_job * jobs.size(),
                  n_reads = n_chunks * per;
@@ -401,10 +377,8 @@ int minimum_gain_batch(const jtk_lc_params_t &params, uint64_t seed, size_t s0, 
             max_len = std::max<uint32_t>(max_len, (uint32_t)reads[i * seq_num + t].size());
         }
     }
-    if (max_len > EDIT_MAX_LEN) {
-        jtk_internal_set_error("estimate_minimum_gain: simulated sequence longer than 250 bases");
-        return JTK_ERR_UNSUPPORTED;
-    }
+    if (max_len > EDIT_MAX_LEN)
+        return jtk_fail(JTK_ERR_UNSUPPORTED, "estimate_minimum_gain: simulated sequence longer than 250 bases");
     const size_t n_chunks = 2 * ns, n_reads = n_chunks * seq_num;
     std::vector<jtk_lc_chunk_t> chunks(n_chunks);
     std::vector<uint8_t> tb, rb, strand(n_reads);
@@ -461,17 +435,12 @@ extern "C" {
 // (phmm_likelihood_correction.rs:118).  The reference's constants are (23908, 1000, 500, 100, 25).
 int jtk_lc_estimate_minimum_gain(const jtk_hmm_t *forward, const jtk_hmm_t *reverse, uint64_t seed, uint32_t sample_num,
                                  uint32_t seq_num, uint32_t len, uint32_t band, double *out, int device) {
-    jtk_internal_set_error("");
+    g_last_error.clear();
     if (!forward || !reverse || !out || sample_num < 3 || seq_num == 0 || len < 2 || len > 200 || band == 0 ||
-        band > JTK_MAX_RADIUS) {
-        jtk_internal_set_error("jtk_lc_estimate_minimum_gain: bad argument (sample_num >= 3, 2 <= len <= 200, 1 <= band <= 30)");
-        return JTK_ERR_INVALID_ARG;
-    }
-    if (!jtk_lc_device_ok(device)) {
-        jtk_internal_set_error("no gfx950 device (jtk_lc has no CPU fallback)");
-        return JTK_ERR_NO_DEVICE;
-    }
-    HIP_OK(hipSetDevice(device));
+        band > JTK_MAX_RADIUS)
+        return jtk_fail(JTK_ERR_INVALID_ARG,
+                        "jtk_lc_estimate_minimum_gain: bad argument (sample_num >= 3, 2 <= len <= 200, 1 <= band <= 30)");
+    if (int rc = jtk_require_device(device)) return rc;
     jtk_lc_params_t params;
     memset(&params, 0, sizeof params);
     params.forward = *forward;
@@ -494,17 +463,11 @@ int jtk_lc_estimate_minimum_gain(const jtk_hmm_t *forward, const jtk_hmm_t *reve
 
 int jtk_lc_estimate_gains(const jtk_hmm_t *forward, const jtk_hmm_t *reverse, uint64_t seed, uint32_t seq_len,
                           uint32_t band, uint32_t homop_len, jtk_gains_t *out, int device) {
-    jtk_internal_set_error("");
+    g_last_error.clear();
     if (!forward || !reverse || !out || homop_len == 0 || homop_len > JTK_GAINS_MAX_HOMOP || seq_len < 2 || band == 0 ||
-        band > JTK_MAX_RADIUS) {
-        jtk_internal_set_error("jtk_lc_estimate_gains: bad argument (1 <= homop_len <= 8, 1 <= band <= 30)");
-        return JTK_ERR_INVALID_ARG;
-    }
-    if (!jtk_lc_device_ok(device)) {
-        jtk_internal_set_error("no gfx950 device (jtk_lc has no CPU fallback)");
-        return JTK_ERR_NO_DEVICE;
-    }
-    HIP_OK(hipSetDevice(device));
+        band > JTK_MAX_RADIUS)
+        return jtk_fail(JTK_ERR_INVALID_ARG, "jtk_lc_estimate_gains: bad argument (1 <= homop_len <= 8, 1 <= band <= 30)");
+    if (int rc = jtk_require_device(device)) return rc;
     jtk_lc_params_t params;
     memset(&params, 0, sizeof params);
     params.forward = *forward;
