@@ -357,6 +357,47 @@ JTK_LC_API int jtk_lc_correct_clustering(size_t n_reads, const uint64_t *read_id
                               const uint64_t *selection, double haploid_coverage, double min_gain, uint64_t *cluster_out,
                               uint8_t *touched, int device);
 
+/* ---- the step in front of the correction: squish erroneous clusters ---------------------------------------------
+ * Replaces `SquishErroneousClusters::squish_erroneous_clusters` (haplotyper/src/squish_erroneous_clusters.rs:44-60), which
+ * both call sites of correct_clustering run first on the same DataSet (cli/src/pipeline.rs:174-175,
+ * haplotyper/src/dense_encoding.rs:62-64).  On the flattened data set of jtk_lc_correct_clustering:
+ *   - a node is biased when Node::is_biased(0.2) holds (definitions/src/lib.rs:703-709);
+ *   - every position pair i < j of biased nodes of a read adds 1 to the chunk pair (min id, max id) (:80-90; a chunk twice in
+ *     a read gives (u, u)); pairs with count_thr < count whose two chunks have 1 < cluster_num survive (:96-97);
+ *   - per surviving pair, the adjusted Rand index (misc.rs:22-46, in 64-bit integers and one division) of the reads' minimum
+ *     clusters on the two chunks, one observation per read that has biased nodes of both (:213-252);
+ *   - classify (:254-365): chunks are labelled stiff or not by 10 x (one sweep + 1,000 Metropolis proposals) on the pair
+ *     graph, Xoshiro256PlusPlus::seed_from_u64(3093240);
+ *   - class per chunk of chunks[] (:137-165): JTK_REL_STIFF if labelled stiff or 2 < copy_num, else JTK_REL_SUSPICIOUS if a
+ *     pair in which it is the SMALLER id names a stiff chunk, else JTK_REL_ISOLATED.
+ * Pair order.  The reference's pair list comes out of a HashMap under par_iter: its order, and with it classify's node
+ * numbering, sweep order and summation order, differs from run to run.  This build fixes one admissible order: pairs
+ * ascending by (u1, u2).  It is the order of the optional pair list below.
+ * Output: class_out[c] per chunk; chunks[c].cluster_num = 1 where suspicious; cluster_out[e] = Node.cluster after the call,
+ * touched[e] = 1 where the reference rewrites the node (a node of a suspicious chunk: cluster 0), whose posterior then is one
+ * entry, 0.0 (:55-58).  With all of pair_u1 / pair_u2 / pair_ari / pair_count given (any NULL skips all four) the surviving pairs
+ * are returned, pair_count being the number of observations (what classify weighs); JTK_ERR_INVALID_ARG with *n_pairs set
+ * when pair_cap is too small.
+ * Returns JTK_ERR_CHUNK_FAILED where the reference panics (a pair above count_thr whose retain indexes a chunk id that is not
+ * in chunks[], :97), and JTK_ERR_UNSUPPORTED when a read that enters the table of a surviving pair has a biased node of either
+ * chunk with cluster >= 64 (the table is 64 x 64 counters; the reference sizes its table by the largest label and has no such
+ * limit) or a read has more than 65535 nodes.  Nothing is written on failure. */
+typedef struct jtk_squish_config {
+    double ari_thr, match_score, mismatch_score;
+    uint64_t count_thr;
+} jtk_squish_config_t;
+/* SquishConfig::default(): 0.5, 4, -1, 10 (squish_erroneous_clusters.rs:29-38) */
+enum jtk_rel_class { JTK_REL_STIFF = 0, JTK_REL_ISOLATED = 1, JTK_REL_SUSPICIOUS = 2 };
+JTK_LC_API int jtk_lc_squish_clusters(size_t n_reads, const uint64_t *node_off, const jtk_cc_node_t *nodes, const double *posteriors,
+                           size_t n_chunks, jtk_cc_chunk_t *chunks, const jtk_squish_config_t *cfg, uint8_t *class_out,
+                           uint64_t *cluster_out, uint8_t *touched, uint64_t *pair_u1, uint64_t *pair_u2, double *pair_ari,
+                           uint64_t *pair_count, size_t pair_cap, size_t *n_pairs, int device);
+/* Host only, no GPU: classify (:254-365) on a pair list in the order GIVEN.  ids[] = the chunk ids in first-appearance order
+ * over the list (u1 then u2), stiff[i] = 1 where ids[i] is labelled stiff.  JTK_ERR_INVALID_ARG with *n_ids set when id_cap
+ * is too small. */
+JTK_LC_API int jtk_lc_squish_classify(size_t n_pairs, const uint64_t *u1, const uint64_t *u2, const double *ari, const uint64_t *count,
+                           const jtk_squish_config_t *cfg, uint64_t *ids, uint8_t *stiff, size_t id_cap, size_t *n_ids);
+
 /* Sort key of pileup_nodes (mod.rs:47-50): number of alignment columns that are not '|' in
  * Node::recover (definitions/src/lib.rs:773-813) for run-length cigar ops given per base. */
 JTK_LC_API int jtk_lc_pileup_sort_key(const uint8_t *tmpl, uint64_t tmpl_len, const uint8_t *read, uint64_t read_len,

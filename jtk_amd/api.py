@@ -192,6 +192,55 @@ def correct_clustering(read_id, node_off, nodes, posteriors, chunks, selection, 
     return cluster, touched
 
 
+def squish_clusters(node_off, nodes, posteriors, chunks, config=None, device=0):
+    """jtk_lc_squish_clusters: SquishErroneousClusters::squish_erroneous_clusters (squish_erroneous_clusters.rs:44-60) on the
+    flattened data set of correct_clustering.  `chunks` (ffi.CC_CHUNK_DT) is updated in place (cluster_num = 1 where
+    suspicious).  Returns dict(classes, cluster, touched, pair_u1, pair_u2, pair_ari, pair_count): the class per chunk
+    (ffi.REL_*), the cluster and the rewritten flag per node (a rewritten node's posterior is [0.0]) and the surviving chunk
+    pairs ascending by (u1, u2)."""
+    nodes = np.ascontiguousarray(nodes, dtype=ffi.CC_NODE_DT)
+    posteriors = np.ascontiguousarray(posteriors, dtype=np.float64)
+    node_off = np.ascontiguousarray(node_off, dtype=np.uint64)
+    if chunks.dtype != ffi.CC_CHUNK_DT or not chunks.flags.c_contiguous:
+        raise ValueError("chunks must be a contiguous array of ffi.CC_CHUNK_DT (it is updated in place)")
+    cfg = config if config is not None else ffi.SquishConfig()
+    # every surviving pair has count_thr < count, and the counts add up to at most sum n (n - 1) / 2 over the reads
+    lens = np.diff(node_off).astype(object)
+    total = int(sum(n * (n - 1) // 2 for n in lens))
+    k = int((chunks["cluster_num"] > 1).sum())
+    cap = min(total // (int(cfg.count_thr) + 1), k * (k + 1) // 2)
+    u1, u2 = np.zeros(cap + 1, dtype=np.uint64), np.zeros(cap + 1, dtype=np.uint64)
+    ari, count = np.zeros(cap + 1, dtype=np.float64), np.zeros(cap + 1, dtype=np.uint64)
+    classes = np.zeros(len(chunks) + 1, dtype=np.uint8)
+    cluster = np.zeros(len(nodes) + 1, dtype=np.uint64)
+    touched = np.zeros(len(nodes) + 1, dtype=np.uint8)
+    n_pairs = C.c_size_t(0)
+    check(ffi.lib().jtk_lc_squish_clusters(len(node_off) - 1, u64p(node_off), nodes.ctypes.data, f64p(posteriors), len(chunks),
+                                           chunks.ctypes.data, C.byref(cfg), u8p(classes), u64p(cluster), u8p(touched), u64p(u1),
+                                           u64p(u2), f64p(ari), u64p(count), cap, C.byref(n_pairs), device))
+    n = n_pairs.value
+    return dict(classes=classes[:len(chunks)], cluster=cluster[:len(nodes)], touched=touched[:len(nodes)], pair_u1=u1[:n],
+                pair_u2=u2[:n], pair_ari=ari[:n], pair_count=count[:n])
+
+
+def squish_classify(u1, u2, ari, count, config=None):
+    """jtk_lc_squish_classify (host only): classify (squish_erroneous_clusters.rs:254-365) on a pair list in the order given.
+    Returns (ids, stiff): the chunk ids in first-appearance order and their labels."""
+    u1 = np.ascontiguousarray(u1, dtype=np.uint64)
+    u2 = np.ascontiguousarray(u2, dtype=np.uint64)
+    ari = np.ascontiguousarray(ari, dtype=np.float64)
+    count = np.ascontiguousarray(count, dtype=np.uint64)
+    if not len(u1) == len(u2) == len(ari) == len(count):
+        raise ValueError("the four pair arrays differ in length")
+    cfg = config if config is not None else ffi.SquishConfig()
+    cap = 2 * len(u1)
+    ids, stiff = np.zeros(cap + 1, dtype=np.uint64), np.zeros(cap + 1, dtype=np.uint8)
+    n_ids = C.c_size_t(0)
+    check(ffi.lib().jtk_lc_squish_classify(len(u1), u64p(u1), u64p(u2), f64p(ari), u64p(count), C.byref(cfg), u64p(ids), u8p(stiff),
+                                           cap, C.byref(n_ids)))
+    return ids[:n_ids.value], stiff[:n_ids.value]
+
+
 def correct_clustering_with_sims(*args, **kw):
     """correct_clustering with the diagnostic switch of include/jtk_lc_debug.h on: returns (cluster, touched, sims), sims = the
     raw similarity matrix (before filter_similarity) of every corrected chunk, in selected_chunks order.  A test hook: the

@@ -375,6 +375,37 @@ def correct_clustering_selected(ds, selection, device=0, min_gain=None):
             e += 1
 
 
+def squish_erroneous_clusters(ds, config=None, device=0):
+    """SquishErroneousClusters::squish_erroneous_clusters (squish_erroneous_clusters.rs:44-60) on the parsed JSON object `ds`
+    (modified in place): jtk_lc_squish_clusters on the flattened nodes, then the write-back of :47-58 -- a suspicious chunk
+    gets cluster_num 1, its nodes cluster 0 and the posterior [0.0].  Returns the class per chunk id (ffi.REL_*)."""
+    n_nodes = sum(len(r["nodes"]) for r in ds["encoded_reads"])
+    nodes = np.zeros(n_nodes, dtype=ffi.CC_NODE_DT)
+    node_off = np.zeros(len(ds["encoded_reads"]) + 1, dtype=np.uint64)
+    post = []
+    e = 0
+    for r, read in enumerate(ds["encoded_reads"]):
+        for node in read["nodes"]:
+            nodes[e] = (node["chunk"], node["cluster"], 1 if node["is_forward"] else 0, len(node["posterior"]), len(post))
+            post.extend(float(x) for x in node["posterior"])
+            e += 1
+        node_off[r + 1] = e
+    chunks = np.zeros(len(ds["selected_chunks"]), dtype=ffi.CC_CHUNK_DT)
+    for i, c in enumerate(ds["selected_chunks"]):
+        chunks[i] = (c["id"], c["cluster_num"], c["copy_num"], c["score"])
+    out = api.squish_clusters(node_off, nodes, np.array(post, dtype=np.float64), chunks, config=config, device=device)
+    for i, c in enumerate(ds["selected_chunks"]):
+        c["cluster_num"] = int(chunks["cluster_num"][i])
+    e = 0
+    for read in ds["encoded_reads"]:
+        for node in read["nodes"]:
+            if out["touched"][e]:                                    # :55-58
+                node["cluster"] = int(out["cluster"][e])
+                node["posterior"] = [0.0]
+            e += 1
+    return {c["id"]: int(k) for c, k in zip(ds["selected_chunks"], out["classes"])}
+
+
 _COMPLEMENT = {"A": "T", "C": "G", "G": "C", "T": "A"}
 
 
@@ -446,8 +477,10 @@ def correct_clustering(ds, device=0, min_gain=None):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--stage", default="local_clustering", choices=("local_clustering", "correct_clustering", "realign"),
-                    help="which JTK stage to run on the file (jtk local_clustering / jtk correct_clustering); realign: "
+    ap.add_argument("--stage", default="local_clustering", choices=("local_clustering", "correct_clustering", "squish_erroneous_clusters", "corrected", "realign"),
+                    help="which JTK stage to run on the file (jtk local_clustering / jtk correct_clustering); "
+                         "squish_erroneous_clusters: the step JTK runs in front of the correction, with its default "
+                         "configuration; corrected: that step, then correct_clustering (cli/src/pipeline.rs:174-175); realign: "
                          "replace every node's cigar by its global alignment to the chunk sequence")
     ap.add_argument("input", help="DataSet JSON ('-' = stdin)")
     ap.add_argument("output", help="DataSet JSON ('-' = stdout)")
@@ -468,7 +501,12 @@ def main(argv=None):
     failed = [] if args.keep_going else None
     record = [] if args.verbose else None
     trace = [] if args.trace else None
-    if args.stage == "correct_clustering":
+    if args.stage in ("squish_erroneous_clusters", "corrected"):
+        validate(ds)
+        squish_erroneous_clusters(ds, device=args.device)
+        if args.stage == "corrected":
+            correct_clustering(ds, device=args.device)
+    elif args.stage == "correct_clustering":
         validate(ds)
         if args.chunks:
             correct_clustering_selected(ds, [int(x) for x in args.chunks.split(",")], device=args.device)

@@ -63,6 +63,16 @@ class Timing(C.Structure):
                 ("chain_lds_bytes", C.c_uint32 * 2)]
 
 
+class SquishConfig(C.Structure):
+    """jtk_squish_config_t; the defaults are SquishConfig::default() (squish_erroneous_clusters.rs:29-38)."""
+    _fields_ = [("ari_thr", C.c_double), ("match_score", C.c_double), ("mismatch_score", C.c_double), ("count_thr", C.c_uint64)]
+
+    def __init__(self, ari_thr=0.5, match_score=4.0, mismatch_score=-1.0, count_thr=10):
+        super().__init__(ari_thr, match_score, mismatch_score, count_thr)
+
+
+REL_STIFF, REL_ISOLATED, REL_SUSPICIOUS = 0, 1, 2   # enum jtk_rel_class
+
 CHUNK_DT = np.dtype([("chunk_id", "<u8"), ("copy_num", "<u4"), ("n_reads", "<u4"), ("tmpl_off", "<u8"),
                      ("tmpl_len", "<u8"), ("read_first", "<u8")])
 RESULT_DT = np.dtype([("score", "<f8"), ("cluster_num", "<u4"), ("status", "<i4"), ("polish_rounds", "<u4"),
@@ -77,7 +87,7 @@ CC_CHUNK_DT = np.dtype([("id", "<u8"), ("cluster_num", "<u4"), ("copy_num", "<u4
 # every symbol declared in include/jtk_lc.h (tests check the library exports them)
 EXPORTED_SYMBOLS = (
     "jtk_lc_cluster_chunks", "jtk_lc_cluster_chunks_multi", "jtk_lc_cluster_polished", "jtk_lc_polish_chunks", "jtk_lc_align_reads", "jtk_lc_align_reads_mode", "jtk_lc_modification_table",
-    "jtk_lc_cluster_features", "jtk_lc_estimate_gains", "jtk_lc_estimate_minimum_gain", "jtk_lc_fit_model", "jtk_lc_correct_clustering", "jtk_lc_trim_cache", "jtk_lc_pileup_sort_key", "jtk_lc_normalize_pileup", "jtk_lc_strerror",
+    "jtk_lc_cluster_features", "jtk_lc_estimate_gains", "jtk_lc_estimate_minimum_gain", "jtk_lc_fit_model", "jtk_lc_correct_clustering", "jtk_lc_squish_clusters", "jtk_lc_squish_classify", "jtk_lc_trim_cache", "jtk_lc_pileup_sort_key", "jtk_lc_normalize_pileup", "jtk_lc_strerror",
     "jtk_lc_last_error", "jtk_lc_version", "jtk_lc_device_ok", "jtk_lc_last_timing",
     "jtk_lc_session_create", "jtk_lc_session_run", "jtk_lc_session_fetch", "jtk_lc_session_destroy", "jtk_lc_session_trace",
 )
@@ -138,6 +148,9 @@ def lib():
     sig("jtk_lc_estimate_minimum_gain", i32, C.POINTER(Hmm), C.POINTER(Hmm), u64, u32, u32, u32, u32, PD, i32)
     sig("jtk_lc_fit_model", i32, PP, sz, vp, PU8, PU8, PU64, PU8, PU64, PU8, u32, C.POINTER(Hmm), C.POINTER(Hmm), i32)
     sig("jtk_lc_correct_clustering", i32, sz, PU64, PU64, vp, PD, sz, vp, sz, PU64, C.c_double, C.c_double, PU64, PU8, i32)
+    PSQ, PSZ = C.POINTER(SquishConfig), C.POINTER(sz)
+    sig("jtk_lc_squish_clusters", i32, sz, PU64, vp, PD, sz, vp, PSQ, PU8, PU64, PU8, PU64, PU64, PD, PU64, sz, PSZ, i32)
+    sig("jtk_lc_squish_classify", i32, sz, PU64, PU64, PD, PU64, PSQ, PU64, PU8, sz, PSZ)
     sig("jtk_lc_trim_cache", i32, i32)
     sig("jtk_lc_cluster_features", i32, PP, sz, vp, PD, PU32, PU32, PD, u32, vp, i32)
     sig("jtk_lc_pileup_sort_key", i32, PU8, u64, PU8, u64, PU8, u64, PU64)

@@ -43,6 +43,11 @@ pub struct JtkCcNode {
 pub struct JtkCcChunk {
     pub id: u64, pub cluster_num: u32, pub copy_num: u32, pub score: f64,
 }
+// SquishConfig (squish_erroneous_clusters.rs:6-11; default 0.5, 4, -1, 10)
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct JtkSquishConfig {
+    pub ari_thr: f64, pub match_score: f64, pub mismatch_score: f64, pub count_thr: u64,
+}
 
 extern "C" {
     pub fn jtk_lc_cluster_chunks(
@@ -94,6 +99,18 @@ extern "C" {
         n_reads: usize, read_id: *const u64, node_off: *const u64, nodes: *const JtkCcNode, posteriors: *const f64,
         n_chunks: usize, chunks: *mut JtkCcChunk, n_selected: usize, selection: *const u64,
         haploid_coverage: f64, min_gain: f64, cluster_out: *mut u64, touched: *mut u8, device: c_int) -> c_int;
+    // SquishErroneousClusters::squish_erroneous_clusters (squish_erroneous_clusters.rs:44-60), which pipeline.rs:174-175 and
+    // dense_encoding.rs:62-64 run in front of correct_clustering; class_out: 0 Stiff, 1 Isolated, 2 Suspicious.  The four pair
+    // arrays are optional (null skips them): the surviving chunk pairs ascending by (u1, u2)
+    pub fn jtk_lc_squish_clusters(
+        n_reads: usize, node_off: *const u64, nodes: *const JtkCcNode, posteriors: *const f64,
+        n_chunks: usize, chunks: *mut JtkCcChunk, cfg: *const JtkSquishConfig, class_out: *mut u8,
+        cluster_out: *mut u64, touched: *mut u8, pair_u1: *mut u64, pair_u2: *mut u64, pair_ari: *mut f64,
+        pair_count: *mut u64, pair_cap: usize, n_pairs: *mut usize, device: c_int) -> c_int;
+    // classify (:254-365) alone, on the host, on a pair list in the order given
+    pub fn jtk_lc_squish_classify(
+        n_pairs: usize, u1: *const u64, u2: *const u64, ari: *const f64, count: *const u64,
+        cfg: *const JtkSquishConfig, ids: *mut u64, stiff: *mut u8, id_cap: usize, n_ids: *mut usize) -> c_int;
     // the resident-batch form (jtk_lc.h: session_create + run + fetch == jtk_lc_cluster_chunks) and, on it, the reference's
     // trace! rows of one chunk (TOTAL / CAND / PICK / DUMP / RANGE / LK / COUNTS; pseudo_mcmc.rs:122-127,236,250-262,467-472,539)
     pub fn jtk_lc_session_create(
