@@ -207,7 +207,7 @@ void launch_pick_trace(hipStream_t s, uint32_t ci, const ReadMeta *reads, const 
                        const jtk_lc_params_t *params, const double *table, const uint16_t *homop, const uint64_t *homop_off,
                        const double *cand, uint32_t *list, uint8_t *sel, double *feat, uint32_t *vtype, uint32_t *pos,
                        const HmmDev *hmm2, const int *rawG, const double *lk, int fused, uint32_t *tr, uint32_t *tr_count);
-// mcmc_kernels.hip: the chain.  Its work area lives in LDS (launch_mcmc, sized per launch by mcmc_lds_bytes) or, for pile-ups
+// mcmc_kernels.hip (with the chain_*.h headers it alone includes; the sizes: chain_layout.h): the chain.  Its work area lives in LDS (launch_mcmc, sized per launch by mcmc_lds_bytes) or, for pile-ups
 // beyond that, in global memory (launch_mcmc_huge, mcmc_ws_bytes); launch_mcmc_trace runs one chunk again with its records
 size_t mcmc_trace_doubles(uint32_t n_reads);
 int launch_mcmc_trace(hipStream_t s, const ChunkMeta *chunks, ChunkState *state, const jtk_lc_params_t *params, const double *feat,

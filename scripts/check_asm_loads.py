@@ -1,4 +1,5 @@
-"""Static check of the hand-issued LDS loads of mcmc_chain_tab's rejected-step loop (jtk_amd/csrc/mcmc_kernels.hip).
+"""Static check of the hand-issued LDS loads of mcmc_chain_tab's rejected-step loop (jtk_amd/csrc/chain_tab.h, compiled as part of
+mcmc_kernels.hip, the one file that includes it).
 
 The loop loads a proposal's row with `ds_read_b64` from inline asm -- invisible to hipcc's wait-count scoreboard -- and waits for it
 with a hand-placed `s_waitcnt lgkmcnt(1)` / `lgkmcnt(0)`.  What the compiler must not do is touch the destination registers between

@@ -2,6 +2,7 @@
 """Static census of the gfx950 assembly of one source file of the library -- no GPU needed.
 
     python3 scripts/isa_census.py mcmc_kernels.hip                 # every function: size, instruction mix, scalar spills
+                                                                   # (the chains' code is in the chain_*.h headers this file includes)
     python3 scripts/isa_census.py mcmc_kernels.hip -f chain_tabILi3 # + every loop of the matching functions
     python3 scripts/isa_census.py phmm_sweep.hip -D JTK_PHMM_MARKS   # + the regions between `; MARK x` comments
 

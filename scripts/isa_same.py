@@ -6,6 +6,9 @@ recording instantiations behind jtk_lc_session_trace: `same` for every product k
 
     python3 scripts/isa_same.py mcmc_kernels.hip filter_kernels.hip [--rev HEAD]
 
+Headers are compared through the sources that include them: the chain's chain_*.h through mcmc_kernels.hip, the one file that
+includes them.
+
 A kernel whose mangled name changed without its code changing (template parameters added, a trailing argument) is paired by
 hand: `--renamed SUBSTRING_OF_OLD_NAME=SUBSTRING_OF_NEW_NAME` (repeatable) compares the one old function whose name contains
 the first with the one new function whose name contains the second and prints both names.
