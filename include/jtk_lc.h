@@ -398,6 +398,75 @@ JTK_LC_API int jtk_lc_squish_clusters(size_t n_reads, const uint64_t *node_off, 
 JTK_LC_API int jtk_lc_squish_classify(size_t n_pairs, const uint64_t *u1, const uint64_t *u2, const double *ari, const uint64_t *count,
                            const jtk_squish_config_t *cfg, uint64_t *ids, uint8_t *stiff, size_t id_cap, size_t *n_ids);
 
+/* ---- the step after the stage: purge diverged clusters, and the two functions it rests on ---------------------------
+ * `ds.purge(&purge_config)` runs right after local_clustering, twice (cli/src/pipeline.rs:164-165; purge_diverged.rs:42-48):
+ * purge_diverged_nodes (:238-322), then re_cluster (:189-236), which estimates copy numbers over the assembly graph (not part
+ * of this library) and calls local_clustering_selected on the purged chunks (jtk_lc_cluster_chunks).  It rests on
+ * `determine_chunks::calc_sim_thr` (determine_chunks.rs:796-823) and `estimate_error_rate::estimate_error_rate`
+ * (estimate_error_rate.rs:37-133), which correct_deletion (encode/deletion_fill.rs:141-144), jtk.rs:251-253 and
+ * determine_chunks.rs:113,157,164 call too: they have entry points of their own.  purge_largeindel is not covered.
+ * The data set is flattened as for jtk_lc_correct_clustering (n_reads, node_off, nodes in encoded_reads order, chunks), plus
+ * what Node::recover (definitions/src/lib.rs:773-813) reads: node e's sequence at seq_bases[seq_off[e] .. seq_off[e+1]) and its
+ * per-base ops at ops[ops_off[e] .. ops_off[e+1]) (codes as above; 0 and 1 both stand for a cigar Match column, whether it
+ * shows '|' or 'X' is decided by the bases; the ops_out of jtk_lc_cluster_chunks can be passed as it is), and chunk c's
+ * sequence (c indexes chunks[]) at tmpl_bases[tmpl_off[c] .. tmpl_off[c+1]).  Bases are compared after ASCII upper-casing; no
+ * base is refused.  Chunk ids must not repeat in chunks[] (JTK_ERR_INVALID_ARG); a sequence, op list or template of 2^31
+ * bytes or more is JTK_ERR_UNSUPPORTED.
+ *
+ * jtk_lc_node_errors: per node, err_len[e] = the number of alignment columns and err_num[e] = those that are not '|'; the
+ * node's error rate is err_num / err_len as one f64 division (determine_chunks.rs:796-803 == estimate_error_rate.rs:68-70).
+ * status[e]: 0, or, decided by the first op in order that fails,
+ *   JTK_ERR_OPS_MISMATCH  an op steps past the end of the node's sequence or of the template (the reference's slice panics;
+ *                         ops that consume LESS than a sequence are accepted: recover does not check),
+ *   JTK_ERR_INVALID_ARG   an op code above 3,
+ *   JTK_ERR_CHUNK_FAILED  a node without columns (0 / 0) or of a chunk id that is not in chunks[] (chunks[&node.chunk]);
+ * err_num = err_len = 0 for such a node.  Returns JTK_ERR_CHUNK_FAILED if any node failed; every node is written. */
+JTK_LC_API int jtk_lc_node_errors(size_t n_reads, const uint64_t *node_off, const jtk_cc_node_t *nodes, size_t n_chunks,
+                       const jtk_cc_chunk_t *chunks, const uint8_t *seq_bases, const uint64_t *seq_off, const uint8_t *ops,
+                       const uint64_t *ops_off, const uint8_t *tmpl_bases, const uint64_t *tmpl_off, uint32_t *err_num,
+                       uint32_t *err_len, int32_t *status, int device);
+/* calc_sim_thr (determine_chunks.rs:806-823): the value at index min(floor(n_nodes x quantile), n_nodes - 1) of the ascending
+ * error rates err_num[e] / err_len[e].  JTK_ERR_INVALID_ARG for a quantile outside [0, 1], n_nodes = 0 or an err_len of 0. */
+JTK_LC_API int jtk_lc_error_quantile(size_t n_nodes, const uint32_t *err_num, const uint32_t *err_len, double quantile, double *out,
+                          int device);
+/* estimate_error_rate (estimate_error_rate.rs:37-133) on the nodes' error counts: one rate per read (read_err[n_reads], by
+ * position in the flattened data set; a read without nodes gets the 0 / 0 of :101 as the NaN 0x7ff8000000000000) and one per
+ * (chunk, cluster): chunk c's clusters at chunk_err[chunk_err_off[c] .. chunk_err_off[c+1]), chunk_err_off[n_chunks + 1] being
+ * the prefix sum of cluster_num (the caller gives chunk_err_cap doubles; sum(cluster_num) are needed), the square root of the
+ * median squared residual, and the number of passes of the loop :78-108.  Every sum runs in the reference's order (chunk rates:
+ * reads in order, their nodes in order; the regulariser :32: chunks ascending by id), so the outputs and the pass count are
+ * the reference's bit for bit.  fallback is every read's first rate (:55-58).
+ * JTK_ERR_CHUNK_FAILED: a node's cluster is not below its chunk's cluster_num or its chunk is not in chunks[] (:49-50 index
+ * out of bounds), or 100,000 passes without convergence (the reference would not return).  JTK_ERR_INVALID_ARG: no nodes (the
+ * median of nothing, :123-126), an err_len of 0, chunk_err_cap too small.  Nothing is written on failure. */
+JTK_LC_API int jtk_lc_estimate_error_rate(size_t n_reads, const uint64_t *node_off, const jtk_cc_node_t *nodes, const uint32_t *err_num,
+                               const uint32_t *err_len, size_t n_chunks, const jtk_cc_chunk_t *chunks, double fallback,
+                               double *read_err, double *chunk_err, uint64_t *chunk_err_off, size_t chunk_err_cap,
+                               double *median_of_sqrt_err, uint32_t *n_iter, int device);
+/* purge_diverged_nodes (purge_diverged.rs:238-322) with get_diverged_clusters (:299-309) on one upload: the node errors, their
+ * 0.5 quantile as the fallback (:301), the fit, then diverged[slot] = thr < chunk_err[slot] (THR = 0.1, :40); a chunk whose
+ * clusters are ALL diverged keeps them all (:241-249).  n_post = the length of the data set's posterior array (only the nodes'
+ * post_off / post_len are read).  Output, to be applied by the caller:
+ *   diverged[], chunk_err_off[]  flat as in jtk_lc_estimate_error_rate (slot_cap entries given, sum(cluster_num) needed)
+ *   chunks[c].cluster_num        reduced by the chunk's number of flags (:261-265)
+ *   keep[e]                      0 where the node's (chunk, cluster) is flagged: the node is removed (:271-272)
+ *   cluster_out[e]               Node.cluster minus the flagged clusters below it (:312-316)
+ *   touched[e]                   1 for a kept node of a chunk with a flag: remove_diverged rewrites it (:273-278)
+ *   post_keep[n_post]            0 for the posterior entries remove_diverged drops (:318-321), 1 everywhere else
+ *   purged[], *n_purged          the chunk ids with a flag, ascending (:291-295; purged_cap entries given, n_chunks suffice)
+ *   read_err, chunk_err, median_of_sqrt_err   the fit, each optional (NULL skips it)
+ * The caller then drops the reads left without nodes (:283) and rebuilds every read's gaps and edges from its nodes
+ * (encode::nodes_to_encoded_read, :284-290).
+ * JTK_ERR_CHUNK_FAILED: a node fails in jtk_lc_node_errors, the fit fails, or a kept node of a chunk with a flag carries a
+ * posterior longer than the chunk's cluster_num (:320 indexes past cluster_info).  JTK_ERR_INVALID_ARG: no nodes
+ * (calc_sim_thr indexes an empty list), slot_cap or purged_cap too small.  Nothing is written on failure, chunks[] included. */
+JTK_LC_API int jtk_lc_purge_diverged(size_t n_reads, const uint64_t *node_off, const jtk_cc_node_t *nodes, size_t n_post, size_t n_chunks,
+                          jtk_cc_chunk_t *chunks, const uint8_t *seq_bases, const uint64_t *seq_off, const uint8_t *ops,
+                          const uint64_t *ops_off, const uint8_t *tmpl_bases, const uint64_t *tmpl_off, double thr, uint8_t *diverged,
+                          uint64_t *chunk_err_off, size_t slot_cap, uint8_t *keep, uint64_t *cluster_out, uint8_t *touched,
+                          uint8_t *post_keep, uint64_t *purged, size_t purged_cap, size_t *n_purged, double *read_err,
+                          double *chunk_err, double *median_of_sqrt_err, int device);
+
 /* Sort key of pileup_nodes (mod.rs:47-50): number of alignment columns that are not '|' in
  * Node::recover (definitions/src/lib.rs:773-813) for run-length cigar ops given per base. */
 JTK_LC_API int jtk_lc_pileup_sort_key(const uint8_t *tmpl, uint64_t tmpl_len, const uint8_t *read, uint64_t read_len,

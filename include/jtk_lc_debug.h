@@ -28,6 +28,11 @@ JTK_LC_API size_t jtk_lc_debug_cc_sims(size_t job, double *out, size_t cap);
  * slowest chunk: this is how bench.py names it.  Either pointer may be null. */
 JTK_LC_API int jtk_lc_debug_chain_profile(jtk_lc_session_t *s, uint64_t *cycles, uint32_t *events);
 
+/* HIP-event times of this thread's last jtk_lc_node_errors / jtk_lc_estimate_error_rate / jtk_lc_purge_diverged call, 4 doubles:
+ * the upload of the sequences (allocation included) in ms, the column-walk kernel in ms, the whole call on its stream in ms
+ * (upload to the last copy back), and the passes of the fit. */
+JTK_LC_API void jtk_lc_debug_purge_timing(double *out);
+
 #ifdef __cplusplus
 }
 #endif

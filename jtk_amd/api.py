@@ -241,6 +241,104 @@ def squish_classify(u1, u2, ari, count, config=None):
     return ids[:n_ids.value], stiff[:n_ids.value]
 
 
+def _sequences(seqs):
+    """(bases, off, ops, ops_off, tmpl, tmpl_off) of the purge entry points as contiguous arrays of the ABI's types"""
+    kinds = (np.uint8, np.uint64, np.uint8, np.uint64, np.uint8, np.uint64)
+    return tuple(np.ascontiguousarray(a, dtype=k) for a, k in zip(seqs, kinds))
+
+
+def _flat_chunks(chunks):
+    if chunks.dtype != ffi.CC_CHUNK_DT or not chunks.flags.c_contiguous:
+        raise ValueError("chunks must be a contiguous array of ffi.CC_CHUNK_DT")
+
+
+def node_errors(node_off, nodes, chunks, seqs, device=0, raise_on_node_failure=True):
+    """jtk_lc_node_errors: per node the alignment columns against its chunk (Node::recover, definitions/src/lib.rs:773-813)
+    that are not '|' and their number; a node's error rate is err_num / err_len (determine_chunks.rs:796-803).
+    `seqs` = (seq_bases, seq_off, ops, ops_off, tmpl_bases, tmpl_off): the nodes' sequences and per-base ops, the chunks'
+    sequences in `chunks` order.  Returns dict(err_num, err_len, status, rc); rc is -6 when a node failed (status per node)."""
+    nodes = np.ascontiguousarray(nodes, dtype=ffi.CC_NODE_DT)
+    node_off = np.ascontiguousarray(node_off, dtype=np.uint64)
+    _flat_chunks(chunks)
+    sb, so, ob, oo, tb, to = _sequences(seqs)
+    n = len(nodes)
+    num, length = np.zeros(n + 1, dtype=np.uint32), np.zeros(n + 1, dtype=np.uint32)
+    status = np.zeros(n + 1, dtype=np.int32)
+    rc = ffi.lib().jtk_lc_node_errors(len(node_off) - 1, u64p(node_off), nodes.ctypes.data, len(chunks), chunks.ctypes.data, u8p(sb),
+                                      u64p(so), u8p(ob), u64p(oo), u8p(tb), u64p(to), u32p(num), u32p(length),
+                                      status.ctypes.data_as(C.POINTER(C.c_int32)), device)
+    if rc != 0 and (raise_on_node_failure or rc != -6):
+        check(rc)
+    return dict(err_num=num[:n], err_len=length[:n], status=status[:n], rc=rc)
+
+
+def error_quantile(err_num, err_len, quantile, device=0):
+    """jtk_lc_error_quantile: calc_sim_thr (determine_chunks.rs:806-823) on the nodes' error counts."""
+    err_num = np.ascontiguousarray(err_num, dtype=np.uint32)
+    err_len = np.ascontiguousarray(err_len, dtype=np.uint32)
+    if len(err_num) != len(err_len):
+        raise ValueError("err_num and err_len differ in length")
+    out = C.c_double(0.0)
+    check(ffi.lib().jtk_lc_error_quantile(len(err_num), u32p(err_num), u32p(err_len), float(quantile), C.byref(out), device))
+    return out.value
+
+
+def estimate_error_rate(node_off, nodes, err_num, err_len, chunks, fallback, device=0):
+    """jtk_lc_estimate_error_rate: estimate_error_rate (estimate_error_rate.rs:37-133).  Returns dict(read_err, chunk_err,
+    chunk_err_off, median_of_sqrt_err, n_iter): one rate per read, one per (chunk, cluster) flat in `chunks` order."""
+    nodes = np.ascontiguousarray(nodes, dtype=ffi.CC_NODE_DT)
+    node_off = np.ascontiguousarray(node_off, dtype=np.uint64)
+    err_num = np.ascontiguousarray(err_num, dtype=np.uint32)
+    err_len = np.ascontiguousarray(err_len, dtype=np.uint32)
+    _flat_chunks(chunks)
+    if not len(err_num) == len(err_len) == len(nodes):
+        raise ValueError("err_num / err_len need one entry per node")
+    n_reads, cap = len(node_off) - 1, int(chunks["cluster_num"].astype(np.uint64).sum())
+    read_err, chunk_err = np.zeros(n_reads + 1, dtype=np.float64), np.zeros(cap + 1, dtype=np.float64)
+    off = np.zeros(len(chunks) + 1, dtype=np.uint64)
+    median, n_iter = C.c_double(0.0), C.c_uint32(0)
+    check(ffi.lib().jtk_lc_estimate_error_rate(n_reads, u64p(node_off), nodes.ctypes.data, u32p(err_num), u32p(err_len), len(chunks),
+                                               chunks.ctypes.data, float(fallback), f64p(read_err), f64p(chunk_err), u64p(off), cap,
+                                               C.byref(median), C.byref(n_iter), device))
+    return dict(read_err=read_err[:n_reads], chunk_err=chunk_err[:cap], chunk_err_off=off, median_of_sqrt_err=median.value,
+                n_iter=n_iter.value)
+
+
+def purge_diverged(node_off, nodes, n_post, chunks, seqs, thr=0.1, device=0):
+    """jtk_lc_purge_diverged: purge_diverged_nodes (purge_diverged.rs:238-322) on the flattened data set of correct_clustering
+    plus `seqs` (see node_errors); thr defaults to the reference's THR.  `chunks` (ffi.CC_CHUNK_DT) is updated in place
+    (cluster_num).  Returns dict(diverged, chunk_err_off, keep, cluster, touched, post_keep, purged, read_err, chunk_err,
+    median_of_sqrt_err): the flag per (chunk, cluster) flat in `chunks` order, per node whether it stays, its new cluster and
+    whether it is rewritten, per posterior entry whether it stays, and the ids of the chunks that lost a cluster."""
+    nodes = np.ascontiguousarray(nodes, dtype=ffi.CC_NODE_DT)
+    node_off = np.ascontiguousarray(node_off, dtype=np.uint64)
+    _flat_chunks(chunks)
+    sb, so, ob, oo, tb, to = _sequences(seqs)
+    n, n_reads, m, n_post = len(nodes), len(node_off) - 1, len(chunks), int(n_post)
+    cap = int(chunks["cluster_num"].astype(np.uint64).sum())
+    diverged, off = np.zeros(cap + 1, dtype=np.uint8), np.zeros(m + 1, dtype=np.uint64)
+    keep, cluster, touched = np.zeros(n + 1, dtype=np.uint8), np.zeros(n + 1, dtype=np.uint64), np.zeros(n + 1, dtype=np.uint8)
+    post_keep, purged = np.zeros(n_post + 1, dtype=np.uint8), np.zeros(m + 1, dtype=np.uint64)
+    read_err, chunk_err = np.zeros(n_reads + 1, dtype=np.float64), np.zeros(cap + 1, dtype=np.float64)
+    n_purged, median = C.c_size_t(0), C.c_double(0.0)
+    check(ffi.lib().jtk_lc_purge_diverged(n_reads, u64p(node_off), nodes.ctypes.data, n_post, m, chunks.ctypes.data, u8p(sb), u64p(so),
+                                          u8p(ob), u64p(oo), u8p(tb), u64p(to), float(thr), u8p(diverged), u64p(off), cap, u8p(keep),
+                                          u64p(cluster), u8p(touched), u8p(post_keep), u64p(purged), m, C.byref(n_purged),
+                                          f64p(read_err), f64p(chunk_err), C.byref(median), device))
+    return dict(diverged=diverged[:cap], chunk_err_off=off, keep=keep[:n], cluster=cluster[:n], touched=touched[:n],
+                post_keep=post_keep[:n_post], purged=purged[:n_purged.value], read_err=read_err[:n_reads], chunk_err=chunk_err[:cap],
+                median_of_sqrt_err=median.value)
+
+
+def purge_timing():
+    """jtk_lc_debug_purge_timing (include/jtk_lc_debug.h): upload ms, column-walk ms, device ms and fit passes of the last call"""
+    f = ffi.lib().jtk_lc_debug_purge_timing
+    f.restype, f.argtypes = None, [C.POINTER(C.c_double)]
+    out = (C.c_double * 4)()
+    f(out)
+    return dict(upload_ms=out[0], walk_ms=out[1], device_ms=out[2], n_iter=int(out[3]))
+
+
 def correct_clustering_with_sims(*args, **kw):
     """correct_clustering with the diagnostic switch of include/jtk_lc_debug.h on: returns (cluster, touched, sims), sims = the
     raw similarity matrix (before filter_similarity) of every corrected chunk, in selected_chunks order.  A test hook: the

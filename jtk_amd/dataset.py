@@ -406,6 +406,82 @@ def squish_erroneous_clusters(ds, config=None, device=0):
     return {c["id"]: int(k) for c, k in zip(ds["selected_chunks"], out["classes"])}
 
 
+def query_length(node):
+    """Node::query_length (definitions/src/lib.rs:754-762): the read bases the node's cigar consumes"""
+    return sum(int(n) for n, k in _OP_RE.findall(node["cigar"]) if k in "MI")
+
+
+def nodes_to_encoded_read(read, raw_seq):
+    """encode::nodes_to_encoded_read (encode/mod.rs:94-119) with Edge::from_nodes (definitions/src/lib.rs:647-669): the read's
+    gaps and edges rebuilt, in place, from its nodes and its raw read (upper-cased)."""
+    seq, nodes = raw_seq.upper(), read["nodes"]
+    last = nodes[-1]
+    read["original_length"] = len(seq)
+    read["leading_gap"] = seq[:nodes[0]["position_from_start"]]
+    read["trailing_gap"] = seq[last["position_from_start"] + query_length(last):]
+    read["edges"] = []
+    for a, b in zip(nodes, nodes[1:]):
+        end, start = a["position_from_start"] + query_length(a), b["position_from_start"]
+        read["edges"].append({"from": a["chunk"], "to": b["chunk"], "offset": start - end,
+                              "label": "" if start <= end else seq[:start][end:]})
+
+
+def purge_diverged_nodes(ds, device=0, thr=0.1):
+    """purge_diverged_nodes (purge_diverged.rs:238-322) on the parsed JSON object `ds` (modified in place):
+    jtk_lc_purge_diverged on the flattened nodes with their sequences, then the write-back -- the flagged clusters' nodes go
+    (:271-272), the other nodes of those chunks are renumbered and lose the flagged posterior entries (:311-322), reads left
+    without nodes are dropped (:283), every other read gets its gaps and edges rebuilt from its raw read (:284-290).  Returns
+    the ids of the chunks that lost a cluster, ascending: what `purge` (:42-48) hands to re_cluster, whose copy-number
+    estimation (estimate_multiplicity, :210-212) is not part of this library."""
+    n_nodes = sum(len(r["nodes"]) for r in ds["encoded_reads"])
+    nodes = np.zeros(n_nodes, dtype=ffi.CC_NODE_DT)
+    node_off = np.zeros(len(ds["encoded_reads"]) + 1, dtype=np.uint64)
+    seq_off, ops_off = np.zeros(n_nodes + 1, dtype=np.uint64), np.zeros(n_nodes + 1, dtype=np.uint64)
+    seqs, ops = [], []
+    e = n_post = 0
+    for r, read in enumerate(ds["encoded_reads"]):
+        for node in read["nodes"]:
+            nodes[e] = (node["chunk"], node["cluster"], 1 if node["is_forward"] else 0, len(node["posterior"]), n_post)
+            n_post += len(node["posterior"])
+            seqs.append(_seq(node["seq"]))
+            ops.append(cigar_to_ops(node["cigar"]))
+            seq_off[e + 1] = seq_off[e] + len(seqs[-1])
+            ops_off[e + 1] = ops_off[e] + len(ops[-1])
+            e += 1
+        node_off[r + 1] = e
+    chunks = np.zeros(len(ds["selected_chunks"]), dtype=ffi.CC_CHUNK_DT)
+    tmpls = [_seq(c["seq"]) for c in ds["selected_chunks"]]
+    tmpl_off = np.zeros(len(tmpls) + 1, dtype=np.uint64)
+    for i, c in enumerate(ds["selected_chunks"]):
+        chunks[i] = (c["id"], c["cluster_num"], c["copy_num"], c["score"])
+        tmpl_off[i + 1] = tmpl_off[i] + len(tmpls[i])
+    cat = lambda parts: np.concatenate(parts) if parts else np.zeros(0, np.uint8)   # noqa: E731
+    out = api.purge_diverged(node_off, nodes, n_post, chunks, (cat(seqs), seq_off, cat(ops), ops_off, cat(tmpls), tmpl_off), thr=thr,
+                             device=device)
+    for i, c in enumerate(ds["selected_chunks"]):
+        c["cluster_num"] = int(chunks["cluster_num"][i])                     # :261-265
+    raw = {r["id"]: r["seq"] for r in ds["raw_reads"]}
+    e = p = 0
+    reads = []
+    for read in ds["encoded_reads"]:
+        kept = []
+        for node in read["nodes"]:
+            m = len(node["posterior"])
+            if out["keep"][e]:
+                if out["touched"][e]:                                        # remove_diverged :311-322
+                    node["cluster"] = int(out["cluster"][e])
+                    node["posterior"] = [x for i, x in enumerate(node["posterior"]) if out["post_keep"][p + i]]
+                kept.append(node)
+            e += 1
+            p += m
+        if kept:                                                             # :283
+            read["nodes"] = kept
+            nodes_to_encoded_read(read, raw[read["id"]])                     # :284-290
+            reads.append(read)
+    ds["encoded_reads"] = reads
+    return [int(x) for x in out["purged"]]
+
+
 _COMPLEMENT = {"A": "T", "C": "G", "G": "C", "T": "A"}
 
 
@@ -477,17 +553,21 @@ def correct_clustering(ds, device=0, min_gain=None):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--stage", default="local_clustering", choices=("local_clustering", "correct_clustering", "squish_erroneous_clusters", "corrected", "realign"),
+    ap.add_argument("--stage", default="local_clustering", choices=("local_clustering", "correct_clustering", "squish_erroneous_clusters", "corrected", "realign", "purge_diverged_nodes"),
                     help="which JTK stage to run on the file (jtk local_clustering / jtk correct_clustering); "
                          "squish_erroneous_clusters: the step JTK runs in front of the correction, with its default "
                          "configuration; corrected: that step, then correct_clustering (cli/src/pipeline.rs:174-175); realign: "
-                         "replace every node's cigar by its global alignment to the chunk sequence")
+                         "replace every node's cigar by its global alignment to the chunk sequence; purge_diverged_nodes: the first "
+                         "half of `ds.purge` (purge_diverged.rs:238-322), the purged chunk ids go to stderr")
     ap.add_argument("input", help="DataSet JSON ('-' = stdin)")
     ap.add_argument("output", help="DataSet JSON ('-' = stdout)")
     ap.add_argument("--chunks", default="", help="comma-separated chunk ids (local_clustering_selected); default: all")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--no-refit", action="store_true",
                     help="skip update_models_on_both_strands (mod.rs:58): cluster with model_param as found in the file")
+    ap.add_argument("--recluster", action="store_true",
+                    help="after purge_diverged_nodes: local_clustering_selected on the purged chunks with the copy numbers as they "
+                         "stand (re_cluster, purge_diverged.rs:189-236, without its estimate_multiplicity)")
     ap.add_argument("--keep-going", action="store_true",
                     help="a chunk that fails (where the reference would panic, or an unsupported shape) is left untouched "
                          "and listed on stderr instead of aborting the stage")
@@ -506,6 +586,12 @@ def main(argv=None):
         squish_erroneous_clusters(ds, device=args.device)
         if args.stage == "corrected":
             correct_clustering(ds, device=args.device)
+    elif args.stage == "purge_diverged_nodes":
+        validate(ds)
+        purged = purge_diverged_nodes(ds, device=args.device)
+        sys.stderr.write("PD\tPurged\t%s\n" % ",".join(str(x) for x in purged))
+        if args.recluster and purged:
+            local_clustering_selected(ds, purged, device=args.device, failed=failed, refit=not args.no_refit, record=record, trace=trace)
     elif args.stage == "correct_clustering":
         validate(ds)
         if args.chunks:

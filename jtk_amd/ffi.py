@@ -87,7 +87,7 @@ CC_CHUNK_DT = np.dtype([("id", "<u8"), ("cluster_num", "<u4"), ("copy_num", "<u4
 # every symbol declared in include/jtk_lc.h (tests check the library exports them)
 EXPORTED_SYMBOLS = (
     "jtk_lc_cluster_chunks", "jtk_lc_cluster_chunks_multi", "jtk_lc_cluster_polished", "jtk_lc_polish_chunks", "jtk_lc_align_reads", "jtk_lc_align_reads_mode", "jtk_lc_modification_table",
-    "jtk_lc_cluster_features", "jtk_lc_estimate_gains", "jtk_lc_estimate_minimum_gain", "jtk_lc_fit_model", "jtk_lc_correct_clustering", "jtk_lc_squish_clusters", "jtk_lc_squish_classify", "jtk_lc_trim_cache", "jtk_lc_pileup_sort_key", "jtk_lc_normalize_pileup", "jtk_lc_strerror",
+    "jtk_lc_cluster_features", "jtk_lc_estimate_gains", "jtk_lc_estimate_minimum_gain", "jtk_lc_fit_model", "jtk_lc_correct_clustering", "jtk_lc_squish_clusters", "jtk_lc_squish_classify", "jtk_lc_node_errors", "jtk_lc_error_quantile", "jtk_lc_estimate_error_rate", "jtk_lc_purge_diverged", "jtk_lc_trim_cache", "jtk_lc_pileup_sort_key", "jtk_lc_normalize_pileup", "jtk_lc_strerror",
     "jtk_lc_last_error", "jtk_lc_version", "jtk_lc_device_ok", "jtk_lc_last_timing",
     "jtk_lc_session_create", "jtk_lc_session_run", "jtk_lc_session_fetch", "jtk_lc_session_destroy", "jtk_lc_session_trace",
 )
@@ -151,6 +151,12 @@ def lib():
     PSQ, PSZ = C.POINTER(SquishConfig), C.POINTER(sz)
     sig("jtk_lc_squish_clusters", i32, sz, PU64, vp, PD, sz, vp, PSQ, PU8, PU64, PU8, PU64, PU64, PD, PU64, sz, PSZ, i32)
     sig("jtk_lc_squish_classify", i32, sz, PU64, PU64, PD, PU64, PSQ, PU64, PU8, sz, PSZ)
+    PI32 = C.POINTER(C.c_int32)
+    sig("jtk_lc_node_errors", i32, sz, PU64, vp, sz, vp, PU8, PU64, PU8, PU64, PU8, PU64, PU32, PU32, PI32, i32)
+    sig("jtk_lc_error_quantile", i32, sz, PU32, PU32, C.c_double, PD, i32)
+    sig("jtk_lc_estimate_error_rate", i32, sz, PU64, vp, PU32, PU32, sz, vp, C.c_double, PD, PD, PU64, sz, PD, PU32, i32)
+    sig("jtk_lc_purge_diverged", i32, sz, PU64, vp, sz, sz, vp, PU8, PU64, PU8, PU64, PU8, PU64, C.c_double, PU8, PU64, sz, PU8, PU64,
+        PU8, PU8, PU64, sz, PSZ, PD, PD, PD, i32)
     sig("jtk_lc_trim_cache", i32, i32)
     sig("jtk_lc_cluster_features", i32, PP, sz, vp, PD, PU32, PU32, PD, u32, vp, i32)
     sig("jtk_lc_pileup_sort_key", i32, PU8, u64, PU8, u64, PU8, u64, PU64)

@@ -111,6 +111,29 @@ extern "C" {
     pub fn jtk_lc_squish_classify(
         n_pairs: usize, u1: *const u64, u2: *const u64, ari: *const f64, count: *const u64,
         cfg: *const JtkSquishConfig, ids: *mut u64, stiff: *mut u8, id_cap: usize, n_ids: *mut usize) -> c_int;
+    // the step after the stage, `ds.purge` (purge_diverged.rs:42-48), and the two functions it rests on.  The flattened DataSet of
+    // jtk_lc_correct_clustering plus what Node::recover reads: node sequences, per-base ops (0 Match, 1 Mismatch, 2 Ins, 3 Del)
+    // and the chunk sequences in chunks[] order.
+    // Node::recover's columns per node (definitions/src/lib.rs:773-813): err_num / err_len is the node's error rate
+    pub fn jtk_lc_node_errors(
+        n_reads: usize, node_off: *const u64, nodes: *const JtkCcNode, n_chunks: usize, chunks: *const JtkCcChunk,
+        seq_bases: *const u8, seq_off: *const u64, ops: *const u8, ops_off: *const u64, tmpl_bases: *const u8, tmpl_off: *const u64,
+        err_num: *mut u32, err_len: *mut u32, status: *mut i32, device: c_int) -> c_int;
+    // calc_sim_thr (determine_chunks.rs:806-823; also deletion_fill.rs:141, jtk.rs:251, determine_chunks.rs:113,157,164)
+    pub fn jtk_lc_error_quantile(n_nodes: usize, err_num: *const u32, err_len: *const u32, quantile: f64, out: *mut f64,
+                                 device: c_int) -> c_int;
+    // estimate_error_rate (estimate_error_rate.rs:37-133); chunk_err is flat in chunks[] order, chunk_err_off its n_chunks + 1 offsets
+    pub fn jtk_lc_estimate_error_rate(
+        n_reads: usize, node_off: *const u64, nodes: *const JtkCcNode, err_num: *const u32, err_len: *const u32,
+        n_chunks: usize, chunks: *const JtkCcChunk, fallback: f64, read_err: *mut f64, chunk_err: *mut f64,
+        chunk_err_off: *mut u64, chunk_err_cap: usize, median_of_sqrt_err: *mut f64, n_iter: *mut u32, device: c_int) -> c_int;
+    // purge_diverged_nodes (purge_diverged.rs:238-322) up to the rebuild of the reads; read_err / chunk_err / median are optional
+    pub fn jtk_lc_purge_diverged(
+        n_reads: usize, node_off: *const u64, nodes: *const JtkCcNode, n_post: usize, n_chunks: usize, chunks: *mut JtkCcChunk,
+        seq_bases: *const u8, seq_off: *const u64, ops: *const u8, ops_off: *const u64, tmpl_bases: *const u8, tmpl_off: *const u64,
+        thr: f64, diverged: *mut u8, chunk_err_off: *mut u64, slot_cap: usize, keep: *mut u8, cluster_out: *mut u64,
+        touched: *mut u8, post_keep: *mut u8, purged: *mut u64, purged_cap: usize, n_purged: *mut usize,
+        read_err: *mut f64, chunk_err: *mut f64, median_of_sqrt_err: *mut f64, device: c_int) -> c_int;
     // the resident-batch form (jtk_lc.h: session_create + run + fetch == jtk_lc_cluster_chunks) and, on it, the reference's
     // trace! rows of one chunk (TOTAL / CAND / PICK / DUMP / RANGE / LK / COUNTS; pseudo_mcmc.rs:122-127,236,250-262,467-472,539)
     pub fn jtk_lc_session_create(

@@ -96,6 +96,71 @@ pub(crate) fn clustering_on_pileups_gpu(
     consensus_and_clusternum  // mod.rs:73 on is unchanged (chunk.seq/score/cluster_num write-back, normalize_local_clustering)
 }
 
+/// `PurgeDivergent::purge` (purge_diverged.rs:42-48) with purge_diverged_nodes (:238-322) on the device: the data set is flattened,
+/// jtk_lc_purge_diverged says which nodes go and how the others are renumbered, the outputs are applied as :261-290 does, and
+/// re_cluster (:189-236: estimate_multiplicity over the assembly graph, then local_clustering_selected, which enters the GPU
+/// through clustering_on_pileups_gpu above) stays JTK's own.
+pub(crate) fn purge_gpu(ds: &mut definitions::DataSet, thr: f64) -> std::collections::HashSet<u64> {
+    let (mut node_off, mut nodes, mut n_post) = (vec![0u64], vec![], 0usize);
+    let (mut seq, mut seq_off, mut ops, mut ops_off) = (vec![], vec![0u64], vec![], vec![0u64]);
+    for read in ds.encoded_reads.iter() {
+        for node in read.nodes.iter() {
+            nodes.push(JtkCcNode { chunk: node.chunk, cluster: node.cluster, is_forward: node.is_forward as u32,
+                post_len: node.posterior.len() as u32, post_off: n_post as u64 });
+            n_post += node.posterior.len();
+            seq.extend_from_slice(node.seq());
+            seq_off.push(seq.len() as u64);
+            ops.extend(crate::misc::ops_to_kiley(&node.cigar).iter().map(|op| match op {
+                kiley::Op::Match => 0u8, kiley::Op::Mismatch => 1, kiley::Op::Ins => 2, kiley::Op::Del => 3 }));
+            ops_off.push(ops.len() as u64);
+        }
+        node_off.push(nodes.len() as u64);
+    }
+    let (mut tmpl, mut tmpl_off) = (vec![], vec![0u64]);
+    let mut chunks: Vec<JtkCcChunk> = ds.selected_chunks.iter().map(|c| {
+        tmpl.extend_from_slice(c.seq());
+        tmpl_off.push(tmpl.len() as u64);
+        JtkCcChunk { id: c.id, cluster_num: c.cluster_num as u32, copy_num: c.copy_num as u32, score: c.score }
+    }).collect();
+    let n_slots: usize = chunks.iter().map(|c| c.cluster_num as usize).sum();
+    let (mut diverged, mut slot_off) = (vec![0u8; n_slots], vec![0u64; chunks.len() + 1]);
+    let (mut keep, mut cluster, mut touched) = (vec![0u8; nodes.len()], vec![0u64; nodes.len()], vec![0u8; nodes.len()]);
+    let (mut post_keep, mut purged, mut n_purged) = (vec![0u8; n_post], vec![0u64; chunks.len()], 0usize);
+    let rc = unsafe { jtk_lc_purge_diverged(ds.encoded_reads.len(), node_off.as_ptr(), nodes.as_ptr(), n_post, chunks.len(),
+        chunks.as_mut_ptr(), seq.as_ptr(), seq_off.as_ptr(), ops.as_ptr(), ops_off.as_ptr(), tmpl.as_ptr(), tmpl_off.as_ptr(), thr,
+        diverged.as_mut_ptr(), slot_off.as_mut_ptr(), n_slots, keep.as_mut_ptr(), cluster.as_mut_ptr(), touched.as_mut_ptr(),
+        post_keep.as_mut_ptr(), purged.as_mut_ptr(), chunks.len(), &mut n_purged, std::ptr::null_mut(), std::ptr::null_mut(),
+        std::ptr::null_mut(), /*device*/ 0) };
+    // -6: a condition on which purge_diverged_nodes itself panics (a slice past a sequence in recover, an index past a table)
+    assert!(rc == 0, "{}", unsafe { std::ffi::CStr::from_ptr(jtk_lc_last_error()) }.to_string_lossy());
+    for (chunk, c) in ds.selected_chunks.iter_mut().zip(chunks.iter()) {
+        chunk.cluster_num = c.cluster_num as usize;                 // :261-265
+    }
+    let (mut e, mut p) = (0usize, 0usize);
+    for read in ds.encoded_reads.iter_mut() {
+        let first = e;
+        for node in read.nodes.iter_mut() {
+            let len = node.posterior.len();
+            if keep[e] == 1 && touched[e] == 1 {                    // remove_diverged :311-322
+                node.cluster = cluster[e];
+                let mut i = 0;
+                node.posterior.retain(|_| { i += 1; post_keep[p + i - 1] == 1 });
+            }
+            e += 1;
+            p += len;
+        }
+        let mut i = first;
+        read.nodes.retain(|_| { i += 1; keep[i - 1] == 1 });        // :271-272
+    }
+    ds.encoded_reads.retain(|read| !read.nodes.is_empty());         // :283
+    let seqs: HashMap<_, _> = ds.raw_reads.iter().map(|r| (r.id, r.seq())).collect();
+    for read in ds.encoded_reads.iter_mut() {                        // :284-290
+        let nodes = std::mem::take(&mut read.nodes);
+        *read = crate::encode::nodes_to_encoded_read(read.id, nodes, seqs[&read.id]).unwrap();
+    }
+    purged[..n_purged].iter().copied().collect()                     // what `purge` hands to re_cluster (:47)
+}
+
 fn to_ffi(h: &kiley::hmm::PairHiddenMarkovModel) -> JtkHmm {
     let d = crate::model_tune::kiley_into_def(h);                  // model_tune.rs:65-92
     JtkHmm { mat_mat: d.mat_mat, mat_ins: d.mat_ins, mat_del: d.mat_del, ins_mat: d.ins_mat, ins_ins: d.ins_ins,
