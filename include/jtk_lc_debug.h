@@ -33,6 +33,23 @@ JTK_LC_API int jtk_lc_debug_chain_profile(jtk_lc_session_t *s, uint64_t *cycles,
  * (upload to the last copy back), and the passes of the fit. */
 JTK_LC_API void jtk_lc_debug_purge_timing(double *out);
 
+/* Keep (on != 0) what the device batches of the following jtk_lc_estimate_gains / jtk_lc_estimate_minimum_gain calls on this thread
+ * held: while the switch is on, the last such call keeps, per batch and in batch order, the template and read bytes with their
+ * offsets, the ops and their lengths exactly as edit_ops_kernel wrote them (JTK_LC_DEBUG_GAINS_OPS_STRIDE bytes per pair, before the
+ * host packs them) and the likelihood of every (template, read) pair.  Pair g of a batch scores read g against template
+ * g / (pairs / templates).  A call that fails keeps the batches it finished.  Nothing is kept while it is off, and switching it
+ * off drops what was kept. */
+#define JTK_LC_DEBUG_GAINS_OPS_STRIDE 512
+JTK_LC_API void jtk_lc_debug_gains_keep(int on);
+JTK_LC_API size_t jtk_lc_debug_gains_batches(void);
+/* sizes[0..3] of batch `batch`: its templates, template bytes, pairs and read bytes; JTK_ERR_INVALID_ARG for a batch that does not
+ * exist */
+JTK_LC_API int jtk_lc_debug_gains_batch_sizes(size_t batch, uint64_t *sizes);
+/* Copy one batch out; a null pointer skips its part.  tmpl_off holds templates + 1 entries, read_off pairs + 1, ops pairs x
+ * JTK_LC_DEBUG_GAINS_OPS_STRIDE bytes, ops_len and lk pairs entries. */
+JTK_LC_API int jtk_lc_debug_gains_batch(size_t batch, uint8_t *tmpl, uint64_t *tmpl_off, uint8_t *reads, uint64_t *read_off,
+                                        uint8_t *ops, uint32_t *ops_len, double *lk);
+
 #ifdef __cplusplus
 }
 #endif

@@ -163,6 +163,40 @@ def estimate_minimum_gain(hmm_forward, hmm_reverse, seed=23908, sample_num=1000,
     return out.value
 
 
+def gains_batches():
+    """what jtk_lc_debug_gains_batch (include/jtk_lc_debug.h) kept of this thread's last estimate_gains / estimate_minimum_gain
+    call: one dict per device batch with tmpl / tmpl_off, reads / read_off, ops [pairs, 512] / ops_len as edit_ops_kernel wrote
+    them, and lk [pairs].  Empty unless the switch was on during the call."""
+    L = ffi.lib()
+    out = []
+    for b in range(L.jtk_lc_debug_gains_batches()):
+        sizes = np.zeros(4, dtype=np.uint64)
+        check(L.jtk_lc_debug_gains_batch_sizes(b, u64p(sizes)))
+        n_tmpl, tmpl_bytes, pairs, read_bytes = (int(v) for v in sizes)
+        k = dict(tmpl=np.zeros(tmpl_bytes, np.uint8), tmpl_off=np.zeros(n_tmpl + 1, np.uint64), reads=np.zeros(read_bytes, np.uint8),
+                 read_off=np.zeros(pairs + 1, np.uint64), ops=np.zeros((pairs, ffi.DEBUG_GAINS_OPS_STRIDE), np.uint8),
+                 ops_len=np.zeros(pairs, np.uint32), lk=np.zeros(pairs))
+        check(L.jtk_lc_debug_gains_batch(b, u8p(k["tmpl"]), u64p(k["tmpl_off"]), u8p(k["reads"]), u64p(k["read_off"]), u8p(k["ops"]),
+                                         u32p(k["ops_len"]), f64p(k["lk"])))
+        out.append(k)
+    return out
+
+
+def with_gains_batches(call, *args, **kw):
+    """call(*args, **kw) -- estimate_gains or estimate_minimum_gain -- with the diagnostic keep switch on: returns (its result, or
+    the JtkError it raised; gains_batches()).  A test hook: the switch is off again, and nothing is kept, when this returns."""
+    L = ffi.lib()
+    L.jtk_lc_debug_gains_keep(1)
+    try:
+        try:
+            res = call(*args, **kw)
+        except ffi.JtkError as e:
+            res = e
+        return res, gains_batches()
+    finally:
+        L.jtk_lc_debug_gains_keep(0)
+
+
 def fit_model(params, batch, rounds=10, device=0):
     """jtk_lc_fit_model: the model refit of the stage preamble (model_tune.rs:119-152) on the training pile-ups `batch`;
     returns (forward, reverse)."""

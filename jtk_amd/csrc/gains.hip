@@ -24,6 +24,7 @@
 
 #include "device_common.h"
 #include "host_common.h"
+#include "jtk_lc_debug.h"
 
 namespace {
 
@@ -140,6 +141,7 @@ struct PairMeta {
 };
 #define EDIT_MAX_LEN 250  // distances fit a byte
 #define EDIT_OPS_STRIDE 512
+static_assert(EDIT_OPS_STRIDE == JTK_LC_DEBUG_GAINS_OPS_STRIDE, "jtk_lc_debug.h states the stride of the kept ops");
 
 // Global unit-cost alignment of one (template, read) pair per wavefront; ties resolve diagonal, then Del, then Ins
 // on the traceback from the end (the stand-in for kiley's bootstrap alignment, oracle/phmm.c jo_edit_ops).
@@ -214,6 +216,32 @@ int device_edit_ops(const std::vector<PairMeta> &pairs, const std::vector<uint8_
     JTK_HIP_TRY(hipMemcpy(ops.data(), d_ops.p, ops.size(), hipMemcpyDeviceToHost));
     JTK_HIP_TRY(hipMemcpy(ops_len.data(), d_len.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     return 0;
+}
+
+// ---- diagnostic (include/jtk_lc_debug.h): the batches of this thread's last call, as the device saw and left them
+struct KeptGainsBatch {
+    std::vector<uint8_t> tmpl, reads, ops;
+    std::vector<uint64_t> tmpl_off, read_off;
+    std::vector<uint32_t> ops_len;
+    std::vector<double> lk;
+};
+thread_local bool g_keep_gains = false;
+thread_local std::vector<KeptGainsBatch> g_kept_gains;
+
+void keep_gains_batch(const std::vector<jtk_lc_chunk_t> &chunks, const std::vector<uint8_t> &tb, const std::vector<uint8_t> &rb,
+                      const std::vector<uint64_t> &roff, const std::vector<uint8_t> &ops_strided,
+                      const std::vector<uint32_t> &ops_len, const std::vector<double> &lk) {
+    if (!g_keep_gains) return;
+    g_kept_gains.emplace_back();
+    KeptGainsBatch &k = g_kept_gains.back();
+    k.tmpl = tb;
+    k.reads = rb;
+    k.ops = ops_strided;
+    k.read_off = roff;
+    k.ops_len = ops_len;
+    k.lk = lk;
+    for (const jtk_lc_chunk_t &c : chunks) k.tmpl_off.push_back(c.tmpl_off);
+    k.tmpl_off.push_back(tb.size());
 }
 
 double nth(std::vector<double> xs, size_t k) {  // select_nth_unstable_by(k).1: the k-th smallest
@@ -324,6 +352,7 @@ int gains_of(const jtk_lc_params_t &params, uint64_t seed, uint32_t seq_len, uin
     rc = jtk_internal_likelihoods(&params, n_chunks, chunks.data(), tb.data(), rb.data(), roff.data(), ops.data(), ooff.data(),
                                   strand.data(), band, device, lk.data());
     if (rc) return rc;
+    keep_gains_batch(chunks, tb, rb, roff, ops_strided, ops_len, lk);
     // ---- host: likelihood_gains.rs:276-314, per profile
     for (size_t q = 0; q < jobs.size(); q++) {
         const double *lkq = lk.data() + q * chunks_per_job * per;
@@ -419,6 +448,7 @@ int minimum_gain_batch(const jtk_lc_params_t &params, uint64_t seed, size_t s0, 
     rc = jtk_internal_likelihoods(&params, n_chunks, chunks.data(), tb.data(), rb.data(), roff.data(), ops.data(), ooff.data(),
                                   strand.data(), band, device, lk.data());
     if (rc) return rc;
+    keep_gains_batch(chunks, tb, rb, roff, ops_strided, ops_len, lk);
     for (size_t i = 0; i < ns; i++) {
         std::vector<double> d(seq_num);
         for (uint32_t t = 0; t < seq_num; t++) d[t] = lk[(2 * i) * seq_num + t] - lk[(2 * i + 1) * seq_num + t];
@@ -436,6 +466,7 @@ extern "C" {
 int jtk_lc_estimate_minimum_gain(const jtk_hmm_t *forward, const jtk_hmm_t *reverse, uint64_t seed, uint32_t sample_num,
                                  uint32_t seq_num, uint32_t len, uint32_t band, double *out, int device) {
     g_last_error.clear();
+    g_kept_gains.clear();
     if (!forward || !reverse || !out || sample_num < 3 || seq_num == 0 || len < 2 || len > 200 || band == 0 ||
         band > JTK_MAX_RADIUS)
         return jtk_fail(JTK_ERR_INVALID_ARG,
@@ -464,6 +495,7 @@ int jtk_lc_estimate_minimum_gain(const jtk_hmm_t *forward, const jtk_hmm_t *reve
 int jtk_lc_estimate_gains(const jtk_hmm_t *forward, const jtk_hmm_t *reverse, uint64_t seed, uint32_t seq_len,
                           uint32_t band, uint32_t homop_len, jtk_gains_t *out, int device) {
     g_last_error.clear();
+    g_kept_gains.clear();
     if (!forward || !reverse || !out || homop_len == 0 || homop_len > JTK_GAINS_MAX_HOMOP || seq_len < 2 || band == 0 ||
         band > JTK_MAX_RADIUS)
         return jtk_fail(JTK_ERR_INVALID_ARG, "jtk_lc_estimate_gains: bad argument (1 <= homop_len <= 8, 1 <= band <= 30)");
@@ -492,6 +524,34 @@ int jtk_lc_estimate_gains(const jtk_hmm_t *forward, const jtk_hmm_t *reverse, ui
         const int rc = gains_of(params, seed, seq_len, band, jobs, device);
         if (rc) return rc;
     }
+    return 0;
+}
+
+void jtk_lc_debug_gains_keep(int on) {
+    g_keep_gains = on != 0;
+    if (!g_keep_gains) g_kept_gains.clear();
+}
+size_t jtk_lc_debug_gains_batches(void) { return g_kept_gains.size(); }
+int jtk_lc_debug_gains_batch_sizes(size_t batch, uint64_t *sizes) {
+    if (batch >= g_kept_gains.size() || !sizes) return JTK_ERR_INVALID_ARG;
+    const KeptGainsBatch &k = g_kept_gains[batch];
+    sizes[0] = k.tmpl_off.size() - 1;
+    sizes[1] = k.tmpl.size();
+    sizes[2] = k.lk.size();
+    sizes[3] = k.reads.size();
+    return 0;
+}
+int jtk_lc_debug_gains_batch(size_t batch, uint8_t *tmpl, uint64_t *tmpl_off, uint8_t *reads, uint64_t *read_off, uint8_t *ops,
+                             uint32_t *ops_len, double *lk) {
+    if (batch >= g_kept_gains.size()) return JTK_ERR_INVALID_ARG;
+    const KeptGainsBatch &k = g_kept_gains[batch];
+    if (tmpl && !k.tmpl.empty()) memcpy(tmpl, k.tmpl.data(), k.tmpl.size());
+    if (tmpl_off) memcpy(tmpl_off, k.tmpl_off.data(), k.tmpl_off.size() * 8);
+    if (reads && !k.reads.empty()) memcpy(reads, k.reads.data(), k.reads.size());
+    if (read_off) memcpy(read_off, k.read_off.data(), k.read_off.size() * 8);
+    if (ops && !k.ops.empty()) memcpy(ops, k.ops.data(), k.ops.size());
+    if (ops_len && !k.ops_len.empty()) memcpy(ops_len, k.ops_len.data(), k.ops_len.size() * 4);
+    if (lk && !k.lk.empty()) memcpy(lk, k.lk.data(), k.lk.size() * 8);
     return 0;
 }
 

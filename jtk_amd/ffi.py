@@ -91,6 +91,13 @@ EXPORTED_SYMBOLS = (
     "jtk_lc_last_error", "jtk_lc_version", "jtk_lc_device_ok", "jtk_lc_last_timing",
     "jtk_lc_session_create", "jtk_lc_session_run", "jtk_lc_session_fetch", "jtk_lc_session_destroy", "jtk_lc_session_trace",
 )
+# every symbol declared in include/jtk_lc_debug.h: diagnostic entry points, not part of the drop-in boundary
+DEBUG_SYMBOLS = (
+    "jtk_lc_debug_cc_keep_sims", "jtk_lc_debug_cc_first_sims", "jtk_lc_debug_cc_sims_count", "jtk_lc_debug_cc_sims",
+    "jtk_lc_debug_chain_profile", "jtk_lc_debug_purge_timing",
+    "jtk_lc_debug_gains_keep", "jtk_lc_debug_gains_batches", "jtk_lc_debug_gains_batch_sizes", "jtk_lc_debug_gains_batch",
+)
+DEBUG_GAINS_OPS_STRIDE = 512   # JTK_LC_DEBUG_GAINS_OPS_STRIDE
 SYNTH_SYMBOLS = ("jtk_synth_pileup",)
 
 
@@ -172,6 +179,10 @@ def lib():
     sig("jtk_lc_session_fetch", i32, vp, PU32, PD, vp, PU8, PU64, u64, PU8, PU64, u64)
     sig("jtk_lc_session_destroy", i32, vp)
     sig("jtk_lc_session_trace", i32, vp, sz, C.c_char_p, sz, C.POINTER(sz))
+    sig("jtk_lc_debug_gains_keep", None, i32)
+    sig("jtk_lc_debug_gains_batches", sz)
+    sig("jtk_lc_debug_gains_batch_sizes", i32, sz, PU64)
+    sig("jtk_lc_debug_gains_batch", i32, sz, PU8, PU64, PU8, PU64, PU8, PU32, PD)
     _lib = L
     return L
 

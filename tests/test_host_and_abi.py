@@ -39,7 +39,7 @@ def test_library_exports_nothing_but_the_declared_entry_points():
     out = subprocess.run(["nm", "-D", "--defined-only", ffi.LIB_PATH], stdout=subprocess.PIPE, text=True, check=True).stdout
     names = {ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-2] in "TDBRW"}
     debug = set(re.findall(r"\b(jtk_lc_debug_[a-z_0-9]+)\s*\(", re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "jtk_lc_debug.h")).read(), flags=re.S)))
-    assert debug, "jtk_lc_debug.h declares the diagnostic entry points"
+    assert debug == set(ffi.DEBUG_SYMBOLS), "jtk_lc_debug.h declares the diagnostic entry points that ffi.DEBUG_SYMBOLS lists"
     assert names == set(ffi.EXPORTED_SYMBOLS) | debug, sorted(names ^ (set(ffi.EXPORTED_SYMBOLS) | debug))
 
 

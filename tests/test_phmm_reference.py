@@ -145,9 +145,12 @@ def oracle_centers(ops, L, n):
 
 # ---- comparisons (the tolerances of the issue that asked for this file: lk 1e-11 relative, table - lk 1e-8, counts 1e-9)
 
+LK_RTOL = 1e-11   # (tests/test_gains_reference.py and tests/test_gpu_gains_reference.py take the bound on lk from here)
+
+
 def assert_table_matches(ref_tab, ref_lk, tab_minus_lk, lk, where=""):
     """ref_tab: log V [L + 1, 14] (sentinel for impossible edits); tab_minus_lk: the oracle's or the device's table - lk"""
-    assert abs(lk - ref_lk) <= 1e-11 * abs(ref_lk), (where, lk, ref_lk)
+    assert abs(lk - ref_lk) <= LK_RTOL * abs(ref_lk), (where, lk, ref_lk)
     fin = ref_tab > -1e299
     assert np.array_equal(fin, tab_minus_lk > -1e299), (where, np.argwhere(fin != (tab_minus_lk > -1e299))[:5])
     err = np.abs(tab_minus_lk[fin] - (ref_tab[fin] - ref_lk))
