@@ -467,6 +467,51 @@ JTK_LC_API int jtk_lc_purge_diverged(size_t n_reads, const uint64_t *node_off, c
                           uint8_t *post_keep, uint64_t *purged, size_t purged_cap, size_t *n_purged, double *read_err,
                           double *chunk_err, double *median_of_sqrt_err, int device);
 
+/* ---- correct_deletion's candidate search: the skeleton pile-up -------------------------------------------------------
+ * `ds.correct_deletion(..)` runs three times per pipeline run (cli/src/pipeline.rs:149,166,168).  In each of its up to 3 x 12
+ * rounds `correct_deletion_error` (encode/deletion_fill.rs:301-337) calls get_pileup (deletion_fill.rs:642-698) for every live
+ * read: the read's node skeleton against EVERY read's skeleton -- check_alignment_by_chunkmatch (:611-637),
+ * pairwise_alignment_gotoh (:738-827), the verdict of `alignment` (:707-725), the walk into per-slot insertion lists -- then
+ * mean_cov and ins_thr (:312-314) and check_insertion_head / _tail (:883-981), whose candidates try_encoding_head / _tail test
+ * against the sequence.  This call returns those candidates, all integers, bit for bit.  What follows a candidate stays the
+ * caller's: the failed-trial filter (:318,:328), encode_node (:451-528: jtk_lc_align_reads_mode in infix mode for
+ * fit_query_by_edlib, then kiley's infix_guided), remove_slippy_alignment, remove_overlapping_encoding.
+ *
+ * Read r's nodes are nodes[node_off[r] .. node_off[r+1]) in read order.  The query set is every read, the target included;
+ * `target` (NULL = every read) selects the reads that get output -- the reference's `is_alive` filter.  A read without nodes
+ * or with target[r] == 0 keeps zero coverage, ins_thr 0 and no candidate.
+ *   coverage[node_off[r] + r + slot]   Pileup.coverage of slot 0 ..= n of read r (slot n stays 0)
+ *   ins_thr[r]                         min(mean_cov / 5, 2), mean_cov = sum(coverage) / (n + 1)
+ *   cands[cand_off[r] .. cand_off[r+1]) sorted by (slot, side, chunk, cluster, is_forward): the keys whose entry count in the
+ *                                      slot's head (side 0) or tail (side 1) list is >= ins_thr and which carry an offset;
+ *                                      position = the value the reference's HashMap holds afterwards.  A head position is
+ *                                      written signed: a negative one is what wraps to a huge usize in the reference, and
+ *                                      `start_position < seq.len()` (:381) rejects it.
+ * The reference's arm `position == pileups.len() - 1` (:669) reads the length of the shadowing iterator, i.e. what REMAINS:
+ * it fires where 2 position + 1 == n, and at position == n the subtraction wraps (release build) and the general arm runs.
+ * That is restated as it stands.
+ * JTK_ERR_UNSUPPORTED: a read with more than 65,535 nodes.  JTK_ERR_INVALID_ARG with *n_cands = the need: cand_cap is too
+ * small.  Nothing else is written on failure. */
+typedef struct jtk_fill_node {      /* what ReadSkelton::from_rich_nodes reads of a Node (deletion_fill.rs:1003-1030) */
+    uint64_t chunk, cluster;        /* Node.chunk, Node.cluster */
+    uint32_t is_forward;            /* Node.is_forward */
+    uint32_t query_len;             /* Node.query_length() */
+    uint64_t position;              /* Node.position_from_start */
+} jtk_fill_node_t;
+typedef struct jtk_fill_cand {
+    uint32_t read, slot;            /* slot idx of get_pileup's vector, 0 ..= n_nodes(read) */
+    uint32_t side;                  /* 0 = check_insertion_head, 1 = check_insertion_tail */
+    uint32_t is_forward;
+    uint64_t chunk, cluster;        /* the LightNode key */
+    uint32_t count, reserved;       /* entries of that key in the slot's list (what `threshold <= *num` saw) */
+    int64_t  position;              /* the value the HashMap holds afterwards: start_position (head) / end_position (tail) */
+} jtk_fill_cand_t;
+JTK_LC_API int jtk_lc_fill_candidates(size_t n_reads, const uint64_t *node_off, const jtk_fill_node_t *nodes,
+        const uint8_t *target /* NULL = every read; else 1 = compute this read (the reference's `is_alive` filter) */,
+        uint32_t *coverage /* node_off[n_reads] + n_reads entries; read r's slots start at node_off[r] + r */,
+        uint32_t *ins_thr /* n_reads */, uint64_t *cand_off /* n_reads + 1 */, jtk_fill_cand_t *cands, size_t cand_cap,
+        size_t *n_cands, int device);
+
 /* Sort key of pileup_nodes (mod.rs:47-50): number of alignment columns that are not '|' in
  * Node::recover (definitions/src/lib.rs:773-813) for run-length cigar ops given per base. */
 JTK_LC_API int jtk_lc_pileup_sort_key(const uint8_t *tmpl, uint64_t tmpl_len, const uint8_t *read, uint64_t read_len,

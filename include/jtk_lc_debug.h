@@ -33,6 +33,18 @@ JTK_LC_API int jtk_lc_debug_chain_profile(jtk_lc_session_t *s, uint64_t *cycles,
  * (upload to the last copy back), and the passes of the fit. */
 JTK_LC_API void jtk_lc_debug_purge_timing(double *out);
 
+/* The aligner of jtk_lc_fill_candidates by itself: for pair p = (pair_target[p], pair_query[p]) of reads given as for that call,
+ * dir[p] = 1 forward, 0 reverse, -1 where check_alignment_by_chunkmatch rejects the pair or the target has no node (score and
+ * pass are then 0 and the pair has no ops); score[p] = pairwise_alignment_gotoh's; pass[p] = `alignment` returns Some; and the
+ * compressed ops at ops[ops_off[p] .. ops_off[p+1]) in alignment order, each len << 2 | code with code 0 = Match, 1 = Ins,
+ * 2 = Del.  JTK_ERR_INVALID_ARG with *n_ops = the need when ops_cap is too small. */
+JTK_LC_API int jtk_lc_debug_fill_pairs(size_t n_reads, const uint64_t *node_off, const jtk_fill_node_t *nodes, size_t n_pairs,
+                                       const uint32_t *pair_target, const uint32_t *pair_query, int32_t *dir, int32_t *score, uint8_t *pass,
+                                       uint64_t *ops_off, uint32_t *ops, size_t ops_cap, size_t *n_ops, int device);
+/* Of this thread's last jtk_lc_fill_candidates call, 4 doubles: the pairs aligned, the insertion records, the HIP-event time of
+ * the whole call on its stream in ms (upload to the last copy back) and of the pair kernels in ms. */
+JTK_LC_API void jtk_lc_debug_fill_timing(double *out);
+
 /* Keep (on != 0) what the device batches of the following jtk_lc_estimate_gains / jtk_lc_estimate_minimum_gain calls on this thread
  * held: while the switch is on, the last such call keeps, per batch and in batch order, the template and read bytes with their
  * offsets, the ops and their lengths exactly as edit_ops_kernel wrote them (JTK_LC_DEBUG_GAINS_OPS_STRIDE bytes per pair, before the

@@ -373,6 +373,70 @@ def purge_timing():
     return dict(upload_ms=out[0], walk_ms=out[1], device_ms=out[2], n_iter=int(out[3]))
 
 
+def _fill_reads(node_off, nodes):
+    nodes = np.ascontiguousarray(nodes, dtype=ffi.FILL_NODE_DT)
+    node_off = np.ascontiguousarray(node_off, dtype=np.uint64)
+    if len(node_off) == 0 or int(node_off[-1]) != len(nodes):
+        raise ValueError("node_off must hold n_reads + 1 offsets that end at len(nodes)")
+    return node_off, nodes
+
+
+def fill_candidates(node_off, nodes, target=None, device=0, cand_cap=None):
+    """jtk_lc_fill_candidates: get_pileup, ins_thr and check_insertion_head / _tail of correct_deletion
+    (encode/deletion_fill.rs:301-337, 642-698, 883-981) for the reads nodes[node_off[r] .. node_off[r+1]) (ffi.FILL_NODE_DT).
+    target: None, or per read 1 = compute it.  Returns dict(coverage, ins_thr, cand_off, cands): coverage flat with read r's
+    n + 1 slots at node_off[r] + r, cands (ffi.FILL_CAND_DT) in (read, slot, side, chunk, cluster, is_forward) order.  The
+    candidate array is grown once on the capacity reply (cand_cap: its first size, default one per node)."""
+    node_off, nodes = _fill_reads(node_off, nodes)
+    n_reads, n = len(node_off) - 1, len(nodes)
+    tgt = None
+    if target is not None:
+        tgt = np.ascontiguousarray(target, dtype=np.uint8)
+        if len(tgt) != n_reads:
+            raise ValueError("target must hold one entry per read")
+    coverage, ins_thr = np.zeros(n + n_reads + 1, dtype=np.uint32), np.zeros(n_reads + 1, dtype=np.uint32)
+    cand_off = np.zeros(n_reads + 1, dtype=np.uint64)
+    cap = n if cand_cap is None else int(cand_cap)
+    need = C.c_size_t(0)
+    L = ffi.lib()
+    for attempt in range(2):
+        cands = np.zeros(cap + 1, dtype=ffi.FILL_CAND_DT)
+        rc = L.jtk_lc_fill_candidates(n_reads, u64p(node_off), nodes.ctypes.data, None if tgt is None else u8p(tgt), u32p(coverage),
+                                      u32p(ins_thr), u64p(cand_off), cands.ctypes.data, cap, C.byref(need), device)
+        if rc == -1 and attempt == 0 and need.value > cap:
+            cap = need.value
+            continue
+        check(rc)
+        break
+    return dict(coverage=coverage[:n + n_reads], ins_thr=ins_thr[:n_reads], cand_off=cand_off, cands=cands[:need.value])
+
+
+def fill_pairs(node_off, nodes, pair_target, pair_query, device=0):
+    """jtk_lc_debug_fill_pairs (include/jtk_lc_debug.h): per (target, query) pair the direction (1 forward, 0 reverse, -1 = the
+    pre-filter rejects it), the score, the pass flag and the compressed ops as a list of (code, length)."""
+    node_off, nodes = _fill_reads(node_off, nodes)
+    pt, pq = np.ascontiguousarray(pair_target, dtype=np.uint32), np.ascontiguousarray(pair_query, dtype=np.uint32)
+    n_pairs = len(pt)
+    length = np.diff(node_off.astype(np.int64))
+    cap = int(sum(int(length[t]) + int(length[q]) + 2 for t, q in zip(pt, pq) if t < len(length) and q < len(length)))
+    direction, score = np.zeros(n_pairs + 1, dtype=np.int32), np.zeros(n_pairs + 1, dtype=np.int32)
+    passed, ops_off, ops = np.zeros(n_pairs + 1, dtype=np.uint8), np.zeros(n_pairs + 1, dtype=np.uint64), np.zeros(cap + 1, dtype=np.uint32)
+    n_ops = C.c_size_t(0)
+    check(ffi.lib().jtk_lc_debug_fill_pairs(len(node_off) - 1, u64p(node_off), nodes.ctypes.data, n_pairs, u32p(pt), u32p(pq),
+                                            direction.ctypes.data_as(C.POINTER(C.c_int32)), score.ctypes.data_as(C.POINTER(C.c_int32)),
+                                            u8p(passed), u64p(ops_off), u32p(ops), cap, C.byref(n_ops), device))
+    runs = [[(int(o) & 3, int(o) >> 2) for o in ops[int(ops_off[p]):int(ops_off[p + 1])]] for p in range(n_pairs)]
+    return dict(dir=direction[:n_pairs], score=score[:n_pairs], passed=passed[:n_pairs], ops=runs)
+
+
+def fill_timing():
+    """jtk_lc_debug_fill_timing (include/jtk_lc_debug.h): pairs aligned, insertion records, device ms and pair-kernel ms of the
+    last fill_candidates call"""
+    out = (C.c_double * 4)()
+    ffi.lib().jtk_lc_debug_fill_timing(out)
+    return dict(n_pairs=int(out[0]), n_records=int(out[1]), device_ms=out[2], pair_ms=out[3])
+
+
 def correct_clustering_with_sims(*args, **kw):
     """correct_clustering with the diagnostic switch of include/jtk_lc_debug.h on: returns (cluster, touched, sims), sims = the
     raw similarity matrix (before filter_similarity) of every corrected chunk, in selected_chunks order.  A test hook: the

@@ -485,6 +485,37 @@ def purge_diverged_nodes(ds, device=0, thr=0.1):
 _COMPLEMENT = {"A": "T", "C": "G", "G": "C", "T": "A"}
 
 
+def fill_candidates(ds, alive=None, device=0):
+    """The candidate search of correct_deletion (encode/deletion_fill.rs:301-337: get_pileup, ins_thr, check_insertion_head /
+    _tail) on encoded_reads[*].nodes, query_length taken from the cigar as Node::query_length does.  alive: None, or the ids of
+    the reads to compute (the reference's `is_alive` filter).  Returns a list, one entry per computed read with a node, in read
+    order: {"id", "ins_thr", "coverage": [n + 1], "candidates": [{"slot", "side": "head" | "tail", "chunk", "cluster",
+    "is_forward", "count", "position"}]}.  What the reference does with a candidate (encode_node with kiley's infix_guided,
+    remove_slippy_alignment, remove_overlapping_encoding) is not part of this: the data set is not changed."""
+    reads = ds["encoded_reads"]
+    node_off = np.zeros(len(reads) + 1, dtype=np.uint64)
+    flat = []
+    for r, read in enumerate(reads):
+        flat += [(n["chunk"], n["cluster"], int(bool(n["is_forward"])), query_length(n), n["position_from_start"]) for n in read["nodes"]]
+        node_off[r + 1] = len(flat)
+    nodes = np.array(flat, dtype=ffi.FILL_NODE_DT) if flat else np.zeros(0, dtype=ffi.FILL_NODE_DT)
+    ids = None if alive is None else set(alive)
+    target = None if ids is None else np.array([read["id"] in ids for read in reads], dtype=np.uint8)
+    out = api.fill_candidates(node_off, nodes, target=target, device=device)
+    report = []
+    for r, read in enumerate(reads):
+        if not read["nodes"] or (target is not None and not target[r]):
+            continue
+        b = int(node_off[r]) + r
+        cands = out["cands"][int(out["cand_off"][r]):int(out["cand_off"][r + 1])]
+        report.append({"id": read["id"], "ins_thr": int(out["ins_thr"][r]),
+                       "coverage": [int(x) for x in out["coverage"][b:b + len(read["nodes"]) + 1]],
+                       "candidates": [{"slot": int(c["slot"]), "side": "tail" if c["side"] else "head", "chunk": int(c["chunk"]),
+                                       "cluster": int(c["cluster"]), "is_forward": bool(c["is_forward"]), "count": int(c["count"]),
+                                       "position": int(c["position"])} for c in cands]})
+    return report
+
+
 def recover_raw_read(read):
     """EncodedRead::recover_raw_read (definitions/src/lib.rs:604-619): leading gap, then every node's original sequence
     (Node::original_seq :737-753: reverse complement of a reverse node; anything but ACGT panics) with the overlap of a
@@ -553,12 +584,15 @@ def correct_clustering(ds, device=0, min_gain=None):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--stage", default="local_clustering", choices=("local_clustering", "correct_clustering", "squish_erroneous_clusters", "corrected", "realign", "purge_diverged_nodes"),
+    ap.add_argument("--stage", default="local_clustering", choices=("local_clustering", "correct_clustering", "squish_erroneous_clusters", "corrected", "realign", "purge_diverged_nodes", "fill_candidates"),
                     help="which JTK stage to run on the file (jtk local_clustering / jtk correct_clustering); "
                          "squish_erroneous_clusters: the step JTK runs in front of the correction, with its default "
                          "configuration; corrected: that step, then correct_clustering (cli/src/pipeline.rs:174-175); realign: "
                          "replace every node's cigar by its global alignment to the chunk sequence; purge_diverged_nodes: the first "
-                         "half of `ds.purge` (purge_diverged.rs:238-322), the purged chunk ids go to stderr")
+                         "half of `ds.purge` (purge_diverged.rs:238-322), the purged chunk ids go to stderr; fill_candidates: the "
+                         "candidate search of correct_deletion (deletion_fill.rs:301-337) -- the output is a REPORT, a JSON list "
+                         "keyed by read id with coverage, ins_thr and the head / tail candidates, not a DataSet: testing a "
+                         "candidate against the sequence (encode_node, kiley's infix_guided) is JTK's")
     ap.add_argument("input", help="DataSet JSON ('-' = stdin)")
     ap.add_argument("output", help="DataSet JSON ('-' = stdout)")
     ap.add_argument("--chunks", default="", help="comma-separated chunk ids (local_clustering_selected); default: all")
@@ -592,6 +626,8 @@ def main(argv=None):
         sys.stderr.write("PD\tPurged\t%s\n" % ",".join(str(x) for x in purged))
         if args.recluster and purged:
             local_clustering_selected(ds, purged, device=args.device, failed=failed, refit=not args.no_refit, record=record, trace=trace)
+    elif args.stage == "fill_candidates":
+        ds = fill_candidates(ds, device=args.device)   # the report takes the data set's place in the output
     elif args.stage == "correct_clustering":
         validate(ds)
         if args.chunks:

@@ -83,18 +83,23 @@ FEATURE_CHUNK_DT = np.dtype([("chunk_id", "<u8"), ("copy_num", "<u4"), ("n_reads
 
 CC_NODE_DT = np.dtype([("chunk", "<u8"), ("cluster", "<u8"), ("is_forward", "<u4"), ("post_len", "<u4"), ("post_off", "<u8")])
 CC_CHUNK_DT = np.dtype([("id", "<u8"), ("cluster_num", "<u4"), ("copy_num", "<u4"), ("score", "<f8")])
+# jtk_fill_node_t / jtk_fill_cand_t (jtk_lc_fill_candidates)
+FILL_NODE_DT = np.dtype([("chunk", "<u8"), ("cluster", "<u8"), ("is_forward", "<u4"), ("query_len", "<u4"), ("position", "<u8")])
+FILL_CAND_DT = np.dtype([("read", "<u4"), ("slot", "<u4"), ("side", "<u4"), ("is_forward", "<u4"), ("chunk", "<u8"), ("cluster", "<u8"),
+                         ("count", "<u4"), ("reserved", "<u4"), ("position", "<i8")])
+FILL_MATCH, FILL_INS, FILL_DEL = 0, 1, 2   # op codes of jtk_lc_debug_fill_pairs
 
 # every symbol declared in include/jtk_lc.h (tests check the library exports them)
 EXPORTED_SYMBOLS = (
     "jtk_lc_cluster_chunks", "jtk_lc_cluster_chunks_multi", "jtk_lc_cluster_polished", "jtk_lc_polish_chunks", "jtk_lc_align_reads", "jtk_lc_align_reads_mode", "jtk_lc_modification_table",
-    "jtk_lc_cluster_features", "jtk_lc_estimate_gains", "jtk_lc_estimate_minimum_gain", "jtk_lc_fit_model", "jtk_lc_correct_clustering", "jtk_lc_squish_clusters", "jtk_lc_squish_classify", "jtk_lc_node_errors", "jtk_lc_error_quantile", "jtk_lc_estimate_error_rate", "jtk_lc_purge_diverged", "jtk_lc_trim_cache", "jtk_lc_pileup_sort_key", "jtk_lc_normalize_pileup", "jtk_lc_strerror",
+    "jtk_lc_cluster_features", "jtk_lc_estimate_gains", "jtk_lc_estimate_minimum_gain", "jtk_lc_fit_model", "jtk_lc_correct_clustering", "jtk_lc_squish_clusters", "jtk_lc_squish_classify", "jtk_lc_node_errors", "jtk_lc_error_quantile", "jtk_lc_estimate_error_rate", "jtk_lc_purge_diverged", "jtk_lc_fill_candidates", "jtk_lc_trim_cache", "jtk_lc_pileup_sort_key", "jtk_lc_normalize_pileup", "jtk_lc_strerror",
     "jtk_lc_last_error", "jtk_lc_version", "jtk_lc_device_ok", "jtk_lc_last_timing",
     "jtk_lc_session_create", "jtk_lc_session_run", "jtk_lc_session_fetch", "jtk_lc_session_destroy", "jtk_lc_session_trace",
 )
 # every symbol declared in include/jtk_lc_debug.h: diagnostic entry points, not part of the drop-in boundary
 DEBUG_SYMBOLS = (
     "jtk_lc_debug_cc_keep_sims", "jtk_lc_debug_cc_first_sims", "jtk_lc_debug_cc_sims_count", "jtk_lc_debug_cc_sims",
-    "jtk_lc_debug_chain_profile", "jtk_lc_debug_purge_timing",
+    "jtk_lc_debug_chain_profile", "jtk_lc_debug_purge_timing", "jtk_lc_debug_fill_pairs", "jtk_lc_debug_fill_timing",
     "jtk_lc_debug_gains_keep", "jtk_lc_debug_gains_batches", "jtk_lc_debug_gains_batch_sizes", "jtk_lc_debug_gains_batch",
 )
 DEBUG_GAINS_OPS_STRIDE = 512   # JTK_LC_DEBUG_GAINS_OPS_STRIDE
@@ -164,6 +169,9 @@ def lib():
     sig("jtk_lc_estimate_error_rate", i32, sz, PU64, vp, PU32, PU32, sz, vp, C.c_double, PD, PD, PU64, sz, PD, PU32, i32)
     sig("jtk_lc_purge_diverged", i32, sz, PU64, vp, sz, sz, vp, PU8, PU64, PU8, PU64, PU8, PU64, C.c_double, PU8, PU64, sz, PU8, PU64,
         PU8, PU8, PU64, sz, PSZ, PD, PD, PD, i32)
+    sig("jtk_lc_fill_candidates", i32, sz, PU64, vp, PU8, PU32, PU32, PU64, vp, sz, PSZ, i32)
+    sig("jtk_lc_debug_fill_pairs", i32, sz, PU64, vp, sz, PU32, PU32, PI32, PI32, PU8, PU64, PU32, sz, PSZ, i32)
+    sig("jtk_lc_debug_fill_timing", None, PD)
     sig("jtk_lc_trim_cache", i32, i32)
     sig("jtk_lc_cluster_features", i32, PP, sz, vp, PD, PU32, PU32, PD, u32, vp, i32)
     sig("jtk_lc_pileup_sort_key", i32, PU8, u64, PU8, u64, PU8, u64, PU64)

@@ -48,6 +48,17 @@ pub struct JtkCcChunk {
 pub struct JtkSquishConfig {
     pub ari_thr: f64, pub match_score: f64, pub mismatch_score: f64, pub count_thr: u64,
 }
+// what ReadSkelton::from_rich_nodes reads of a Node (encode/deletion_fill.rs:1003-1030), and one candidate of
+// check_insertion_head (side 0) / check_insertion_tail (side 1) (:940-981)
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct JtkFillNode {
+    pub chunk: u64, pub cluster: u64, pub is_forward: u32, pub query_len: u32, pub position: u64,
+}
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct JtkFillCand {
+    pub read: u32, pub slot: u32, pub side: u32, pub is_forward: u32, pub chunk: u64, pub cluster: u64,
+    pub count: u32, pub reserved: u32, pub position: i64,
+}
 
 extern "C" {
     pub fn jtk_lc_cluster_chunks(
@@ -134,6 +145,12 @@ extern "C" {
         thr: f64, diverged: *mut u8, chunk_err_off: *mut u64, slot_cap: usize, keep: *mut u8, cluster_out: *mut u64,
         touched: *mut u8, post_keep: *mut u8, purged: *mut u64, purged_cap: usize, n_purged: *mut usize,
         read_err: *mut f64, chunk_err: *mut f64, median_of_sqrt_err: *mut f64, device: c_int) -> c_int;
+    // get_pileup, ins_thr and check_insertion_head / _tail of correct_deletion_error (encode/deletion_fill.rs:301-337, 642-698,
+    // 883-981) for every read with target[r] == 1 (null: every read); cands sorted by (read, slot, side, chunk, cluster, is_forward)
+    pub fn jtk_lc_fill_candidates(
+        n_reads: usize, node_off: *const u64, nodes: *const JtkFillNode, target: *const u8, coverage: *mut u32,
+        ins_thr: *mut u32, cand_off: *mut u64, cands: *mut JtkFillCand, cand_cap: usize, n_cands: *mut usize,
+        device: c_int) -> c_int;
     // the resident-batch form (jtk_lc.h: session_create + run + fetch == jtk_lc_cluster_chunks) and, on it, the reference's
     // trace! rows of one chunk (TOTAL / CAND / PICK / DUMP / RANGE / LK / COUNTS; pseudo_mcmc.rs:122-127,236,250-262,467-472,539)
     pub fn jtk_lc_session_create(

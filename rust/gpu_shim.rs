@@ -161,6 +161,39 @@ pub(crate) fn purge_gpu(ds: &mut definitions::DataSet, thr: f64) -> std::collect
     purged[..n_purged].iter().copied().collect()                     // what `purge` hands to re_cluster (:47)
 }
 
+/// One inner round of `filling_until` (encode/deletion_fill.rs:186-212) asks this once, in place of the get_pileup (:642-698) and
+/// the check_insertion_head / _tail calls (:317,:327) of every live read: per read index, its candidates as
+/// (slot, side, LightNode key, position), side 0 = head, 1 = tail.  `correct_deletion_error` then goes on from :318 as it stands
+/// with them: the failed-trial filter, try_encoding_head / _tail (fit_query_by_edlib through jtk_lc_align_reads_mode in infix
+/// mode, kiley's infix_guided on the host), remove_slippy_alignment, remove_overlapping_encoding.  `alive[r]` = the filter of
+/// :196, `!r.nodes.is_empty() && t.is_alive`; the skeletons are those of the reads as they stand at the start of the round,
+/// which is what `read_skeltons` holds after updates_reads (:204).
+pub(crate) fn fill_candidates_gpu(reads: &[definitions::EncodedRead], alive: &[bool])
+    -> Vec<Vec<(usize, u32, (u64, u64, bool), isize)>> {
+    let (mut node_off, mut nodes) = (vec![0u64], vec![]);
+    for read in reads.iter() {
+        nodes.extend(read.nodes.iter().map(|n| JtkFillNode { chunk: n.chunk, cluster: n.cluster, is_forward: n.is_forward as u32,
+            query_len: n.query_length() as u32, position: n.position_from_start as u64 }));
+        node_off.push(nodes.len() as u64);
+    }
+    let target: Vec<u8> = alive.iter().map(|&a| a as u8).collect();
+    let (mut coverage, mut ins_thr) = (vec![0u32; nodes.len() + reads.len()], vec![0u32; reads.len()]);
+    let (mut cand_off, mut cands, mut n_cands) = (vec![0u64; reads.len() + 1], vec![JtkFillCand::default(); nodes.len()], 0usize);
+    for _ in 0..2 {   // once more with the capacity the first reply names
+        let rc = unsafe { jtk_lc_fill_candidates(reads.len(), node_off.as_ptr(), nodes.as_ptr(), target.as_ptr(),
+            coverage.as_mut_ptr(), ins_thr.as_mut_ptr(), cand_off.as_mut_ptr(), cands.as_mut_ptr(), cands.len(), &mut n_cands,
+            /*device*/ 0) };
+        if rc == -1 && n_cands > cands.len() {
+            cands.resize(n_cands, JtkFillCand::default());
+            continue;
+        }
+        assert!(rc == 0, "{}", unsafe { std::ffi::CStr::from_ptr(jtk_lc_last_error()) }.to_string_lossy());
+        break;
+    }
+    (0..reads.len()).map(|r| cands[cand_off[r] as usize..cand_off[r + 1] as usize].iter()
+        .map(|c| (c.slot as usize, c.side, (c.chunk, c.cluster, c.is_forward == 1), c.position as isize)).collect()).collect()
+}
+
 fn to_ffi(h: &kiley::hmm::PairHiddenMarkovModel) -> JtkHmm {
     let d = crate::model_tune::kiley_into_def(h);                  // model_tune.rs:65-92
     JtkHmm { mat_mat: d.mat_mat, mat_ins: d.mat_ins, mat_del: d.mat_del, ins_mat: d.ins_mat, ins_ins: d.ins_ins,
