@@ -474,8 +474,8 @@ JTK_LC_API int jtk_lc_purge_diverged(size_t n_reads, const uint64_t *node_off, c
  * pairwise_alignment_gotoh (:738-827), the verdict of `alignment` (:707-725), the walk into per-slot insertion lists -- then
  * mean_cov and ins_thr (:312-314) and check_insertion_head / _tail (:883-981), whose candidates try_encoding_head / _tail test
  * against the sequence.  This call returns those candidates, all integers, bit for bit.  What follows a candidate stays the
- * caller's: the failed-trial filter (:318,:328), encode_node (:451-528: jtk_lc_align_reads_mode in infix mode for
- * fit_query_by_edlib, then kiley's infix_guided), remove_slippy_alignment, remove_overlapping_encoding.
+ * caller's: the failed-trial filter (:318,:328), remove_slippy_alignment, remove_overlapping_encoding; encode_node
+ * (:451-566) is jtk_lc_encode_nodes below.
  *
  * Read r's nodes are nodes[node_off[r] .. node_off[r+1]) in read order.  The query set is every read, the target included;
  * `target` (NULL = every read) selects the reads that get output -- the reference's `is_alive` filter.  A read without nodes
@@ -511,6 +511,94 @@ JTK_LC_API int jtk_lc_fill_candidates(size_t n_reads, const uint64_t *node_off, 
         uint32_t *coverage /* node_off[n_reads] + n_reads entries; read r's slots start at node_off[r] + r */,
         uint32_t *ins_thr /* n_reads */, uint64_t *cand_off /* n_reads + 1 */, jtk_fill_cand_t *cands, size_t cand_cap,
         size_t *n_cands, int device);
+
+/* ---- banded affine-gap alignment along a guide path --------------------------------------------------------------
+ * What the reference gets from kiley::bialignment::guided (`global_guided`, `infix_guided`): an alignment that already
+ * exists (an edlib alignment of jtk_lc_align_reads*, an earlier pass of this call) is refined under affine gap scores inside
+ * a band of `radius` cells around its path.  Call sites: encode/deletion_fill.rs:526,553-554 (infix, radius = band, scores
+ * (2, -6, -5, -1)), dense_encoding.rs:757, determine_chunks.rs:538, consensus/mod.rs:560,1231-1233,1259-1261 (global).
+ * kiley is not part of the reference tree: the aligner follows THIS build's specification, DESIGN.md section 4 ("Guided
+ * alignment"), and parity with kiley's band shape and its choice among equally good alignments is NOT pinned.  In short:
+ * the guide is walked from (0, 0) (ops that do not fit are skipped, a short guide goes on diagonally, then by Del, then by
+ * Ins); row i of the band holds the columns within `radius` of the path's columns in that row; three states M, D, I per cell,
+ * a gap of length L costs gap_open + (L - 1) gap_ext; ties go to the first of M, D, I, in the end cell and at every step
+ * back.  mode = JTK_ALIGN_INFIX frees both ends of x: M(i, 0) = 0 in every row the band reaches, the end is the best
+ * (i, |y|), the smallest i on a tie, and the walk back stops the first time it is in M at column 0.
+ * A pair indexes two base buffers and one op buffer, so that many pairs can share a sequence:
+ *   x      the sequence whose ends may be free; Del (3) consumes an x base
+ *   y      the sequence that is consumed whole; Ins (2) consumes a y base
+ * Output per pair: score_out, the stretch [start_out, end_out) of x that was aligned (global: 0, x_len), status, and the ops at
+ * ops_out[ops_out_off[p] .. ops_out_off[p+1]) (capacity ops_cap bytes; sum(x_len + y_len) is always enough).  The ops of
+ * either mode consume both sequences whole -- infix: start x Del, the path, (x_len - end) x Del -- Match and Mismatch are
+ * told apart, and the score leaves the free runs out.  Empty sequences are valid input.
+ * JTK_ERR_INVALID_ARG: a base that is not ACGT, a guide op above 3, a mode other than GLOBAL / INFIX, scores outside
+ * gap_open <= gap_ext <= 0, mismatch <= 0 <= match, or one above JTK_GUIDED_MAX_SCORE in magnitude (the table is 32-bit).
+ * Limits, per pair (status[p] = JTK_ERR_UNSUPPORTED, no ops, the rest of the batch is aligned and the call returns
+ * JTK_ERR_CHUNK_FAILED): 32,000 bases per sequence, and JTK_GUIDED_MAX_WIDTH cells in one row of the band (2 radius + 1 plus
+ * the columns the path itself spans in that row). */
+#define JTK_GUIDED_MAX_WIDTH 4096
+#define JTK_GUIDED_MAX_SCORE 1024
+typedef struct jtk_guided_pair {
+    uint64_t x_off, y_off;          /* first base in x_bases / y_bases */
+    uint64_t guide_off;             /* first op in guide_ops */
+    uint32_t x_len, y_len, guide_len;
+    uint32_t radius;
+} jtk_guided_pair_t;
+JTK_LC_API int jtk_lc_align_guided(size_t n_pairs, const jtk_guided_pair_t *pairs, const uint8_t *x_bases, const uint8_t *y_bases,
+                        const uint8_t *guide_ops, int mode, int match, int mismatch, int gap_open, int gap_ext,
+                        uint8_t *ops_out, uint64_t *ops_out_off, uint64_t ops_cap, int32_t *score_out, uint32_t *start_out,
+                        uint32_t *end_out, int32_t *status, int device);
+
+/* ---- correct_deletion's trial of a candidate: encode_node, batched ------------------------------------------------------
+ * `encode_node` with `fine_mapping` and `fit_query_by_edlib` (encode/deletion_fill.rs:451-566) for a batch of trials, as it
+ * stands.  Trial t lays the consensus cons_bases[cons_off .. + cons_len) of a (chunk, cluster) into the window
+ * read_bases[read_off + start .. read_off + end) of a raw read (reverse-complemented when is_forward == 0, upper-cased), and
+ * then the chunk's own sequence chunk_bases[chunk_off .. + chunk_len) onto what is left of the window:
+ *   1. sim_thr < (cons_len -. (end - start)) / cons_len in f64 (:461-465, saturating subtraction): verdict 1, nothing else runs;
+ *   2. the edlib infix alignment of the consensus into the window (jtk_lc_align_reads_mode), padded at both ends with ops
+ *      that consume the window (:546-550); band = max(ceil(window_len * sim_thr * 0.3), 10) (:552);
+ *   3. two passes of jtk_lc_align_guided's infix aligner, x = window, y = consensus, scores (2, -6, -5, -1) (:553-554);
+ *   4. Ins and Del swapped, the window-consuming runs at both ends trimmed (:556-564): trim_head, trim_tail, and the query
+ *      = window[trim_head .. window_len - trim_tail);
+ *   5. mat_num, ops_len and edge_identity's four counts with EDGE_LEN = 100 (:501-503, :568-592);
+ *   6. the third pass, infix, x = the chunk's sequence, y = the query, the same band (:526): its score and ops are the node's;
+ *   7. verdict 0 when 1 - sim_thr < mat_num / ops_len && 0.5 < min(head_match / head_len, tail_match / tail_len), else 2
+ *      (:504-505; f64: a 0 / 0 identity is NaN and rejects, and f64::min hands back the other operand where one edge is NaN).
+ *      The reference runs 6 only for verdict 0; here it runs for every trial that passed 1 and the host applies 7 afterwards.
+ * The guided passes follow this build's specification (see jtk_lc_align_guided): parity with kiley is NOT pinned.
+ * result[t]: status (0; JTK_ERR_UNSUPPORTED where the infix alignment or a guided pass refuses the trial -- verdict is then 2 and
+ * the call returns JTK_ERR_CHUNK_FAILED after finishing the rest), verdict, trim_head, trim_tail, position_from_start = start +
+ * (is_forward ? trim_head : trim_tail) (:477-480), query_len, band, score and the counts; the third pass's ops at
+ * ops_out[ops_out_off[t] .. ops_out_off[t+1]) (sum(chunk_len + end - start) bytes are always enough).  The caller runs
+ * kiley_op_to_ops on them, takes `seq` from the window and keeps max_by_key(score) over a slot's accepted trials.
+ * JTK_ERR_INVALID_ARG: start >= end (the reference asserts), an empty consensus or chunk sequence, a base that is not ACGT after
+ * upper-casing. */
+typedef struct jtk_encode_trial {
+    uint64_t read_off;              /* the read's first base in read_bases */
+    uint32_t start, end;            /* the window, in bases of the read */
+    uint32_t is_forward;
+    uint32_t cons_len;
+    uint64_t cons_off;              /* into cons_bases */
+    uint64_t chunk_off;             /* into chunk_bases: Chunk.seq() */
+    uint32_t chunk_len;
+    uint32_t reserved;
+    double sim_thr;                 /* error_rate_bound (:400, :442) */
+} jtk_encode_trial_t;
+enum jtk_encode_verdict { JTK_ENCODE_ACCEPTED = 0, JTK_ENCODE_LOWER_BOUND = 1, JTK_ENCODE_REJECTED = 2 };
+typedef struct jtk_encode_result {
+    int32_t status;
+    uint32_t verdict;
+    uint32_t trim_head, trim_tail;
+    uint64_t position_from_start;
+    uint32_t query_len, band;
+    int32_t score;
+    uint32_t mat_num, ops_len;      /* of the fitted ops (step 5) */
+    uint32_t head_match, head_len, tail_match, tail_len;
+    uint32_t reserved;
+} jtk_encode_result_t;
+JTK_LC_API int jtk_lc_encode_nodes(size_t n_trials, const jtk_encode_trial_t *trials, const uint8_t *read_bases,
+                        const uint8_t *cons_bases, const uint8_t *chunk_bases, jtk_encode_result_t *result, uint8_t *ops_out,
+                        uint64_t *ops_out_off, uint64_t ops_cap, int device);
 
 /* Sort key of pileup_nodes (mod.rs:47-50): number of alignment columns that are not '|' in
  * Node::recover (definitions/src/lib.rs:773-813) for run-length cigar ops given per base. */

@@ -45,6 +45,17 @@ JTK_LC_API int jtk_lc_debug_fill_pairs(size_t n_reads, const uint64_t *node_off,
  * the whole call on its stream in ms (upload to the last copy back) and of the pair kernels in ms. */
 JTK_LC_API void jtk_lc_debug_fill_timing(double *out);
 
+/* The work-area budget of jtk_lc_align_guided / jtk_lc_encode_nodes on this thread, in bytes (traceback cells and row tables
+ * per slice of the batch; 0 = the default, 4 GiB): a small value makes a small batch run in several slices.  A pair that
+ * alone needs more still runs, in a slice of its own. */
+JTK_LC_API void jtk_lc_debug_guided_scratch_cap(uint64_t bytes);
+/* Of this thread's last jtk_lc_align_guided call, 4 doubles: the pairs, the cells filled, the HIP-event time of its kernels in
+ * ms, and the slices it ran in. */
+JTK_LC_API void jtk_lc_debug_guided_timing(double *out);
+/* Of this thread's last jtk_lc_encode_nodes call, 8 doubles: the trials that passed the lower-bound filter, the HIP-event time
+ * in ms of the three guided passes [1..3] and the cells they filled [4..6], and the host clock of the infix alignment in ms. */
+JTK_LC_API void jtk_lc_debug_encode_timing(double *out);
+
 /* Keep (on != 0) what the device batches of the following jtk_lc_estimate_gains / jtk_lc_estimate_minimum_gain calls on this thread
  * held: while the switch is on, the last such call keeps, per batch and in batch order, the template and read bytes with their
  * offsets, the ops and their lengths exactly as edit_ops_kernel wrote them (JTK_LC_DEBUG_GAINS_OPS_STRIDE bytes per pair, before the

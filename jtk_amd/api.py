@@ -437,6 +437,127 @@ def fill_timing():
     return dict(n_pairs=int(out[0]), n_records=int(out[1]), device_ms=out[2], pair_ms=out[3])
 
 
+ALN_PARAMETER = (2, -6, -5, -1)     # (match, mismatch, open, ext): haplotyper's ALN_PARAMETER
+
+
+def _flat(seqs, dtype=np.uint8):
+    """sequences (bytes / arrays) back to back -> (buffer, offsets)"""
+    arrs = [np.frombuffer(s, dtype=np.uint8) if isinstance(s, (bytes, bytearray)) else np.asarray(s, dtype=dtype) for s in seqs]
+    off = np.zeros(len(arrs) + 1, dtype=np.uint64)
+    if arrs:
+        off[1:] = np.cumsum([len(a) for a in arrs])
+    buf = np.concatenate(arrs).astype(dtype) if arrs else np.zeros(0, dtype)
+    return np.ascontiguousarray(np.append(buf, dtype(0))), off      # one spare byte: never a null pointer
+
+
+def align_guided(pairs, x_bases, y_bases, guide_ops, mode="global", scores=ALN_PARAMETER, device=0, raise_on_pair_failure=True):
+    """jtk_lc_align_guided: banded affine-gap alignment of every pair (ffi.GUIDED_PAIR_DT: offsets and lengths into x_bases,
+    y_bases, guide_ops, and a radius) along its guide, mode "global" or "infix" (both ends of x free).
+    -> dict(score, start, end, status, ops, ops_off, rc).  The aligner is this build's own specification:
+    parity with kiley's guided alignment is not pinned."""
+    if mode not in ("global", "infix"):
+        raise ValueError("mode is global or infix")
+    pairs = np.ascontiguousarray(pairs, dtype=ffi.GUIDED_PAIR_DT)
+    n = len(pairs)
+    xb, yb, gb = (np.ascontiguousarray(np.append(np.asarray(a, dtype=np.uint8), np.uint8(0))) for a in (x_bases, y_bases, guide_ops))
+    cap = int(pairs["x_len"].astype(np.int64).sum() + pairs["y_len"].astype(np.int64).sum()) + 1
+    ops, ops_off = np.zeros(cap, dtype=np.uint8), np.zeros(n + 1, dtype=np.uint64)
+    score, status = np.zeros(n + 1, dtype=np.int32), np.zeros(n + 1, dtype=np.int32)
+    start, end = np.zeros(n + 1, dtype=np.uint32), np.zeros(n + 1, dtype=np.uint32)
+    PI32 = C.POINTER(C.c_int32)
+    rc = ffi.lib().jtk_lc_align_guided(n, pairs.ctypes.data, u8p(xb), u8p(yb), u8p(gb), ALIGN_MODES[mode], *[int(s) for s in scores],
+                                       u8p(ops), u64p(ops_off), cap, score.ctypes.data_as(PI32), u32p(start), u32p(end),
+                                       status.ctypes.data_as(PI32), device)
+    if rc != 0 and (raise_on_pair_failure or rc != -6):
+        check(rc)
+    return dict(score=score[:n], start=start[:n], end=end[:n], status=status[:n], ops=ops[:int(ops_off[n])], ops_off=ops_off, rc=rc)
+
+
+def align_guided_seqs(items, mode="global", scores=ALN_PARAMETER, device=0, raise_on_pair_failure=True):
+    """align_guided for a list of (x, y, guide, radius) with sequences as bytes: every pair gets buffers of its own."""
+    xb, xo = _flat([it[0] for it in items])
+    yb, yo = _flat([it[1] for it in items])
+    gb, go = _flat([it[2] for it in items])
+    pairs = np.zeros(len(items), dtype=ffi.GUIDED_PAIR_DT)
+    for p, it in enumerate(items):
+        pairs[p] = (xo[p], yo[p], go[p], len(it[0]), len(it[1]), len(it[2]), it[3])
+    return align_guided(pairs, xb, yb, gb, mode=mode, scores=scores, device=device, raise_on_pair_failure=raise_on_pair_failure)
+
+
+def guided_scratch_cap(n_bytes):
+    """jtk_lc_debug_guided_scratch_cap (include/jtk_lc_debug.h): the work-area budget of the guided aligner on this thread; 0
+    restores the default.  A test hook: a small budget cuts a small batch into several slices."""
+    ffi.lib().jtk_lc_debug_guided_scratch_cap(int(n_bytes))
+
+
+def guided_timing():
+    """jtk_lc_debug_guided_timing: pairs, cells filled, kernel ms and slices of the last align_guided call"""
+    out = (C.c_double * 4)()
+    ffi.lib().jtk_lc_debug_guided_timing(out)
+    return dict(n_pairs=int(out[0]), cells=int(out[1]), kernel_ms=out[2], slices=int(out[3]))
+
+
+def encode_nodes(trials, read_bases, cons_bases, chunk_bases, device=0, raise_on_trial_failure=True):
+    """jtk_lc_encode_nodes: `encode_node` (encode/deletion_fill.rs:451-566) for every trial (ffi.ENCODE_TRIAL_DT).
+    -> dict(result (ffi.ENCODE_RESULT_DT), ops, ops_off, rc); the caller runs kiley_op_to_ops on a trial's ops, takes seq from the
+    window and keeps the best score among a slot's accepted trials."""
+    trials = np.ascontiguousarray(trials, dtype=ffi.ENCODE_TRIAL_DT)
+    n = len(trials)
+    rb, cb, kb = (np.ascontiguousarray(np.append(np.asarray(a, dtype=np.uint8), np.uint8(0))) for a in (read_bases, cons_bases, chunk_bases))
+    cap = int(trials["chunk_len"].astype(np.int64).sum() + (trials["end"].astype(np.int64) - trials["start"].astype(np.int64)).clip(0).sum()) + 1
+    result = np.zeros(n + 1, dtype=ffi.ENCODE_RESULT_DT)
+    ops, ops_off = np.zeros(cap, dtype=np.uint8), np.zeros(n + 1, dtype=np.uint64)
+    rc = ffi.lib().jtk_lc_encode_nodes(n, trials.ctypes.data, u8p(rb), u8p(cb), u8p(kb), result.ctypes.data, u8p(ops), u64p(ops_off), cap, device)
+    if rc != 0 and (raise_on_trial_failure or rc != -6):
+        check(rc)
+    return dict(result=result[:n], ops=ops[:int(ops_off[n])], ops_off=ops_off, rc=rc)
+
+
+def encode_timing():
+    """jtk_lc_debug_encode_timing: of the last encode_nodes call, the trials past the filter, kernel ms and cells of the three
+    guided passes, host ms of the infix alignment"""
+    out = (C.c_double * 8)()
+    ffi.lib().jtk_lc_debug_encode_timing(out)
+    return dict(n_live=int(out[0]), pass_ms=[out[1], out[2], out[3]], pass_cells=[int(out[4]), int(out[5]), int(out[6])], infix_host_ms=out[7])
+
+
+OFFSET_FACTOR = 0.1     # deletion_fill.rs:293
+
+
+def fill_trials(side, candidates, seq_len, next_node, cons_len_of):
+    """The trial windows try_encoding_head / _tail (encode/deletion_fill.rs:370-446) make from a slot's candidates; pure host
+    arithmetic, no GPU.
+    side: 0 = head (the position is a start), 1 = tail (it is an end); candidates: (chunk, cluster, is_forward, position) each,
+    position as jtk_lc_fill_candidates returns it (a negative head position is the reference's wrapped usize: rejected by
+    `start_position < seq.len()`; a tail position is never negative there, and one that is raises ValueError, where the
+    reference's wrapped value fails `assert!(start_position < end_position)`); seq_len: the raw read's length; next_node: None or (chunk, position_from_start) of
+    nodes.get(idx); cons_len_of(chunk, cluster) -> the consensus length or None (no such chunk or consensus: skipped).
+    -> list of (candidate index, start, end): the windows encode_node is tried on."""
+    import math
+    out = []
+    for k, (chunk, cluster, _fw, position) in enumerate(candidates):
+        if side == 0 and not (0 <= position < seq_len):
+            continue
+        if position < 0:
+            raise ValueError("a negative tail position (jtk_lc_fill_candidates clamps them at 0; the reference's wrapped usize fails its assert)")
+        cons_len = cons_len_of(chunk, cluster)
+        if cons_len is None:
+            continue
+        offset = math.ceil(OFFSET_FACTOR * float(cons_len))
+        if side == 0:
+            end = min(position + cons_len + offset, seq_len)
+            start = max(position - offset, 0)
+        else:
+            start = max(min(position, seq_len) - (offset + cons_len), 0)
+            end = min(position + offset, seq_len)
+        if not start < end:
+            raise ValueError("start_position < end_position does not hold (the reference asserts)")
+        if next_node is not None and next_node[0] == chunk and abs(next_node[1] - start) < cons_len:
+            continue     # is_the_same_encode
+        out.append((k, start, end))
+    return out
+
+
 def correct_clustering_with_sims(*args, **kw):
     """correct_clustering with the diagnostic switch of include/jtk_lc_debug.h on: returns (cluster, touched, sims), sims = the
     raw similarity matrix (before filter_similarity) of every corrected chunk, in selected_chunks order.  A test hook: the

@@ -59,6 +59,23 @@ pub struct JtkFillCand {
     pub read: u32, pub slot: u32, pub side: u32, pub is_forward: u32, pub chunk: u64, pub cluster: u64,
     pub count: u32, pub reserved: u32, pub position: i64,
 }
+// one pair of jtk_lc_align_guided: offsets into two base buffers and one op buffer, so that pairs can share a sequence
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct JtkGuidedPair {
+    pub x_off: u64, pub y_off: u64, pub guide_off: u64, pub x_len: u32, pub y_len: u32, pub guide_len: u32, pub radius: u32,
+}
+// one call of encode_node (encode/deletion_fill.rs:451-489) and what it returns
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct JtkEncodeTrial {
+    pub read_off: u64, pub start: u32, pub end: u32, pub is_forward: u32, pub cons_len: u32, pub cons_off: u64,
+    pub chunk_off: u64, pub chunk_len: u32, pub reserved: u32, pub sim_thr: f64,
+}
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct JtkEncodeResult {
+    pub status: i32, pub verdict: u32, pub trim_head: u32, pub trim_tail: u32, pub position_from_start: u64,
+    pub query_len: u32, pub band: u32, pub score: i32, pub mat_num: u32, pub ops_len: u32, pub head_match: u32,
+    pub head_len: u32, pub tail_match: u32, pub tail_len: u32, pub reserved: u32,
+}
 
 extern "C" {
     pub fn jtk_lc_cluster_chunks(
@@ -151,6 +168,17 @@ extern "C" {
         n_reads: usize, node_off: *const u64, nodes: *const JtkFillNode, target: *const u8, coverage: *mut u32,
         ins_thr: *mut u32, cand_off: *mut u64, cands: *mut JtkFillCand, cand_cap: usize, n_cands: *mut usize,
         device: c_int) -> c_int;
+    // kiley::bialignment::guided::{global_guided, infix_guided} on this library's own specification (parity
+    // with kiley is not pinned): mode 0 global, 1 infix (both ends of x free); Del consumes an x base, Ins a y base
+    pub fn jtk_lc_align_guided(
+        n_pairs: usize, pairs: *const JtkGuidedPair, x_bases: *const u8, y_bases: *const u8, guide_ops: *const u8, mode: c_int,
+        mat: c_int, mismatch: c_int, gap_open: c_int, gap_ext: c_int, ops_out: *mut u8, ops_out_off: *mut u64, ops_cap: u64,
+        score_out: *mut i32, start_out: *mut u32, end_out: *mut u32, status: *mut i32, device: c_int) -> c_int;
+    // encode_node with fine_mapping and fit_query_by_edlib (encode/deletion_fill.rs:451-566) for a batch of trials; verdict 0
+    // accepted, 1 the lower-bound filter (:461-465), 2 identity or edge (:504-505)
+    pub fn jtk_lc_encode_nodes(
+        n_trials: usize, trials: *const JtkEncodeTrial, read_bases: *const u8, cons_bases: *const u8, chunk_bases: *const u8,
+        result: *mut JtkEncodeResult, ops_out: *mut u8, ops_out_off: *mut u64, ops_cap: u64, device: c_int) -> c_int;
     // the resident-batch form (jtk_lc.h: session_create + run + fetch == jtk_lc_cluster_chunks) and, on it, the reference's
     // trace! rows of one chunk (TOTAL / CAND / PICK / DUMP / RANGE / LK / COUNTS; pseudo_mcmc.rs:122-127,236,250-262,467-472,539)
     pub fn jtk_lc_session_create(

@@ -164,8 +164,8 @@ pub(crate) fn purge_gpu(ds: &mut definitions::DataSet, thr: f64) -> std::collect
 /// One inner round of `filling_until` (encode/deletion_fill.rs:186-212) asks this once, in place of the get_pileup (:642-698) and
 /// the check_insertion_head / _tail calls (:317,:327) of every live read: per read index, its candidates as
 /// (slot, side, LightNode key, position), side 0 = head, 1 = tail.  `correct_deletion_error` then goes on from :318 as it stands
-/// with them: the failed-trial filter, try_encoding_head / _tail (fit_query_by_edlib through jtk_lc_align_reads_mode in infix
-/// mode, kiley's infix_guided on the host), remove_slippy_alignment, remove_overlapping_encoding.  `alive[r]` = the filter of
+/// with them: the failed-trial filter, try_encoding_head / _tail (fill_trials and encode_nodes_gpu below, for all reads of the
+/// round at once), remove_slippy_alignment, remove_overlapping_encoding.  `alive[r]` = the filter of
 /// :196, `!r.nodes.is_empty() && t.is_alive`; the skeletons are those of the reads as they stand at the start of the round,
 /// which is what `read_skeltons` holds after updates_reads (:204).
 pub(crate) fn fill_candidates_gpu(reads: &[definitions::EncodedRead], alive: &[bool])
@@ -192,6 +192,75 @@ pub(crate) fn fill_candidates_gpu(reads: &[definitions::EncodedRead], alive: &[b
     }
     (0..reads.len()).map(|r| cands[cand_off[r] as usize..cand_off[r + 1] as usize].iter()
         .map(|c| (c.slot as usize, c.side, (c.chunk, c.cluster, c.is_forward == 1), c.position as isize)).collect()).collect()
+}
+
+/// The windows try_encoding_head (side 0, `position` = start_position) / try_encoding_tail (side 1, end_position) hand to
+/// encode_node (encode/deletion_fill.rs:370-446), with their arithmetic as it stands: OFFSET_FACTOR = 0.1, the
+/// `start_position < seq.len()` filter of the head side (a negative candidate position is the wrapped usize), and
+/// is_the_same_encode against nodes.get(idx).  -> (candidate index, start, end) of the candidates that are tried.
+pub(crate) fn fill_trials(side: u32, cands: &[((u64, u64, bool), isize)], seq_len: usize, next_node: Option<&definitions::Node>,
+                          consensi: &HashMap<(u64, u64), Vec<u8>>) -> Vec<(usize, usize, usize)> {
+    let abs = |x: usize, y: usize| x.max(y) - x.min(y);
+    cands.iter().enumerate().filter_map(|(k, &((uid, cluster, _), position))| {
+        if side == 0 && !(0 <= position && (position as usize) < seq_len) { return None; }             // :381
+        assert!(position >= 0, "a negative tail position");   // (the wrapped usize fails the reference's assert at :428)
+        let position = position as usize;
+        let cons = consensi.get(&(uid, cluster))?;
+        let offset = (0.1 * cons.len() as f64).ceil() as usize;
+        let (start, end) = if side == 0 {
+            ((position.saturating_sub(offset)), (position + cons.len() + offset).min(seq_len))            // :387-388
+        } else {
+            (position.min(seq_len).saturating_sub(offset + cons.len()), (position + offset).min(seq_len)) // :424-427
+        };
+        assert!(start < end);
+        let same = next_node.map_or(false, |n| n.chunk == uid && abs(n.position_from_start, start) < cons.len());
+        if same { None } else { Some((k, start, end)) }
+    }).collect()
+}
+
+/// `encode_node` (encode/deletion_fill.rs:451-489) for all the trials of a round at once, in place of the calls inside
+/// try_encoding_head / _tail: trial t lays consensi[&(chunk, cluster)] into seq[start..end] of its raw read.  Returns per trial
+/// None (the lower-bound filter, the identity / edge verdict, or a trial the library refused) or the node and its score;
+/// the caller keeps max_by_key(score) over a slot's trials, as :405 / :445 do.  The guided passes are the library's own
+/// specification of kiley's infix_guided (parity with kiley is not pinned).
+pub(crate) fn encode_nodes_gpu(trials: &[(&[u8], (usize, usize, bool), (&definitions::Chunk, u64, &[u8]), f64)])
+    -> Vec<Option<(definitions::Node, i32)>> {
+    // a read has many trials and the trials of a (chunk, cluster) share its consensus: every sequence goes up once
+    let (mut reads, mut conses, mut chunks, mut ts) = (vec![], vec![], vec![], vec![]);
+    let (mut read_at, mut cons_at, mut chunk_at) = (HashMap::new(), HashMap::new(), HashMap::new());
+    for &(seq, (start, end, is_forward), (chunk, cluster, cons), sim_thr) in trials.iter() {
+        let read_off = *read_at.entry((seq.as_ptr(), seq.len())).or_insert_with(|| {
+            reads.extend_from_slice(seq);
+            (reads.len() - seq.len()) as u64
+        });
+        let cons_off = *cons_at.entry((chunk.id, cluster)).or_insert_with(|| {
+            conses.extend_from_slice(cons);
+            (conses.len() - cons.len()) as u64
+        });
+        let chunk_off = *chunk_at.entry(chunk.id).or_insert_with(|| {
+            chunks.extend_from_slice(chunk.seq());
+            (chunks.len() - chunk.seq().len()) as u64
+        });
+        ts.push(JtkEncodeTrial { read_off, start: start as u32, end: end as u32, is_forward: is_forward as u32,
+            cons_len: cons.len() as u32, cons_off, chunk_off, chunk_len: chunk.seq().len() as u32, reserved: 0, sim_thr });
+    }
+    let cap: usize = ts.iter().map(|t| (t.chunk_len + t.end - t.start) as usize).sum();
+    let (mut result, mut ops, mut ops_off) = (vec![JtkEncodeResult::default(); ts.len()], vec![0u8; cap + 1], vec![0u64; ts.len() + 1]);
+    let rc = unsafe { jtk_lc_encode_nodes(ts.len(), ts.as_ptr(), reads.as_ptr(), conses.as_ptr(), chunks.as_ptr(), result.as_mut_ptr(),
+        ops.as_mut_ptr(), ops_off.as_mut_ptr(), cap as u64, /*device*/ 0) };
+    assert!(rc == 0 || rc == -6, "{}", unsafe { std::ffi::CStr::from_ptr(jtk_lc_last_error()) }.to_string_lossy());
+    let kop = [kiley::Op::Match, kiley::Op::Mismatch, kiley::Op::Ins, kiley::Op::Del];
+    trials.iter().zip(result.iter()).enumerate().map(|(t, (&(seq, (start, end, is_forward), (chunk, cluster, _), _), r))| {
+        if r.status != 0 || r.verdict != 0 { return None; }
+        let kops: Vec<_> = ops[ops_off[t] as usize..ops_off[t + 1] as usize].iter().map(|&o| kop[o as usize]).collect();
+        let mut window = if is_forward { seq[start..end].to_vec() } else { bio_utils::revcmp(&seq[start..end]) };   // :467-472
+        window.iter_mut().for_each(u8::make_ascii_uppercase);
+        let query = window[r.trim_head as usize..window.len() - r.trim_tail as usize].to_vec();
+        let mut node = definitions::Node::new(chunk.id, is_forward, query, crate::misc::kiley_op_to_ops(&kops).0,
+                                              r.position_from_start as usize, chunk.cluster_num);                   // :475-487
+        node.cluster = cluster;
+        Some((node, r.score))
+    }).collect()
 }
 
 fn to_ffi(h: &kiley::hmm::PairHiddenMarkovModel) -> JtkHmm {
