@@ -600,6 +600,35 @@ JTK_LC_API int jtk_lc_encode_nodes(size_t n_trials, const jtk_encode_trial_t *tr
                         const uint8_t *cons_bases, const uint8_t *chunk_bases, jtk_encode_result_t *result, uint8_t *ops_out,
                         uint64_t *ops_out_off, uint64_t ops_cap, int device);
 
+/* ---- consensus polishing that votes with banded edit distances -----------------------------------------------------------
+ * What the reference gets from kiley::bialignment::guided::polish_until_converge / polish_until_converge_with:
+ * `take_consensus_sequence` (encode/deletion_fill.rs:260-285, whose output is the cons_bases of jtk_lc_encode_nodes),
+ * `polish_chunk` (polish_chunks.rs:64-65), the refresh of `polish_seg` (consensus/mod.rs:442,470-472), determine_chunks.rs:439
+ * and dense_encoding.rs:575-577.  kiley is not part of the reference tree: the polish follows THIS build's specification,
+ * DESIGN.md section 4 ("Guided polishing"), and parity with kiley's polish is NOT pinned.  In short, per pile-up and round t:
+ * every read is aligned to the template at unit costs inside the band of jtk_lc_align_guided around its current ops (walk back:
+ * diagonal, then Del, then Ins; these ops replace the read's); the first take_num reads (0 = all) vote with the 14-row table of
+ * jtk_lc_modification_table's layout, T[p][row] = the banded distance of the read to the edited template, gain = the sum over
+ * the voters of dist - T; the scan of jtk_lc_polish_chunks applies the first best row of a position where its gain is >= 1 and
+ * no voter finds the entry outside its band; edits are applied, every read's ops re-threaded, and the next round begins.  A
+ * round that applies nothing is the last; so is round max_rounds (0 = 20), after which the reads are aligned once more, so
+ * that the ops and distances returned always belong to the consensus returned.
+ * chunks / tmpl_bases / read_bases / read_off / ops / ops_off, cons_out / ops_out and their capacities, and the read-layout
+ * precondition are those of jtk_lc_polish_chunks; copy_num, chunk_id and strands play no part.  radius[c] is pile-up c's band
+ * radius; dist_out[r] the edit distance of read r inside its band; result[c].status and .polish_rounds are filled (rounds
+ * count the one that applied nothing).  A pile-up without reads returns its template after one round; one with
+ * 2 ignore_edge >= tmpl_len is not scanned (one round) and only has its reads aligned.
+ * JTK_ERR_INVALID_ARG, before a device is looked for: a base that is not ACGT, an op above 3, a radius of 0, a null pointer.
+ * Limits, per pile-up (result[c].status = JTK_ERR_UNSUPPORTED, empty consensus and ops, dist_out = UINT32_MAX, the rest of the
+ * batch is polished and the call returns JTK_ERR_CHUNK_FAILED): 32,000 bases per sequence and JTK_GUIDED_MAX_WIDTH cells in
+ * one row of a band; a consensus that outgrows tmpl_len + 64 + tmpl_len / 8 bases fails its pile-up the same way with
+ * JTK_ERR_CHUNK_FAILED. */
+JTK_LC_API int jtk_lc_polish_guided(size_t n_chunks, const jtk_lc_chunk_t *chunks, const uint8_t *tmpl_bases,
+                         const uint8_t *read_bases, const uint64_t *read_off, const uint8_t *ops, const uint64_t *ops_off,
+                         const uint32_t *radius /* per chunk */, uint32_t take_num, uint32_t ignore_edge, uint32_t max_rounds,
+                         uint8_t *cons_out, uint64_t *cons_off, uint64_t cons_cap, uint8_t *ops_out, uint64_t *ops_out_off,
+                         uint64_t ops_cap, uint32_t *dist_out /* per read */, jtk_lc_result_t *result, int device);
+
 /* Sort key of pileup_nodes (mod.rs:47-50): number of alignment columns that are not '|' in
  * Node::recover (definitions/src/lib.rs:773-813) for run-length cigar ops given per base. */
 JTK_LC_API int jtk_lc_pileup_sort_key(const uint8_t *tmpl, uint64_t tmpl_len, const uint8_t *read, uint64_t read_len,

@@ -56,6 +56,19 @@ JTK_LC_API void jtk_lc_debug_guided_timing(double *out);
  * in ms of the three guided passes [1..3] and the cells they filled [4..6], and the host clock of the infix alignment in ms. */
 JTK_LC_API void jtk_lc_debug_encode_timing(double *out);
 
+/* One round's fill of jtk_lc_polish_guided for a single pile-up, nothing applied: dist_out[r] = the banded edit distance of
+ * read r along its ops, and table_out[r * table_stride + p * 14 + row] = T[p][row] of DESIGN.md section 4 ("Guided polishing")
+ * for p = 0 .. tmpl_len, UINT32_MAX for a dead entry; table_stride >= (tmpl_len + 1) * 14.  Unlike the polish it takes a radius
+ * of 0 (the band is the guide's path). */
+JTK_LC_API int jtk_lc_debug_guided_table(const uint8_t *tmpl, uint32_t tmpl_len, uint32_t n_reads, const uint8_t *read_bases,
+                                         const uint64_t *read_off, const uint8_t *ops, const uint64_t *ops_off, uint32_t radius,
+                                         uint32_t *dist_out, uint32_t *table_out, uint64_t table_stride, int device);
+/* Of this thread's last jtk_lc_polish_guided call, 8 doubles: pile-ups, reads, rounds the host enqueued, band cells filled
+ * forward (all passes), the HIP-event time of the rounds' kernels in ms, the slices of the work area, the bytes of work area
+ * that all reads together take by the host's bound (F cells, row tables, rings), and the band cells of the voting reads'
+ * fills (whose table reads F rows p .. p + 3 at every position p). */
+JTK_LC_API void jtk_lc_debug_gpolish_timing(double *out);
+
 /* Keep (on != 0) what the device batches of the following jtk_lc_estimate_gains / jtk_lc_estimate_minimum_gain calls on this thread
  * held: while the switch is on, the last such call keeps, per batch and in batch order, the template and read bytes with their
  * offsets, the ops and their lengths exactly as edit_ops_kernel wrote them (JTK_LC_DEBUG_GAINS_OPS_STRIDE bytes per pair, before the

@@ -497,6 +497,84 @@ def guided_timing():
     return dict(n_pairs=int(out[0]), cells=int(out[1]), kernel_ms=out[2], slices=int(out[3]))
 
 
+def polish_guided(batch, radius, take_num=0, ignore_edge=0, max_rounds=0, device=0, raise_on_chunk_failure=True):
+    """jtk_lc_polish_guided: the consensus polish that votes with banded edit distances (what the reference gets from kiley's
+    `bialignment::guided::polish_until_converge`), on every pile-up of `batch`; strands, copy numbers and ids play no part.
+    radius: one band radius for all pile-ups or one per pile-up; take_num = 0: every read votes; max_rounds = 0: 20.
+    -> dict(cons, cons_off, ops_out, ops_out_off, dist, result, rc).  The polish is this build's own specification (DESIGN.md
+    section 4, "Guided polishing"): parity with kiley's polish is not pinned."""
+    n_chunks, n_reads = batch.n_chunks, len(batch.read_off) - 1
+    rad = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.uint32), (n_chunks,)))
+    result = np.zeros(n_chunks + 1, dtype=ffi.RESULT_DT)
+    tl = batch.chunks["tmpl_len"].astype(np.int64)
+    cons_cap = int((tl + 64 + tl // 8).sum()) + 1
+    rl = np.diff(batch.read_off.astype(np.int64))
+    ops_cap = int((np.repeat(tl + 64 + tl // 8, batch.chunks["n_reads"].astype(np.int64))).sum() + rl.sum()) + 1
+    cons, cons_off = np.zeros(cons_cap, dtype=np.uint8), np.zeros(n_chunks + 1, dtype=np.uint64)
+    ops_out, ops_out_off = np.zeros(ops_cap, dtype=np.uint8), np.zeros(n_reads + 1, dtype=np.uint64)
+    dist = np.zeros(n_reads + 1, dtype=np.uint32)
+    tb, rb, ob = (np.ascontiguousarray(np.append(np.asarray(a, dtype=np.uint8), np.uint8(0))) for a in (batch.tmpl_bases, batch.read_bases, batch.ops))
+    rc = ffi.lib().jtk_lc_polish_guided(n_chunks, batch.chunks.ctypes.data, u8p(tb), u8p(rb), u64p(batch.read_off), u8p(ob), u64p(batch.ops_off),
+                                        u32p(np.append(rad, np.uint32(0))), int(take_num), int(ignore_edge), int(max_rounds), u8p(cons),
+                                        u64p(cons_off), cons_cap, u8p(ops_out), u64p(ops_out_off), ops_cap, u32p(dist), result.ctypes.data, device)
+    if rc != 0 and (raise_on_chunk_failure or rc != -6):
+        check(rc)
+    return dict(cons=cons, cons_off=cons_off, ops_out=ops_out, ops_out_off=ops_out_off, dist=dist[:n_reads], result=result[:n_chunks], rc=rc)
+
+
+def guided_table(tmpl, reads, opss, radius, device=0):
+    """jtk_lc_debug_guided_table (include/jtk_lc_debug.h): one round's fill of polish_guided for one pile-up, nothing applied.
+    -> (dist [n_reads] uint32, table [n_reads, len(tmpl) + 1, 14] uint32 with 0xFFFFFFFF for a dead entry).  A test hook."""
+    tmpl = np.frombuffer(tmpl, dtype=np.uint8) if isinstance(tmpl, (bytes, bytearray)) else np.asarray(tmpl, dtype=np.uint8)
+    rb, ro = _flat(reads)
+    ob, oo = _flat(opss)
+    n, nr = len(tmpl), len(reads)
+    dist = np.zeros(nr + 1, dtype=np.uint32)
+    table = np.zeros((nr, n + 1, ffi.NUM_ROW), dtype=np.uint32)
+    tb = np.ascontiguousarray(np.append(tmpl, np.uint8(0)))
+    check(ffi.lib().jtk_lc_debug_guided_table(u8p(tb), n, nr, u8p(rb), u64p(ro), u8p(ob), u64p(oo), int(radius), u32p(dist), u32p(table),
+                                              (n + 1) * ffi.NUM_ROW, device))
+    return dist[:nr], table
+
+
+def gpolish_timing():
+    """jtk_lc_debug_gpolish_timing: of the last polish_guided call, pile-ups, reads, rounds enqueued, band cells filled forward,
+    kernel ms, the slices of the work area and the bytes all reads take of it by the host's bound"""
+    out = (C.c_double * 8)()
+    ffi.lib().jtk_lc_debug_gpolish_timing(out)
+    return dict(n_chunks=int(out[0]), n_reads=int(out[1]), rounds=int(out[2]), cells=int(out[3]), kernel_ms=out[4], slices=int(out[5]),
+                work_bytes=int(out[6]), vote_cells=int(out[7]))
+
+
+def take_consensus(chunk_seqs, node_chunk, node_cluster, node_seqs, band_frac, device=0):
+    """`take_consensus_sequence` (encode/deletion_fill.rs:260-285) for flat node arrays: the nodes are bucketed by (chunk, cluster)
+    in the order given (that of encoded_reads); cluster 0 stands for the chunk's own sequence; any other bucket is polished from
+    the chunk's sequence with its nodes' sequences -- global ops from align_reads, then polish_guided with radius =
+    ReadType::band_width(len) = ceil(len * band_frac) (definitions/src/lib.rs:201-210).
+    chunk_seqs: {chunk id: uint8 array}; band_frac: dataset.BAND_FRAC of the read type.
+    -> {(chunk, cluster): uint8 array}, in bucket order: the cons_bases that the trials of encode_nodes take.  The polish is this
+    build's own specification: parity with kiley's polish is not pinned."""
+    import math
+    from .batch import pack
+    bucket = {}
+    for cid, cl, seq in zip(node_chunk, node_cluster, node_seqs):
+        bucket.setdefault((int(cid), int(cl)), []).append(np.asarray(seq, dtype=np.uint8))
+    for cid, _ in bucket:
+        if cid not in chunk_seqs:
+            raise KeyError("take_consensus: a node of chunk %d, which has no sequence" % cid)
+    todo = [key for key in bucket if key[1] != 0]
+    polished = {}
+    if todo:
+        none = np.zeros(0, dtype=np.uint8)
+        batch = pack([(key[0], 1, chunk_seqs[key[0]], bucket[key], [none] * len(bucket[key]), [1] * len(bucket[key]), None) for key in todo])
+        aligned = align_reads(batch, device=device)
+        radius = [max(1, math.ceil(len(chunk_seqs[key[0]]) * band_frac)) for key in todo]
+        out = polish_guided(batch.with_ops(aligned["ops"], aligned["ops_off"]), radius, device=device)
+        for c, key in enumerate(todo):
+            polished[key] = out["cons"][int(out["cons_off"][c]):int(out["cons_off"][c + 1])].copy()
+    return {key: (np.asarray(chunk_seqs[key[0]], dtype=np.uint8) if key[1] == 0 else polished[key]) for key in bucket}
+
+
 def encode_nodes(trials, read_bases, cons_bases, chunk_bases, device=0, raise_on_trial_failure=True):
     """jtk_lc_encode_nodes: `encode_node` (encode/deletion_fill.rs:451-566) for every trial (ffi.ENCODE_TRIAL_DT).
     -> dict(result (ffi.ENCODE_RESULT_DT), ops, ops_off, rc); the caller runs kiley_op_to_ops on a trial's ops, takes seq from the

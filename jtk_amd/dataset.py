@@ -516,6 +516,18 @@ def fill_candidates(ds, alive=None, device=0):
     return report
 
 
+def take_consensus_sequence(ds, device=0):
+    """take_consensus_sequence (encode/deletion_fill.rs:260-285): the consensus of every (chunk, cluster) that a node carries --
+    the chunk's own sequence for cluster 0, otherwise the guided polish of the chunk's sequence with the nodes' sequences, band =
+    read_type.band_width(len).  -> {(chunk, cluster): str}; the data set is not changed.  The polish is this build's own
+    specification ("Guided polishing"): parity with kiley's polish_until_converge is not pinned."""
+    chunk_seqs = {c["id"]: _seq(c["seq"].upper()) for c in ds["selected_chunks"]}
+    nodes = [n for read in ds["encoded_reads"] for n in read["nodes"]]
+    out = api.take_consensus(chunk_seqs, [n["chunk"] for n in nodes], [n["cluster"] for n in nodes], [_seq(n["seq"].upper()) for n in nodes],
+                             BAND_FRAC[ds["read_type"]], device=device)
+    return {key: bytes(seq).decode("ascii") for key, seq in out.items()}
+
+
 def recover_raw_read(read):
     """EncodedRead::recover_raw_read (definitions/src/lib.rs:604-619): leading gap, then every node's original sequence
     (Node::original_seq :737-753: reverse complement of a reverse node; anything but ACGT panics) with the overlap of a
@@ -584,7 +596,7 @@ def correct_clustering(ds, device=0, min_gain=None):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--stage", default="local_clustering", choices=("local_clustering", "correct_clustering", "squish_erroneous_clusters", "corrected", "realign", "purge_diverged_nodes", "fill_candidates"),
+    ap.add_argument("--stage", default="local_clustering", choices=("local_clustering", "correct_clustering", "squish_erroneous_clusters", "corrected", "realign", "purge_diverged_nodes", "fill_candidates", "consensus_sequences"),
                     help="which JTK stage to run on the file (jtk local_clustering / jtk correct_clustering); "
                          "squish_erroneous_clusters: the step JTK runs in front of the correction, with its default "
                          "configuration; corrected: that step, then correct_clustering (cli/src/pipeline.rs:174-175); realign: "
@@ -592,7 +604,9 @@ def main(argv=None):
                          "half of `ds.purge` (purge_diverged.rs:238-322), the purged chunk ids go to stderr; fill_candidates: the "
                          "candidate search of correct_deletion (deletion_fill.rs:301-337) -- the output is a REPORT, a JSON list "
                          "keyed by read id with coverage, ins_thr and the head / tail candidates, not a DataSet: testing a "
-                         "candidate against the sequence (encode_node, kiley's infix_guided) is JTK's")
+                         "candidate against the sequence (encode_node, kiley's infix_guided) is JTK's; consensus_sequences: "
+                         "take_consensus_sequence (deletion_fill.rs:260-285) -- also a REPORT, {\"chunk,cluster\": \"ACGT...\"}, made with "
+                         "this build's guided polish (parity with kiley's polish_until_converge is not pinned)")
     ap.add_argument("input", help="DataSet JSON ('-' = stdin)")
     ap.add_argument("output", help="DataSet JSON ('-' = stdout)")
     ap.add_argument("--chunks", default="", help="comma-separated chunk ids (local_clustering_selected); default: all")
@@ -628,6 +642,9 @@ def main(argv=None):
             local_clustering_selected(ds, purged, device=args.device, failed=failed, refit=not args.no_refit, record=record, trace=trace)
     elif args.stage == "fill_candidates":
         ds = fill_candidates(ds, device=args.device)   # the report takes the data set's place in the output
+    elif args.stage == "consensus_sequences":
+        validate(ds)
+        ds = {"%d,%d" % key: seq for key, seq in take_consensus_sequence(ds, device=args.device).items()}   # a report as well
     elif args.stage == "correct_clustering":
         validate(ds)
         if args.chunks:

@@ -102,7 +102,7 @@ ENCODE_ACCEPTED, ENCODE_LOWER_BOUND, ENCODE_REJECTED = 0, 1, 2   # enum jtk_enco
 # every symbol declared in include/jtk_lc.h (tests check the library exports them)
 EXPORTED_SYMBOLS = (
     "jtk_lc_cluster_chunks", "jtk_lc_cluster_chunks_multi", "jtk_lc_cluster_polished", "jtk_lc_polish_chunks", "jtk_lc_align_reads", "jtk_lc_align_reads_mode", "jtk_lc_modification_table",
-    "jtk_lc_cluster_features", "jtk_lc_estimate_gains", "jtk_lc_estimate_minimum_gain", "jtk_lc_fit_model", "jtk_lc_correct_clustering", "jtk_lc_squish_clusters", "jtk_lc_squish_classify", "jtk_lc_node_errors", "jtk_lc_error_quantile", "jtk_lc_estimate_error_rate", "jtk_lc_purge_diverged", "jtk_lc_fill_candidates", "jtk_lc_align_guided", "jtk_lc_encode_nodes", "jtk_lc_trim_cache", "jtk_lc_pileup_sort_key", "jtk_lc_normalize_pileup", "jtk_lc_strerror",
+    "jtk_lc_cluster_features", "jtk_lc_estimate_gains", "jtk_lc_estimate_minimum_gain", "jtk_lc_fit_model", "jtk_lc_correct_clustering", "jtk_lc_squish_clusters", "jtk_lc_squish_classify", "jtk_lc_node_errors", "jtk_lc_error_quantile", "jtk_lc_estimate_error_rate", "jtk_lc_purge_diverged", "jtk_lc_fill_candidates", "jtk_lc_align_guided", "jtk_lc_polish_guided", "jtk_lc_encode_nodes", "jtk_lc_trim_cache", "jtk_lc_pileup_sort_key", "jtk_lc_normalize_pileup", "jtk_lc_strerror",
     "jtk_lc_last_error", "jtk_lc_version", "jtk_lc_device_ok", "jtk_lc_last_timing",
     "jtk_lc_session_create", "jtk_lc_session_run", "jtk_lc_session_fetch", "jtk_lc_session_destroy", "jtk_lc_session_trace",
 )
@@ -112,6 +112,7 @@ DEBUG_SYMBOLS = (
     "jtk_lc_debug_chain_profile", "jtk_lc_debug_purge_timing", "jtk_lc_debug_fill_pairs", "jtk_lc_debug_fill_timing",
     "jtk_lc_debug_gains_keep", "jtk_lc_debug_gains_batches", "jtk_lc_debug_gains_batch_sizes", "jtk_lc_debug_gains_batch",
     "jtk_lc_debug_guided_scratch_cap", "jtk_lc_debug_guided_timing", "jtk_lc_debug_encode_timing",
+    "jtk_lc_debug_guided_table", "jtk_lc_debug_gpolish_timing",
 )
 DEBUG_GAINS_OPS_STRIDE = 512   # JTK_LC_DEBUG_GAINS_OPS_STRIDE
 SYNTH_SYMBOLS = ("jtk_synth_pileup",)
@@ -188,6 +189,9 @@ def lib():
     sig("jtk_lc_debug_guided_scratch_cap", None, u64)
     sig("jtk_lc_debug_guided_timing", None, PD)
     sig("jtk_lc_debug_encode_timing", None, PD)
+    sig("jtk_lc_polish_guided", i32, sz, vp, PU8, PU8, PU64, PU8, PU64, PU32, u32, u32, u32, PU8, PU64, u64, PU8, PU64, u64, PU32, vp, i32)
+    sig("jtk_lc_debug_guided_table", i32, PU8, u32, u32, PU8, PU64, PU8, PU64, u32, PU32, PU32, u64, i32)
+    sig("jtk_lc_debug_gpolish_timing", None, PD)
     sig("jtk_lc_trim_cache", i32, i32)
     sig("jtk_lc_cluster_features", i32, PP, sz, vp, PD, PU32, PU32, PD, u32, vp, i32)
     sig("jtk_lc_pileup_sort_key", i32, PU8, u64, PU8, u64, PU8, u64, PU64)

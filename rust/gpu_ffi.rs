@@ -174,6 +174,15 @@ extern "C" {
         n_pairs: usize, pairs: *const JtkGuidedPair, x_bases: *const u8, y_bases: *const u8, guide_ops: *const u8, mode: c_int,
         mat: c_int, mismatch: c_int, gap_open: c_int, gap_ext: c_int, ops_out: *mut u8, ops_out_off: *mut u64, ops_cap: u64,
         score_out: *mut i32, start_out: *mut u32, end_out: *mut u32, status: *mut i32, device: c_int) -> c_int;
+    // kiley::bialignment::guided::polish_until_converge(_with) on this library's own specification ("Guided
+    // polishing"; parity with kiley's polish is not pinned): encode/deletion_fill.rs:260-285, polish_chunks.rs:64-65,
+    // consensus/mod.rs:442,470-472, determine_chunks.rs:439, dense_encoding.rs:575-577.  radius: one per chunk; take_num 0 = every
+    // read votes; max_rounds 0 = 20; dist_out: one per read
+    pub fn jtk_lc_polish_guided(
+        n_chunks: usize, chunks: *const JtkLcChunk, tmpl_bases: *const u8, read_bases: *const u8, read_off: *const u64,
+        ops: *const u8, ops_off: *const u64, radius: *const u32, take_num: u32, ignore_edge: u32, max_rounds: u32,
+        cons_out: *mut u8, cons_off: *mut u64, cons_cap: u64, ops_out: *mut u8, ops_out_off: *mut u64, ops_cap: u64,
+        dist_out: *mut u32, result: *mut JtkLcResult, device: c_int) -> c_int;
     // encode_node with fine_mapping and fit_query_by_edlib (encode/deletion_fill.rs:451-566) for a batch of trials; verdict 0
     // accepted, 1 the lower-bound filter (:461-465), 2 identity or edge (:504-505)
     pub fn jtk_lc_encode_nodes(

@@ -194,6 +194,53 @@ pub(crate) fn fill_candidates_gpu(reads: &[definitions::EncodedRead], alive: &[b
         .map(|c| (c.slot as usize, c.side, (c.chunk, c.cluster, c.is_forward == 1), c.position as isize)).collect()).collect()
 }
 
+/// `take_consensus_sequence` (encode/deletion_fill.rs:260-285) in one call: the nodes are bucketed by (chunk, cluster) in
+/// encoded_reads order, cluster 0 stands for the chunk's own sequence, and every other bucket is polished from the chunk's
+/// sequence: the global ops of jtk_lc_align_reads, then jtk_lc_polish_guided with radius = read_type.band_width(len) (:277).
+/// Its result is the `consensi` of fill_trials and the cons of encode_nodes_gpu's trials.  The polish is the library's own
+/// specification of kiley's polish_until_converge (parity with kiley is not pinned).
+pub(crate) fn take_consensus_gpu(ds: &definitions::DataSet) -> HashMap<(u64, u64), Vec<u8>> {
+    let ref_chunks: HashMap<_, _> = ds.selected_chunks.iter().map(|u| (u.id, u)).collect();
+    let (mut keys, mut bucket): (Vec<(u64, u64)>, HashMap<(u64, u64), Vec<&[u8]>>) = (vec![], HashMap::new());
+    for node in ds.encoded_reads.iter().flat_map(|r| r.nodes.iter()) {
+        bucket.entry((node.chunk, node.cluster)).or_insert_with(|| { keys.push((node.chunk, node.cluster)); vec![] }).push(node.seq());
+    }
+    let todo: Vec<_> = keys.iter().copied().filter(|k| k.1 != 0).collect();
+    let (mut chunks, mut tmpl, mut reads, mut read_off, mut radius) = (vec![], vec![], vec![], vec![0u64], vec![]);
+    for key in todo.iter() {
+        let seq = ref_chunks[&key.0].seq();
+        chunks.push(JtkLcChunk { chunk_id: key.0, copy_num: 1, n_reads: bucket[key].len() as u32, tmpl_off: tmpl.len() as u64,
+            tmpl_len: seq.len() as u64, read_first: (read_off.len() - 1) as u64 });
+        tmpl.extend(seq.iter().map(u8::to_ascii_uppercase));
+        radius.push(ds.read_type.band_width(seq.len()).max(1) as u32);
+        for rd in bucket[key].iter() {
+            reads.extend(rd.iter().map(u8::to_ascii_uppercase));
+            read_off.push(reads.len() as u64);
+        }
+    }
+    let n_reads = read_off.len() - 1;
+    let per_read: usize = chunks.iter().map(|c| c.n_reads as usize * (c.tmpl_len as usize + 64 + c.tmpl_len as usize / 8)).sum();
+    let ops_cap = reads.len() + per_read + 1;
+    let cons_cap: usize = chunks.iter().map(|c| c.tmpl_len as usize + 64 + c.tmpl_len as usize / 8).sum::<usize>() + 1;
+    let (mut ops, mut ops_off, mut dist, mut status) = (vec![0u8; ops_cap], vec![0u64; n_reads + 1], vec![0u32; n_reads + 1], vec![0i32; n_reads + 1]);
+    let err = || unsafe { std::ffi::CStr::from_ptr(jtk_lc_last_error()) }.to_string_lossy().into_owned();
+    let rc = unsafe { jtk_lc_align_reads(chunks.len(), chunks.as_ptr(), tmpl.as_ptr(), reads.as_ptr(), read_off.as_ptr(), 0,
+        ops.as_mut_ptr(), ops_off.as_mut_ptr(), ops_cap as u64, dist.as_mut_ptr(), status.as_mut_ptr(), /*device*/ 0) };
+    assert!(rc == 0, "{}", err());
+    let (mut cons, mut cons_off) = (vec![0u8; cons_cap], vec![0u64; chunks.len() + 1]);
+    let (mut ops_out, mut ops_out_off) = (vec![0u8; ops_cap], vec![0u64; n_reads + 1]);
+    let mut result = vec![JtkLcResult::default(); chunks.len() + 1];
+    let rc = unsafe { jtk_lc_polish_guided(chunks.len(), chunks.as_ptr(), tmpl.as_ptr(), reads.as_ptr(), read_off.as_ptr(), ops.as_ptr(),
+        ops_off.as_ptr(), radius.as_ptr(), /*take_num*/ 0, /*ignore_edge*/ 0, /*max_rounds*/ 0, cons.as_mut_ptr(), cons_off.as_mut_ptr(),
+        cons_cap as u64, ops_out.as_mut_ptr(), ops_out_off.as_mut_ptr(), ops_cap as u64, dist.as_mut_ptr(), result.as_mut_ptr(), /*device*/ 0) };
+    assert!(rc == 0, "{}", err());
+    let mut out: HashMap<(u64, u64), Vec<u8>> = keys.iter().filter(|k| k.1 == 0).map(|k| (*k, ref_chunks[&k.0].seq().to_vec())).collect();
+    for (c, key) in todo.iter().enumerate() {
+        out.insert(*key, cons[cons_off[c] as usize..cons_off[c + 1] as usize].to_vec());
+    }
+    out
+}
+
 /// The windows try_encoding_head (side 0, `position` = start_position) / try_encoding_tail (side 1, end_position) hand to
 /// encode_node (encode/deletion_fill.rs:370-446), with their arithmetic as it stands: OFFSET_FACTOR = 0.1, the
 /// `start_position < seq.len()` filter of the head side (a negative candidate position is the wrapped usize), and
