@@ -23,6 +23,7 @@
 
 #include "device_common.h"
 #include "host_common.h"
+#include "wave_util.h"
 
 #define ALIGN_MAX_LEN 32000u  // tl + rl stays below the 16-bit infinity
 #define ALIGN_INF 0xFFFFu
@@ -52,13 +53,6 @@ __device__ __forceinline__ uint64_t load_u64_unaligned(const uint8_t *p) {
     uint64_t v;
     __builtin_memcpy(&v, p, 8);
     return v;
-}
-
-// LDS written by some lanes of the wave, read by others
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // the walk goes on: infix stops at the first cell on the free boundary (j == 0 or i == 0; d + k = 2j, d - k = 2i), the
@@ -203,7 +197,7 @@ __global__ __launch_bounds__(THREADS) void align_kernel(const AlignPair *pairs, 
             const int db = db_lo + a / ALIGN_TILE_GROUPS, g = g_lo + a % ALIGN_TILE_GROUPS;
             if (db >= 0 && g < G) tile[a] = scratch[pr.scratch_off + (uint64_t)db * G + g];
         }
-        wave_sync();
+        jtk_wave_sync();
         uint32_t nl = 0;
         while (walk_on<MODE, FREE>(d, klo + s) && nl < 64) {
             const int db = (d >> 3) - db_lo, c = s >> 1, g = (c >> 3) - g_lo;
@@ -219,10 +213,10 @@ __global__ __launch_bounds__(THREADS) void align_kernel(const AlignPair *pairs, 
             if (tid == (int)nl) opbuf[tid] = (uint8_t)(code == MV_DEL ? JTK_OP_DEL : code == MV_INS ? JTK_OP_INS : code);
             nl++;
         }
-        wave_sync();
+        jtk_wave_sync();
         if ((uint32_t)tid < nl) *(slot_end - 1 - (n + tid)) = opbuf[tid];
         n += nl;
-        wave_sync();
+        jtk_wave_sync();
         if (nl == 0) break;  // cannot happen with the codes the fill wrote; never spin on anything else
     }
     if (tid == 0) {

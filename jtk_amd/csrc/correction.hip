@@ -17,7 +17,6 @@
 #include <atomic>
 #include <cmath>
 #include <cstring>
-#include <memory>
 #include <string>
 #include <thread>
 #include <unordered_map>
@@ -25,9 +24,9 @@
 #include <vector>
 
 #include "device_common.h"
-#include "host_common.h"
 #include "jtk_lc_debug.h"
 #include "jtk_eigen.h"
+#include "prim_host.h"
 
 namespace {
 
@@ -532,12 +531,15 @@ extern "C" int jtk_lc_correct_clustering(size_t n_reads, const uint64_t *read_id
         d_cn_off[c] = cn_off[c];
         d_cn_len[c] = cn_len[c];
     }
+    DevStream s;
+    DevArr<double> d_post, d_cn;
+    DevArr<uint64_t> d_cnoff;
+    DevArr<uint32_t> d_cnlen;
+    DevArr<int> d_panic;
     hipStream_t st = nullptr;
-    std::unique_ptr<void, void (*)(void *)> st_guard(nullptr, [](void *s) { if (s) (void)hipStreamDestroy((hipStream_t)s); });
-    DevBuf d_post, d_cn, d_cnoff, d_cnlen, d_panic;
     if (!jobs.empty()) {
-        JTK_HIP_TRY(hipStreamCreate(&st));
-        st_guard.reset(st);
+        JTK_HIP_TRY(s.create());
+        st = s.st;
         size_t n_post = 0;
         for (size_t e = 0; e < n_nodes; e++) n_post = std::max<size_t>(n_post, nodes[e].post_off + nodes[e].post_len);
         std::vector<double> post_v(posteriors, posteriors + n_post);
@@ -545,8 +547,8 @@ extern "C" int jtk_lc_correct_clustering(size_t n_reads, const uint64_t *read_id
         if ((rc = d_post.upload(post_v, st)) || (rc = d_cn.upload(cn, st)) || (rc = d_cnoff.upload(d_cn_off, st)) ||
             (rc = d_cnlen.upload(d_cn_len, st)))
             return jtk_fail(rc, "device upload failed");
-        JTK_HIP_TRY(d_panic.alloc(sizeof(int)));
-        JTK_HIP_TRY(hipMemsetAsync(d_panic.p, 0, sizeof(int), st));
+        JTK_HIP_TRY(d_panic.alloc(1));
+        JTK_HIP_TRY(d_panic.zero(1, st));
         JTK_HIP_TRY(hipStreamSynchronize(st));  // post_v goes out of scope
     }
     g_first_sims.clear();
@@ -621,22 +623,24 @@ extern "C" int jtk_lc_correct_clustering(size_t n_reads, const uint64_t *read_id
     // ---- the similarity fill on the device
     std::vector<double> sims(sims_total);
     if (n_pairs) {
-        DevBuf d_jobs, d_members, d_arms, d_sims, d_scratch;
+        DevArr<PairJob> d_jobs;
+        DevArr<Member> d_members;
+        DevArr<ArmEnt> d_arms;
+        DevArr<double> d_sims, d_scratch;
         int rc;
         if ((rc = d_jobs.upload(pjobs, st)) || (rc = d_members.upload(members, st)) || (rc = d_arms.upload(arms, st)))
             return jtk_fail(rc, "device upload failed");
-        JTK_HIP_TRY(d_sims.alloc(std::max<size_t>(sims_total, 1) * sizeof(double)));
+        JTK_HIP_TRY(d_sims.alloc(sims_total));
         const uint32_t row_doubles = 2 * 3 * (max_arm + 1);
         uint64_t threads = std::min<uint64_t>(n_pairs, 256ull * 1024);
         threads = (threads + 255) / 256 * 256;
-        JTK_HIP_TRY(d_scratch.alloc(threads * row_doubles * sizeof(double)));
-        similarity_kernel<<<(uint32_t)(threads / 256), 256, 0, st>>>(
-            n_pairs, (uint32_t)pjobs.size(), (const PairJob *)d_jobs.p, (const Member *)d_members.p, (const ArmEnt *)d_arms.p,
-            (const double *)d_post.p, (const double *)d_cn.p, (const uint64_t *)d_cnoff.p, (const uint32_t *)d_cnlen.p,
-            (double *)d_sims.p, (double *)d_scratch.p, row_doubles, (int *)d_panic.p);
+        JTK_HIP_TRY(d_scratch.alloc(threads * row_doubles));
+        similarity_kernel<<<(uint32_t)(threads / 256), 256, 0, st>>>(n_pairs, (uint32_t)pjobs.size(), d_jobs.cget(), d_members.cget(), d_arms.cget(),
+                                                                     d_post.cget(), d_cn.cget(), d_cnoff.cget(), d_cnlen.cget(), d_sims.get(),
+                                                                     d_scratch.get(), row_doubles, d_panic.get());
         int dev_panic = 0;
-        JTK_HIP_TRY(hipMemcpyAsync(sims.data(), d_sims.p, sims_total * sizeof(double), hipMemcpyDeviceToHost, st));
-        JTK_HIP_TRY(hipMemcpyAsync(&dev_panic, d_panic.p, sizeof(int), hipMemcpyDeviceToHost, st));
+        JTK_HIP_TRY(d_sims.download(sims.data(), sims_total, st));
+        JTK_HIP_TRY(d_panic.download(&dev_panic, 1, st));
         JTK_HIP_TRY(hipStreamSynchronize(st));
         JTK_HIP_TRY(hipGetLastError());
         if (dev_panic) return jtk_fail(JTK_ERR_CHUNK_FAILED, "sim(): posterior lengths differ from cluster_num, or a log-probability above 0");

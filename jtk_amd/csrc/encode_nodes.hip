@@ -17,8 +17,8 @@
 
 #include "device_common.h"
 #include "guided_internal.h"
-#include "host_common.h"
 #include "jtk_lc_debug.h"
+#include "wave_util.h"
 
 namespace {
 
@@ -65,13 +65,6 @@ __global__ void __launch_bounds__(256) encode_next_kernel(uint32_t n, const jtk_
     out[t] = p;
 }
 
-// memory written by some lanes of the wave, read by others
-__device__ __forceinline__ void en_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // One wave per trial, on the second pass's ops (in their slot, rewritten in place with Ins and Del swapped).
 __global__ void __launch_bounds__(256) encode_fit_kernel(uint32_t n, const EnTrial *trials, const int32_t *status, uint8_t *slots,
                                                          const uint64_t *slot_end, const uint32_t *nops, EnFit *fit, jtk_guided_pair_t *next) {
@@ -96,7 +89,7 @@ __global__ void __launch_bounds__(256) encode_fit_kernel(uint32_t n, const EnTri
                 last_plus = q + 1;
             }
         }
-        en_wave_sync();  // the counts below read bytes that other lanes have just rewritten
+        jtk_wave_sync();  // the counts below read bytes that other lanes have just rewritten
         for (uint32_t o = 32; o; o >>= 1) {
             const uint32_t u = __shfl_xor(first, o, 64), v = __shfl_xor(last_plus, o, 64);
             first = u < first ? u : first;
@@ -206,29 +199,25 @@ extern "C" int jtk_lc_encode_nodes(size_t n_trials, const jtk_encode_trial_t *tr
         const jtk_encode_trial_t &tr = trials[live[k]];
         std::memcpy(raw.data() + win_off[k], read_bases + tr.read_off + tr.start, wins[k].len);
     }
-    struct Stream {
-        hipStream_t st = nullptr;
-        ~Stream() {
-            if (st) (void)hipStreamDestroy(st);
-        }
-    } s;
-    JTK_HIP_TRY(hipStreamCreate(&s.st));
+    DevStream s;
+    JTK_HIP_TRY(s.create());
     const hipStream_t st = s.st;
-    DevBuf d_wins, d_raw, d_win, d_flags, d_cons, d_chunk;
+    DevArr<EnWindow> d_wins;
+    DevArr<uint8_t> d_raw, d_win, d_cons, d_chunk;
+    DevArr<uint32_t> d_flags;
     {
         int rc;
         const std::vector<uint8_t> cons_v(cons_bases, cons_bases + cons_bytes), chunk_v(chunk_bases, chunk_bases + chunk_bytes);
         if ((rc = d_wins.upload(wins, st)) || (rc = d_raw.upload(raw, st)) || (rc = d_cons.upload(cons_v, st)) || (rc = d_chunk.upload(chunk_v, st)))
             return jtk_fail(rc, "device upload failed");
         JTK_HIP_TRY(d_win.alloc(win_off[n]));
-        JTK_HIP_TRY(d_flags.alloc(sizeof(uint32_t)));
-        JTK_HIP_TRY(hipMemsetAsync(d_flags.p, 0, sizeof(uint32_t), st));
-        encode_window_kernel<<<(uint32_t)n, 256, 0, st>>>((uint32_t)n, (const EnWindow *)d_wins.p, (const uint8_t *)d_raw.p, (uint8_t *)d_win.p,
-                                                          (uint32_t *)d_flags.p);
+        JTK_HIP_TRY(d_flags.alloc(1));
+        JTK_HIP_TRY(d_flags.zero(1, st));
+        encode_window_kernel<<<(uint32_t)n, 256, 0, st>>>((uint32_t)n, d_wins.cget(), d_raw.cget(), d_win.get(), d_flags.get());
         JTK_HIP_TRY(hipGetLastError());
         uint32_t flags = 0;
-        JTK_HIP_TRY(hipMemcpyAsync(windows.data(), d_win.p, win_off[n], hipMemcpyDeviceToHost, st));
-        JTK_HIP_TRY(hipMemcpyAsync(&flags, d_flags.p, sizeof(flags), hipMemcpyDeviceToHost, st));
+        JTK_HIP_TRY(d_win.download(windows.data(), win_off[n], st));
+        JTK_HIP_TRY(d_flags.download(&flags, 1, st));
         JTK_HIP_TRY(hipStreamSynchronize(st));
         JTK_HIP_TRY(hipGetLastError());
         if (flags) return jtk_fail(JTK_ERR_INVALID_ARG, "non-ACGT base in a window");
@@ -297,27 +286,32 @@ extern "C" int jtk_lc_encode_nodes(size_t n_trials, const jtk_encode_trial_t *tr
         slot_end3[k] = s3;
         en[k] = EnTrial{win_off[k], tr.chunk_off, wlen[k], clen[k], klen[k], band[k]};
     }
-    DevBuf d_pairs1, d_pairs2, d_pairs3, d_guide, d_status, d_end12, d_end3, d_slots1, d_slots2, d_slots3, d_en, d_fit;
-    DevBuf d_score[3], d_start[3], d_endv[3], d_nops[3];
+    DevArr<jtk_guided_pair_t> d_pairs1, d_pairs2, d_pairs3;
+    DevArr<uint8_t> d_guide, d_slots1, d_slots2, d_slots3;
+    DevArr<uint64_t> d_end12, d_end3;
+    DevArr<EnTrial> d_en;
+    DevArr<EnFit> d_fit;
+    DevArr<int32_t> d_status, d_score[3];
+    DevArr<uint32_t> d_start[3], d_endv[3], d_nops[3];
     {
         int rc;
         if ((rc = d_pairs1.upload(pairs, st)) || (rc = d_guide.upload(guide, st)) || (rc = d_status.upload(st_v, st)) || (rc = d_end12.upload(slot_end12, st)) ||
             (rc = d_end3.upload(slot_end3, st)) || (rc = d_en.upload(en, st)))
             return jtk_fail(rc, "device upload failed");
     }
-    JTK_HIP_TRY(d_pairs2.alloc(n * sizeof(jtk_guided_pair_t)));
-    JTK_HIP_TRY(d_pairs3.alloc(n * sizeof(jtk_guided_pair_t)));
-    JTK_HIP_TRY(d_fit.alloc(n * sizeof(EnFit)));
+    JTK_HIP_TRY(d_pairs2.alloc(n));
+    JTK_HIP_TRY(d_pairs3.alloc(n));
+    JTK_HIP_TRY(d_fit.alloc(n));
     JTK_HIP_TRY(d_slots1.alloc(s12 + 1));
     JTK_HIP_TRY(d_slots2.alloc(s12 + 1));
     JTK_HIP_TRY(d_slots3.alloc(s3 + 1));
     for (int q = 0; q < 3; q++) {
-        JTK_HIP_TRY(d_score[q].alloc(n * sizeof(int32_t)));
-        JTK_HIP_TRY(d_start[q].alloc(n * sizeof(uint32_t)));
-        JTK_HIP_TRY(d_endv[q].alloc(n * sizeof(uint32_t)));
-        JTK_HIP_TRY(d_nops[q].alloc(n * sizeof(uint32_t)));
-        JTK_HIP_TRY(hipMemsetAsync(d_score[q].p, 0, n * sizeof(int32_t), st));
-        JTK_HIP_TRY(hipMemsetAsync(d_nops[q].p, 0, n * sizeof(uint32_t), st));
+        JTK_HIP_TRY(d_score[q].alloc(n));
+        JTK_HIP_TRY(d_start[q].alloc(n));
+        JTK_HIP_TRY(d_endv[q].alloc(n));
+        JTK_HIP_TRY(d_nops[q].alloc(n));
+        JTK_HIP_TRY(d_score[q].zero(n, st));
+        JTK_HIP_TRY(d_nops[q].zero(n, st));
     }
     GuidedRun run[3];
     GuidedArea area;  // the passes run behind each other: one work area, sized for the largest of them before the first starts
@@ -329,12 +323,12 @@ extern "C" int jtk_lc_encode_nodes(size_t n_trials, const jtk_encode_trial_t *tr
     b.gap_open = EN_OPEN;
     b.gap_ext = EN_EXT;
     b.h_radius = band.data();
-    b.d_status = (int32_t *)d_status.p;
+    b.d_status = d_status.get();
     auto outputs = [&](int q) {
-        b.d_score = (int32_t *)d_score[q].p;
-        b.d_start = (uint32_t *)d_start[q].p;
-        b.d_end = (uint32_t *)d_endv[q].p;
-        b.d_nops = (uint32_t *)d_nops[q].p;
+        b.d_score = d_score[q].get();
+        b.d_start = d_start[q].get();
+        b.d_end = d_endv[q].get();
+        b.d_nops = d_nops[q].get();
     };
     b.h_xlen = wlen.data();
     b.h_ylen = clen.data();
@@ -346,49 +340,47 @@ extern "C" int jtk_lc_encode_nodes(size_t n_trials, const jtk_encode_trial_t *tr
     for (int q = 0; q < 3; q++)
         if (int rc = guided_reserve(area, run[q])) return rc;
     // the first pass
-    b.d_pairs = (const jtk_guided_pair_t *)d_pairs1.p;
-    b.d_x = (const uint8_t *)d_win.p;
-    b.d_y = (const uint8_t *)d_cons.p;
-    b.d_guide = (const uint8_t *)d_guide.p;
+    b.d_pairs = d_pairs1.cget();
+    b.d_x = d_win.cget();
+    b.d_y = d_cons.cget();
+    b.d_guide = d_guide.cget();
     b.h_xlen = wlen.data();
     b.h_ylen = clen.data();
-    b.d_slots = (uint8_t *)d_slots1.p;
-    b.d_slot_end = (const uint64_t *)d_end12.p;
+    b.d_slots = d_slots1.get();
+    b.d_slot_end = d_end12.cget();
     outputs(0);
     if (int rc = guided_enqueue(b, run[0], area, st)) return rc;
     // the second, guided by the first one's ops
     const uint32_t blocks = (uint32_t)((n + 255) / 256);
-    encode_next_kernel<<<blocks, 256, 0, st>>>((uint32_t)n, (const jtk_guided_pair_t *)d_pairs1.p, (const uint64_t *)d_end12.p, (const uint32_t *)d_nops[0].p,
-                                               (jtk_guided_pair_t *)d_pairs2.p);
+    encode_next_kernel<<<blocks, 256, 0, st>>>((uint32_t)n, d_pairs1.cget(), d_end12.cget(), d_nops[0].cget(), d_pairs2.get());
     JTK_HIP_TRY(hipGetLastError());
-    b.d_pairs = (const jtk_guided_pair_t *)d_pairs2.p;
-    b.d_guide = (const uint8_t *)d_slots1.p;
-    b.d_slots = (uint8_t *)d_slots2.p;
+    b.d_pairs = d_pairs2.cget();
+    b.d_guide = d_slots1.cget();
+    b.d_slots = d_slots2.get();
     outputs(1);
     if (int rc = guided_enqueue(b, run[1], area, st)) return rc;
     // swap, trim, count; the third pass
-    encode_fit_kernel<<<(uint32_t)((n + 3) / 4), 256, 0, st>>>((uint32_t)n, (const EnTrial *)d_en.p, (const int32_t *)d_status.p, (uint8_t *)d_slots2.p,
-                                                              (const uint64_t *)d_end12.p, (const uint32_t *)d_nops[1].p, (EnFit *)d_fit.p,
-                                                              (jtk_guided_pair_t *)d_pairs3.p);
+    encode_fit_kernel<<<(uint32_t)((n + 3) / 4), 256, 0, st>>>((uint32_t)n, d_en.cget(), d_status.cget(), d_slots2.get(), d_end12.cget(), d_nops[1].cget(),
+                                                              d_fit.get(), d_pairs3.get());
     JTK_HIP_TRY(hipGetLastError());
-    b.d_pairs = (const jtk_guided_pair_t *)d_pairs3.p;
-    b.d_x = (const uint8_t *)d_chunk.p;
-    b.d_y = (const uint8_t *)d_win.p;
-    b.d_guide = (const uint8_t *)d_slots2.p;
+    b.d_pairs = d_pairs3.cget();
+    b.d_x = d_chunk.cget();
+    b.d_y = d_win.cget();
+    b.d_guide = d_slots2.cget();
     b.h_xlen = klen.data();
     b.h_ylen = wlen.data();
-    b.d_slots = (uint8_t *)d_slots3.p;
-    b.d_slot_end = (const uint64_t *)d_end3.p;
+    b.d_slots = d_slots3.get();
+    b.d_slot_end = d_end3.cget();
     outputs(2);
     if (int rc = guided_enqueue(b, run[2], area, st)) return rc;
     // ---- 5. the results
     std::vector<EnFit> fit(n);
     std::vector<int32_t> score(n);
     std::vector<uint32_t> nops(n);
-    JTK_HIP_TRY(hipMemcpyAsync(fit.data(), d_fit.p, n * sizeof(EnFit), hipMemcpyDeviceToHost, st));
-    JTK_HIP_TRY(hipMemcpyAsync(score.data(), d_score[2].p, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    JTK_HIP_TRY(hipMemcpyAsync(nops.data(), d_nops[2].p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    JTK_HIP_TRY(hipMemcpyAsync(st_v.data(), d_status.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    JTK_HIP_TRY(d_fit.download(fit.data(), n, st));
+    JTK_HIP_TRY(d_score[2].download(score.data(), n, st));
+    JTK_HIP_TRY(d_nops[2].download(nops.data(), n, st));
+    JTK_HIP_TRY(d_status.download(st_v.data(), n, st));
     JTK_HIP_TRY(hipStreamSynchronize(st));
     JTK_HIP_TRY(hipGetLastError());
     for (int q = 0; q < 3; q++)
@@ -406,13 +398,12 @@ extern "C" int jtk_lc_encode_nodes(size_t n_trials, const jtk_encode_trial_t *tr
     const uint64_t total = dst_off[n];
     if (total > ops_cap || (total && !ops_out)) return jtk_fail(JTK_ERR_INVALID_ARG, "ops_cap is smaller than the ops of the batch");
     if (total) {
-        DevBuf d_off, d_out;
+        DevArr<uint64_t> d_off;
+        DevArr<uint8_t> d_out;
         if (int rc2 = d_off.upload(dst_off, st)) return jtk_fail(rc2, "device upload failed");
         JTK_HIP_TRY(d_out.alloc(total));
-        if (int rc2 = guided_pack(n, (const uint8_t *)d_slots3.p, (const uint64_t *)d_end3.p, (const uint32_t *)d_nops[2].p, (const uint64_t *)d_off.p,
-                                  (uint8_t *)d_out.p, st))
-            return rc2;
-        JTK_HIP_TRY(hipMemcpyAsync(ops_out, d_out.p, total, hipMemcpyDeviceToHost, st));
+        if (int rc2 = guided_pack(n, d_slots3.cget(), d_end3.cget(), d_nops[2].cget(), d_off.cget(), d_out.get(), st)) return rc2;
+        JTK_HIP_TRY(d_out.download(ops_out, total, st));
         JTK_HIP_TRY(hipStreamSynchronize(st));
         JTK_HIP_TRY(hipGetLastError());
     }

@@ -32,8 +32,9 @@
 #include <rocprim/device/device_select.hpp>
 
 #include "device_common.h"
-#include "host_common.h"
 #include "jtk_lc_debug.h"
+#include "prim_host.h"
+#include "wave_util.h"
 
 namespace {
 
@@ -73,12 +74,6 @@ struct FillArgs {
     const uint64_t *dbg_ops_off;
 };
 
-// memory written by some lanes of the wave, read by others
-__device__ __forceinline__ void fc_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 __device__ __forceinline__ int32_t fc_max(int32_t a, int32_t b) { return a > b ? a : b; }
 
 // One (target, query) pair by one wave; `area` holds fc_need(n, m) bytes (LDS or global, 8-byte aligned).
@@ -127,7 +122,7 @@ __device__ void fc_pair(const FillArgs &a, uint64_t pi, uint32_t t, uint32_t q, 
             rows[w + j] = j ? 0 : FC_MIN_ALN;
             rows[2 * w + j] = FC_MIN_ALN;
         }
-        fc_wave_sync();
+        jtk_wave_sync();
         // the end cell: (i, m) for i = 0 ..= n, then (n, j) for j = 0 ..= m; the last maximum wins, in the cell and in the chain
         int32_t best = 0;
         uint32_t best_r = 0, best_q = m, best_state = 1;  // cell (0, m) = (MIN, 0, MIN); m >= 1 here
@@ -183,7 +178,7 @@ __device__ void fc_pair(const FillArgs &a, uint64_t pi, uint32_t t, uint32_t q, 
                 const uint32_t other = (uint32_t)__shfl_down((int)nib, 1, 64);  // column j + 1 shares the byte of an odd j
                 if (active && !(lane & 1u)) bits[(uint64_t)(i - 1) * row_bytes + ((j - 1) >> 1)] = (uint8_t)(nib | (other << 4));
             }
-            fc_wave_sync();
+            jtk_wave_sync();
             const int32_t e0 = cur[m], e1 = cur[w + m], e2 = cur[2 * w + m];
             const int32_t ev = fc_max(e0, fc_max(e1, e2));
             if (ev >= best) {
@@ -256,7 +251,7 @@ __device__ void fc_pair(const FillArgs &a, uint64_t pi, uint32_t t, uint32_t q, 
         if (r != 0) push(FC_DEL, r);
         if (c != 0) push(FC_INS, c);
         push(3, 0);  // flushes the open run
-        fc_wave_sync();
+        jtk_wave_sync();
         const uint32_t min_nm = min_match < m ? min_match : m;
         pass = min_nm <= matched && 1 <= dist && proper;
         // ---- get_pileup's walk, twice: the records are counted, one reservation is made, then they are written
@@ -322,7 +317,7 @@ __device__ void fc_pair(const FillArgs &a, uint64_t pi, uint32_t t, uint32_t q, 
             a.dbg_nops[pi] = n_runs;
         }
     }
-    fc_wave_sync();  // the area is the next pair's
+    jtk_wave_sync();  // the area is the next pair's
 }
 
 // Waves take the pairs 64 at a time, a lane looks up whether its pair is this launch's kind, the wave then does them in turn.
@@ -438,30 +433,11 @@ __global__ void summarise_kernel(uint64_t n_rec, const uint64_t *hi, const uint6
     }
 }
 
-uint32_t fc_blocks(uint64_t n, uint32_t per, uint32_t cap) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n + per - 1) / per, 1), cap); }
 unsigned fc_bits(uint64_t top) {  // bits that hold 0 ..= top
     unsigned b = 1;
     while (b < 64 && (top >> b)) b++;
     return b;
 }
-
-struct Stream {
-    hipStream_t st = nullptr;
-    ~Stream() {
-        if (st) (void)hipStreamDestroy(st);
-    }
-};
-struct Temp {  // rocprim's temporary storage, grown as needed
-    DevBuf buf;
-    size_t bytes = 0;
-    int need(size_t n) {
-        if (n > bytes) {
-            JTK_HIP_TRY(buf.alloc(n));
-            bytes = n;
-        }
-        return 0;
-    }
-};
 
 // The reads on the host, then on the device.
 struct Reads {
@@ -469,7 +445,9 @@ struct Reads {
     std::vector<uint32_t> ck, kid, read_of, order, seg_start;
     std::vector<int64_t> start, end;
     std::vector<uint64_t> key_chunk, key_cluster;
-    DevBuf d_off, d_ck, d_kid, d_start, d_end;
+    DevArr<uint64_t> d_off;
+    DevArr<uint32_t> d_ck, d_kid;
+    DevArr<int64_t> d_start, d_end;
 };
 
 int fc_check(size_t n_reads, const uint64_t *node_off, const jtk_fill_node_t *nodes) {
@@ -535,18 +513,31 @@ int fc_upload(Reads &R, const uint64_t *node_off, hipStream_t st) {
     return 0;
 }
 
+// the arguments both entry points give the pair kernel: the pair list and the reads
+FillArgs fc_args(const Reads &R, uint64_t n_pairs, const uint64_t *d_pairs) {
+    FillArgs a{};
+    a.n_pairs = n_pairs;
+    a.pairs = d_pairs;
+    a.node_off = R.d_off.cget();
+    a.ck = R.d_ck.cget();
+    a.kid = R.d_kid.cget();
+    a.start = R.d_start.cget();
+    a.end = R.d_end.cget();
+    return a;
+}
+
 // both launches of the pair kernel over the list in a.pairs; the work area of the second is sized for a target of
 // `max_target` nodes against a query of `max_query`
 int fc_run_pairs(FillArgs &a, uint32_t max_target, uint32_t max_query, hipStream_t st) {
     if (!a.n_pairs) return 0;
-    pair_kernel<false><<<fc_blocks(a.n_pairs, 64 * FC_WAVES, FC_GRID), FC_WAVES * 64, FC_WAVES * FC_LDS_PER_WAVE, st>>>(a);
+    pair_kernel<false><<<jtk_blocks(a.n_pairs, 64 * FC_WAVES, FC_GRID), FC_WAVES * 64, FC_WAVES * FC_LDS_PER_WAVE, st>>>(a);
     JTK_HIP_TRY(hipGetLastError());
     const uint64_t need = (fc_need(max_target, max_query) + 7) & ~7ull;
     if (need > FC_LDS_PER_WAVE) {  // some pair may be too large for the LDS launch
         const uint32_t waves = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(FC_WORK_BYTES / need, 1), FC_LARGE_WAVES);
-        DevBuf d_work;
+        DevArr<uint8_t> d_work;
         JTK_HIP_TRY(d_work.alloc(need * waves));
-        a.work = (uint8_t *)d_work.p;
+        a.work = d_work.get();
         a.work_stride = need;
         pair_kernel<true><<<waves, 64, 0, st>>>(a);
         JTK_HIP_TRY(hipGetLastError());
@@ -574,21 +565,12 @@ extern "C" int jtk_lc_fill_candidates(size_t n_reads, const uint64_t *node_off, 
     Reads R;
     fc_index(R, n_reads, node_off, nodes, target);
     const uint64_t n_slots = (uint64_t)R.n_nodes + R.n_reads;
-    Stream s;
-    JTK_HIP_TRY(hipStreamCreate(&s.st));
+    DevStream s;
+    JTK_HIP_TRY(s.create(4));
     const hipStream_t st = s.st;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    struct EvGuard {
-        hipEvent_t *e;
-        ~EvGuard() {
-            for (int i = 0; i < 4; i++)
-                if (e[i]) (void)hipEventDestroy(e[i]);
-        }
-    } ev_guard{ev};
-    for (hipEvent_t &e : ev) JTK_HIP_TRY(hipEventCreate(&e));
-    JTK_HIP_TRY(hipEventRecord(ev[0], st));
+    JTK_HIP_TRY(hipEventRecord(s.ev[0], st));
     if (int rc = fc_upload(R, node_off, st)) return rc;
-    Temp tmp;
+    RocTemp tmp;
     // ---- 1. the pairs
     std::vector<uint64_t> rec_off((size_t)R.n_nodes + 1, 0);
     for (uint32_t e = 0; e < R.n_nodes; e++) {
@@ -597,69 +579,61 @@ extern "C" int jtk_lc_fill_candidates(size_t n_reads, const uint64_t *node_off, 
     }
     const uint64_t n_emit = rec_off[R.n_nodes];
     uint64_t n_pairs = 0;
-    DevBuf d_pairs;
+    DevArr<uint64_t> d_pairs;
     if (n_emit) {
-        DevBuf d_read_of, d_order, d_seg, d_rec_off, d_raw, d_sorted, d_count;
+        DevArr<uint32_t> d_read_of, d_order, d_seg;
+        DevArr<uint64_t> d_rec_off, d_raw, d_sorted, d_count;
         int rc;
         if ((rc = d_read_of.upload(R.read_of, st)) || (rc = d_order.upload(R.order, st)) || (rc = d_seg.upload(R.seg_start, st)) ||
             (rc = d_rec_off.upload(rec_off, st)))
             return jtk_fail(rc, "device upload failed");
-        JTK_HIP_TRY(d_raw.alloc(n_emit * sizeof(uint64_t)));
-        JTK_HIP_TRY(d_sorted.alloc(n_emit * sizeof(uint64_t)));
-        JTK_HIP_TRY(d_pairs.alloc(n_emit * sizeof(uint64_t)));
-        JTK_HIP_TRY(d_count.alloc(sizeof(uint64_t)));
-        pair_emit_kernel<<<fc_blocks(R.n_nodes, 4, 4096), 256, 0, st>>>(R.n_nodes, (const uint32_t *)R.d_kid.p, (const uint32_t *)d_read_of.p,
-                                                                       (const uint32_t *)d_order.p, (const uint32_t *)d_seg.p,
-                                                                       (const uint64_t *)d_rec_off.p, (uint64_t *)d_raw.p);
+        JTK_HIP_TRY(d_raw.alloc(n_emit));
+        JTK_HIP_TRY(d_sorted.alloc(n_emit));
+        JTK_HIP_TRY(d_pairs.alloc(n_emit));
+        JTK_HIP_TRY(d_count.alloc(1));
+        pair_emit_kernel<<<jtk_blocks(R.n_nodes, 4, 4096), 256, 0, st>>>(R.n_nodes, R.d_kid.cget(), d_read_of.cget(), d_order.cget(), d_seg.cget(),
+                                                                        d_rec_off.cget(), d_raw.get());
         const unsigned end_bit = 32 + fc_bits(R.n_reads);
-        size_t need = 0;
-        JTK_HIP_TRY(rocprim::radix_sort_keys(nullptr, need, (const uint64_t *)d_raw.p, (uint64_t *)d_sorted.p, (size_t)n_emit, 0u, end_bit, st));
-        if (int rc2 = tmp.need(need)) return rc2;
-        JTK_HIP_TRY(rocprim::radix_sort_keys(tmp.buf.p, need, (const uint64_t *)d_raw.p, (uint64_t *)d_sorted.p, (size_t)n_emit, 0u, end_bit, st));
-        need = 0;
-        JTK_HIP_TRY(rocprim::unique(nullptr, need, (const uint64_t *)d_sorted.p, (uint64_t *)d_pairs.p, (uint64_t *)d_count.p, (size_t)n_emit,
-                                    rocprim::equal_to<uint64_t>(), st));
-        if (int rc2 = tmp.need(need)) return rc2;
-        JTK_HIP_TRY(rocprim::unique(tmp.buf.p, need, (const uint64_t *)d_sorted.p, (uint64_t *)d_pairs.p, (uint64_t *)d_count.p, (size_t)n_emit,
-                                    rocprim::equal_to<uint64_t>(), st));
-        JTK_HIP_TRY(hipMemcpyAsync(&n_pairs, d_count.p, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        JTK_HIP_TRY(tmp.run([&](void *t, size_t &bytes) {
+            return rocprim::radix_sort_keys(t, bytes, d_raw.cget(), d_sorted.get(), (size_t)n_emit, 0u, end_bit, st);
+        }));
+        JTK_HIP_TRY(tmp.run([&](void *t, size_t &bytes) {
+            return rocprim::unique(t, bytes, d_sorted.cget(), d_pairs.get(), d_count.get(), (size_t)n_emit, rocprim::equal_to<uint64_t>(), st);
+        }));
+        JTK_HIP_TRY(d_count.download(&n_pairs, 1, st));
         JTK_HIP_TRY(hipStreamSynchronize(st));
         JTK_HIP_TRY(hipGetLastError());
     }
     // ---- 2. the pair kernel; the record list is sized by a guess and the launches repeat once if it was too small
-    DevBuf d_cov, d_hi, d_lo, d_val, d_rec_count;
-    JTK_HIP_TRY(d_cov.alloc(std::max<uint64_t>(n_slots, 1) * sizeof(uint32_t)));
-    JTK_HIP_TRY(d_rec_count.alloc(sizeof(unsigned long long)));
+    DevArr<uint32_t> d_cov;
+    DevArr<uint64_t> d_hi, d_lo;
+    DevArr<int64_t> d_val;
+    DevArr<unsigned long long> d_rec_count;
+    JTK_HIP_TRY(d_cov.alloc(n_slots));
+    JTK_HIP_TRY(d_rec_count.alloc(1));
     uint64_t rec_cap = 4 * n_pairs + 1024, n_rec = 0;
     float pair_ms = 0.f;
     for (int attempt = 0;; attempt++) {
-        JTK_HIP_TRY(d_hi.alloc(rec_cap * sizeof(uint64_t)));
-        JTK_HIP_TRY(d_lo.alloc(rec_cap * sizeof(uint64_t)));
-        JTK_HIP_TRY(d_val.alloc(rec_cap * sizeof(int64_t)));
-        JTK_HIP_TRY(hipMemsetAsync(d_cov.p, 0, n_slots * sizeof(uint32_t), st));
-        JTK_HIP_TRY(hipMemsetAsync(d_rec_count.p, 0, sizeof(unsigned long long), st));
-        FillArgs a{};
-        a.n_pairs = n_pairs;
-        a.pairs = (const uint64_t *)d_pairs.p;
-        a.node_off = (const uint64_t *)R.d_off.p;
-        a.ck = (const uint32_t *)R.d_ck.p;
-        a.kid = (const uint32_t *)R.d_kid.p;
-        a.start = (const int64_t *)R.d_start.p;
-        a.end = (const int64_t *)R.d_end.p;
-        a.coverage = (uint32_t *)d_cov.p;
-        a.rec_hi = (uint64_t *)d_hi.p;
-        a.rec_lo = (uint64_t *)d_lo.p;
-        a.rec_val = (int64_t *)d_val.p;
+        JTK_HIP_TRY(d_hi.alloc(rec_cap));
+        JTK_HIP_TRY(d_lo.alloc(rec_cap));
+        JTK_HIP_TRY(d_val.alloc(rec_cap));
+        JTK_HIP_TRY(d_cov.zero(n_slots, st));
+        JTK_HIP_TRY(d_rec_count.zero(1, st));
+        FillArgs a = fc_args(R, n_pairs, d_pairs.cget());
+        a.coverage = d_cov.get();
+        a.rec_hi = d_hi.get();
+        a.rec_lo = d_lo.get();
+        a.rec_val = d_val.get();
         a.rec_cap = rec_cap;
-        a.rec_count = (unsigned long long *)d_rec_count.p;
-        JTK_HIP_TRY(hipEventRecord(ev[1], st));
+        a.rec_count = d_rec_count.get();
+        JTK_HIP_TRY(hipEventRecord(s.ev[1], st));
         if (int rc = fc_run_pairs(a, R.max_target_nodes, R.max_nodes, st)) return rc;
-        JTK_HIP_TRY(hipEventRecord(ev[2], st));
+        JTK_HIP_TRY(hipEventRecord(s.ev[2], st));
         unsigned long long got = 0;
-        JTK_HIP_TRY(hipMemcpyAsync(&got, d_rec_count.p, sizeof(got), hipMemcpyDeviceToHost, st));
+        JTK_HIP_TRY(d_rec_count.download(&got, 1, st));
         JTK_HIP_TRY(hipStreamSynchronize(st));
         JTK_HIP_TRY(hipGetLastError());
-        JTK_HIP_TRY(hipEventElapsedTime(&pair_ms, ev[1], ev[2]));
+        JTK_HIP_TRY(s.elapsed(1, 2, &pair_ms));
         n_rec = got;
         if (n_rec <= rec_cap) break;
         if (attempt) return jtk_fail(JTK_ERR_CHUNK_FAILED, "the insertion records changed between two runs");
@@ -667,65 +641,57 @@ extern "C" int jtk_lc_fill_candidates(size_t n_reads, const uint64_t *node_off, 
     }
     if (n_rec >= 0xffffffffull) return jtk_fail(JTK_ERR_UNSUPPORTED, "2^32 - 1 or more insertion records");
     // ---- 3. thresholds, the records in order, the candidates
-    DevBuf d_thr, d_per_read;
-    JTK_HIP_TRY(d_thr.alloc(std::max<size_t>(R.n_reads, 1) * sizeof(uint32_t)));
-    JTK_HIP_TRY(d_per_read.alloc(std::max<size_t>(R.n_reads, 1) * sizeof(uint32_t)));
-    JTK_HIP_TRY(hipMemsetAsync(d_per_read.p, 0, std::max<size_t>(R.n_reads, 1) * sizeof(uint32_t), st));
-    ins_thr_kernel<<<fc_blocks(R.n_reads, 256, 4096), 256, 0, st>>>(R.n_reads, (const uint64_t *)R.d_off.p, (const uint32_t *)d_cov.p, (uint32_t *)d_thr.p);
+    DevArr<uint32_t> d_thr, d_per_read;
+    JTK_HIP_TRY(d_thr.alloc(R.n_reads));
+    JTK_HIP_TRY(d_per_read.alloc(R.n_reads));
+    JTK_HIP_TRY(d_per_read.zero(std::max<size_t>(R.n_reads, 1), st));
+    ins_thr_kernel<<<jtk_blocks(R.n_reads, 256, 4096), 256, 0, st>>>(R.n_reads, R.d_off.cget(), d_cov.cget(), d_thr.get());
     uint64_t total = 0;
-    DevBuf d_cands;
+    DevArr<jtk_fill_cand_t> d_cands;
     std::vector<uint32_t> per_read(R.n_reads, 0);
     if (n_rec) {
-        DevBuf d_iota, d_lo_s, d_perm1, d_hi_g, d_hi_s, d_perm, d_flag, d_pos, d_key_chunk, d_key_cluster;
+        DevArr<uint32_t> d_iota, d_perm1, d_perm, d_flag, d_pos;
+        DevArr<uint64_t> d_lo_s, d_hi_g, d_hi_s, d_key_chunk, d_key_cluster;
         int rc;
         if ((rc = d_key_chunk.upload(R.key_chunk, st)) || (rc = d_key_cluster.upload(R.key_cluster, st))) return jtk_fail(rc, "device upload failed");
-        JTK_HIP_TRY(d_iota.alloc(n_rec * sizeof(uint32_t)));
-        JTK_HIP_TRY(d_perm1.alloc(n_rec * sizeof(uint32_t)));
-        JTK_HIP_TRY(d_perm.alloc(n_rec * sizeof(uint32_t)));
-        JTK_HIP_TRY(d_lo_s.alloc(n_rec * sizeof(uint64_t)));
-        JTK_HIP_TRY(d_hi_g.alloc(n_rec * sizeof(uint64_t)));
-        JTK_HIP_TRY(d_hi_s.alloc(n_rec * sizeof(uint64_t)));
-        JTK_HIP_TRY(d_flag.alloc((n_rec + 1) * sizeof(uint32_t)));
-        JTK_HIP_TRY(d_pos.alloc((n_rec + 1) * sizeof(uint32_t)));
-        const uint32_t rec_grid = fc_blocks(n_rec, 256, 4096);
-        fc_iota_kernel<<<rec_grid, 256, 0, st>>>(n_rec, (uint32_t *)d_iota.p);
-        size_t need = 0;
+        JTK_HIP_TRY(d_iota.alloc(n_rec));
+        JTK_HIP_TRY(d_perm1.alloc(n_rec));
+        JTK_HIP_TRY(d_perm.alloc(n_rec));
+        JTK_HIP_TRY(d_lo_s.alloc(n_rec));
+        JTK_HIP_TRY(d_hi_g.alloc(n_rec));
+        JTK_HIP_TRY(d_hi_s.alloc(n_rec));
+        JTK_HIP_TRY(d_flag.alloc(n_rec + 1));
+        JTK_HIP_TRY(d_pos.alloc(n_rec + 1));
+        const uint32_t rec_grid = jtk_blocks(n_rec, 256, 4096);
+        fc_iota_kernel<<<rec_grid, 256, 0, st>>>(n_rec, d_iota.get());
         const unsigned lo_bits = 2 + fc_bits(R.n_keys), hi_bits = 17 + fc_bits(R.n_reads);
         // least significant part first; both sorts are stable.  Bit 0 of lo (an offset is present) is no part of the key.
-        JTK_HIP_TRY(rocprim::radix_sort_pairs(nullptr, need, (const uint64_t *)d_lo.p, (uint64_t *)d_lo_s.p, (const uint32_t *)d_iota.p,
-                                              (uint32_t *)d_perm1.p, (size_t)n_rec, 1u, lo_bits, st));
-        if (int rc2 = tmp.need(need)) return rc2;
-        JTK_HIP_TRY(rocprim::radix_sort_pairs(tmp.buf.p, need, (const uint64_t *)d_lo.p, (uint64_t *)d_lo_s.p, (const uint32_t *)d_iota.p,
-                                              (uint32_t *)d_perm1.p, (size_t)n_rec, 1u, lo_bits, st));
-        fc_gather_kernel<<<rec_grid, 256, 0, st>>>(n_rec, (const uint32_t *)d_perm1.p, (const uint64_t *)d_hi.p, (uint64_t *)d_hi_g.p);
-        need = 0;
-        JTK_HIP_TRY(rocprim::radix_sort_pairs(nullptr, need, (const uint64_t *)d_hi_g.p, (uint64_t *)d_hi_s.p, (const uint32_t *)d_perm1.p,
-                                              (uint32_t *)d_perm.p, (size_t)n_rec, 0u, hi_bits, st));
-        if (int rc2 = tmp.need(need)) return rc2;
-        JTK_HIP_TRY(rocprim::radix_sort_pairs(tmp.buf.p, need, (const uint64_t *)d_hi_g.p, (uint64_t *)d_hi_s.p, (const uint32_t *)d_perm1.p,
-                                              (uint32_t *)d_perm.p, (size_t)n_rec, 0u, hi_bits, st));
+        JTK_HIP_TRY(tmp.run([&](void *t, size_t &bytes) {
+            return rocprim::radix_sort_pairs(t, bytes, d_lo.cget(), d_lo_s.get(), d_iota.cget(), d_perm1.get(), (size_t)n_rec, 1u, lo_bits, st);
+        }));
+        fc_gather_kernel<<<rec_grid, 256, 0, st>>>(n_rec, d_perm1.cget(), d_hi.cget(), d_hi_g.get());
+        JTK_HIP_TRY(tmp.run([&](void *t, size_t &bytes) {
+            return rocprim::radix_sort_pairs(t, bytes, d_hi_g.cget(), d_hi_s.get(), d_perm1.cget(), d_perm.get(), (size_t)n_rec, 0u, hi_bits, st);
+        }));
         auto summarise = [&](int write) {
-            summarise_kernel<<<rec_grid, 256, 0, st>>>(n_rec, (const uint64_t *)d_hi_s.p, (const uint64_t *)d_lo.p, (const uint32_t *)d_perm.p,
-                                                       (const int64_t *)d_val.p, (const uint64_t *)R.d_off.p, (const int64_t *)R.d_start.p,
-                                                       (const int64_t *)R.d_end.p, (const uint32_t *)d_thr.p, (const uint64_t *)d_key_chunk.p,
-                                                       (const uint64_t *)d_key_cluster.p, write, (uint32_t *)d_flag.p, (const uint32_t *)d_pos.p,
-                                                       (jtk_fill_cand_t *)d_cands.p, (uint32_t *)d_per_read.p);
+            summarise_kernel<<<rec_grid, 256, 0, st>>>(n_rec, d_hi_s.cget(), d_lo.cget(), d_perm.cget(), d_val.cget(), R.d_off.cget(), R.d_start.cget(),
+                                                       R.d_end.cget(), d_thr.cget(), d_key_chunk.cget(), d_key_cluster.cget(), write, d_flag.get(),
+                                                       d_pos.cget(), d_cands.get(), d_per_read.get());
         };
-        JTK_HIP_TRY(hipMemsetAsync(d_flag.p, 0, (n_rec + 1) * sizeof(uint32_t), st));
+        JTK_HIP_TRY(d_flag.zero(n_rec + 1, st));
         summarise(0);
-        need = 0;
-        JTK_HIP_TRY(rocprim::exclusive_scan(nullptr, need, (const uint32_t *)d_flag.p, (uint32_t *)d_pos.p, 0u, (size_t)n_rec + 1, rocprim::plus<uint32_t>(), st));
-        if (int rc2 = tmp.need(need)) return rc2;
-        JTK_HIP_TRY(rocprim::exclusive_scan(tmp.buf.p, need, (const uint32_t *)d_flag.p, (uint32_t *)d_pos.p, 0u, (size_t)n_rec + 1, rocprim::plus<uint32_t>(), st));
+        JTK_HIP_TRY(tmp.run([&](void *t, size_t &bytes) {
+            return rocprim::exclusive_scan(t, bytes, d_flag.cget(), d_pos.get(), 0u, (size_t)n_rec + 1, rocprim::plus<uint32_t>(), st);
+        }));
         uint32_t total32 = 0;
-        JTK_HIP_TRY(hipMemcpyAsync(&total32, (const uint32_t *)d_pos.p + n_rec, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        JTK_HIP_TRY(d_pos.download(&total32, 1, st, n_rec));
         JTK_HIP_TRY(hipStreamSynchronize(st));
         JTK_HIP_TRY(hipGetLastError());
         total = total32;
         if (total) {
-            JTK_HIP_TRY(d_cands.alloc(total * sizeof(jtk_fill_cand_t)));
+            JTK_HIP_TRY(d_cands.alloc(total));
             summarise(1);
-            JTK_HIP_TRY(hipMemcpyAsync(per_read.data(), d_per_read.p, (size_t)R.n_reads * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            JTK_HIP_TRY(d_per_read.download(per_read.data(), R.n_reads, st));
             JTK_HIP_TRY(hipStreamSynchronize(st));
             JTK_HIP_TRY(hipGetLastError());
         }
@@ -736,14 +702,14 @@ extern "C" int jtk_lc_fill_candidates(size_t n_reads, const uint64_t *node_off, 
     }
     std::vector<uint32_t> cov_v(n_slots), thr_v(R.n_reads);
     std::vector<jtk_fill_cand_t> cand_v(total);
-    JTK_HIP_TRY(hipMemcpyAsync(cov_v.data(), d_cov.p, n_slots * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    if (R.n_reads) JTK_HIP_TRY(hipMemcpyAsync(thr_v.data(), d_thr.p, (size_t)R.n_reads * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    if (total) JTK_HIP_TRY(hipMemcpyAsync(cand_v.data(), d_cands.p, total * sizeof(jtk_fill_cand_t), hipMemcpyDeviceToHost, st));
-    JTK_HIP_TRY(hipEventRecord(ev[3], st));
+    JTK_HIP_TRY(d_cov.download(cov_v.data(), n_slots, st));
+    if (R.n_reads) JTK_HIP_TRY(d_thr.download(thr_v.data(), R.n_reads, st));
+    if (total) JTK_HIP_TRY(d_cands.download(cand_v.data(), total, st));
+    JTK_HIP_TRY(hipEventRecord(s.ev[3], st));
     JTK_HIP_TRY(hipStreamSynchronize(st));
     JTK_HIP_TRY(hipGetLastError());
     float ms = 0.f;
-    JTK_HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[3]));
+    JTK_HIP_TRY(s.elapsed(0, 3, &ms));
     g_fill_timing[0] = (double)n_pairs;
     g_fill_timing[1] = (double)n_rec;
     g_fill_timing[2] = ms;
@@ -778,45 +744,40 @@ extern "C" int jtk_lc_debug_fill_pairs(size_t n_reads, const uint64_t *node_off,
     if (int rc = jtk_require_device(device)) return rc;
     Reads R;
     fc_index(R, n_reads, node_off, nodes, nullptr);
-    Stream s;
-    JTK_HIP_TRY(hipStreamCreate(&s.st));
+    DevStream s;
+    JTK_HIP_TRY(s.create());
     const hipStream_t st = s.st;
     if (int rc = fc_upload(R, node_off, st)) return rc;
-    DevBuf d_pairs, d_slot_off, d_dir, d_score, d_pass, d_ops, d_nops;
+    DevArr<uint64_t> d_pairs, d_slot_off;
+    DevArr<int32_t> d_dir, d_score;
+    DevArr<uint8_t> d_pass;
+    DevArr<uint32_t> d_ops, d_nops;
     {
         int rc;
         if ((rc = d_pairs.upload(pairs, st)) || (rc = d_slot_off.upload(slot_off, st))) return jtk_fail(rc, "device upload failed");
     }
-    const size_t np = std::max<size_t>(n_pairs, 1);
-    JTK_HIP_TRY(d_dir.alloc(np * sizeof(int32_t)));
-    JTK_HIP_TRY(d_score.alloc(np * sizeof(int32_t)));
-    JTK_HIP_TRY(d_pass.alloc(np));
-    JTK_HIP_TRY(d_nops.alloc(np * sizeof(uint32_t)));
-    JTK_HIP_TRY(d_ops.alloc(std::max<uint64_t>(slot_off[n_pairs], 1) * sizeof(uint32_t)));
-    FillArgs a{};
-    a.n_pairs = n_pairs;
-    a.pairs = (const uint64_t *)d_pairs.p;
-    a.node_off = (const uint64_t *)R.d_off.p;
-    a.ck = (const uint32_t *)R.d_ck.p;
-    a.kid = (const uint32_t *)R.d_kid.p;
-    a.start = (const int64_t *)R.d_start.p;
-    a.end = (const int64_t *)R.d_end.p;
-    a.dbg_dir = (int32_t *)d_dir.p;
-    a.dbg_score = (int32_t *)d_score.p;
-    a.dbg_pass = (uint8_t *)d_pass.p;
-    a.dbg_ops = (uint32_t *)d_ops.p;
-    a.dbg_nops = (uint32_t *)d_nops.p;
-    a.dbg_ops_off = (const uint64_t *)d_slot_off.p;
+    JTK_HIP_TRY(d_dir.alloc(n_pairs));
+    JTK_HIP_TRY(d_score.alloc(n_pairs));
+    JTK_HIP_TRY(d_pass.alloc(n_pairs));
+    JTK_HIP_TRY(d_nops.alloc(n_pairs));
+    JTK_HIP_TRY(d_ops.alloc(slot_off[n_pairs]));
+    FillArgs a = fc_args(R, n_pairs, d_pairs.cget());
+    a.dbg_dir = d_dir.get();
+    a.dbg_score = d_score.get();
+    a.dbg_pass = d_pass.get();
+    a.dbg_ops = d_ops.get();
+    a.dbg_nops = d_nops.get();
+    a.dbg_ops_off = d_slot_off.cget();
     if (int rc = fc_run_pairs(a, max_t, max_q, st)) return rc;
     std::vector<int32_t> dir_v(n_pairs), score_v(n_pairs);
     std::vector<uint8_t> pass_v(n_pairs);
     std::vector<uint32_t> nops_v(n_pairs), ops_v(slot_off[n_pairs]);
     if (n_pairs) {
-        JTK_HIP_TRY(hipMemcpyAsync(dir_v.data(), d_dir.p, n_pairs * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        JTK_HIP_TRY(hipMemcpyAsync(score_v.data(), d_score.p, n_pairs * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        JTK_HIP_TRY(hipMemcpyAsync(pass_v.data(), d_pass.p, n_pairs, hipMemcpyDeviceToHost, st));
-        JTK_HIP_TRY(hipMemcpyAsync(nops_v.data(), d_nops.p, n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        JTK_HIP_TRY(hipMemcpyAsync(ops_v.data(), d_ops.p, ops_v.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        JTK_HIP_TRY(d_dir.download(dir_v.data(), n_pairs, st));
+        JTK_HIP_TRY(d_score.download(score_v.data(), n_pairs, st));
+        JTK_HIP_TRY(d_pass.download(pass_v.data(), n_pairs, st));
+        JTK_HIP_TRY(d_nops.download(nops_v.data(), n_pairs, st));
+        JTK_HIP_TRY(d_ops.download(ops_v.data(), ops_v.size(), st));
     }
     JTK_HIP_TRY(hipStreamSynchronize(st));
     JTK_HIP_TRY(hipGetLastError());

@@ -6,7 +6,7 @@
 // A round is five launches on one stream, and only the count of pile-ups still active crosses to the host:
 //   1. gp_begin_kernel: a pile-up whose template has nothing to scan stops; the others get their gain table zeroed.
 //   2. gp_fill_kernel, one wave per (pile-up, read), slice behind slice of the work area:
-//        the band from the read's current ops (the walk and the scans of guided_rows_kernel);
+//        the band from the read's current ops (jtk_band_rows, wave_util.h);
 //        the forward fill, rows in order, lanes over the columns, 64 at a time: the left neighbour is a prefix minimum with slope
 //        +1, F(i, j) = j + min_{k <= j} (g(k) - k), g the better of the two moves from the row above (six __shfl_up steps and a
 //        carry between the pieces).  F is kept whole as 16-bit cells (n + m <= 64,000; 65,535 is +infinity), the two rows the
@@ -26,8 +26,8 @@
 #include <vector>
 
 #include "guided_internal.h"
-#include "host_common.h"
 #include "jtk_lc_debug.h"
+#include "wave_util.h"
 
 namespace {
 
@@ -89,11 +89,6 @@ struct GpArgs {
     int final_pass;
 };
 
-__device__ __forceinline__ void gp_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 __device__ __forceinline__ int32_t gp_min(int32_t a, int32_t b) { return a < b ? a : b; }
 __device__ __forceinline__ int32_t gp_ld(const uint16_t *p) {
     const uint32_t v = *p;
@@ -109,82 +104,6 @@ __device__ __forceinline__ int32_t gp_scan_min(int32_t t, uint32_t lane) {
     return t;
 }
 __device__ __forceinline__ uint8_t gp_base(uint32_t b) { return b == 0 ? 'A' : (b == 1 ? 'C' : (b == 2 ? 'G' : 'T')); }
-
-// The guide's path and the band: lo[i] = first column of row i, off[i] = cells in the rows above it (off[n + 1] = all).
-// Returns the widest row.  The logic of guided_rows_kernel (guided.hip).
-__device__ uint32_t gp_rows(uint32_t n, uint32_t m, uint32_t radius, const uint8_t *guide, uint32_t guide_len, uint32_t *lo, uint32_t *hi,
-                            uint32_t lane) {
-    const uint32_t longest = n > m ? n : m;
-    const uint32_t r = radius > longest ? longest + 1 : radius;
-    uint32_t i = 0, j = 0;
-    if (lane == 0) lo[0] = 0;
-    for (uint32_t base = 0; base < guide_len; base += 64) {
-        const uint32_t cnt = guide_len - base < 64u ? guide_len - base : 64u;
-        const int mine = lane < cnt ? (int)guide[base + lane] : 2;
-        for (uint32_t t = 0; t < cnt; t++) {
-            const int op = __shfl(mine, (int)t, 64);
-            if (op <= JTK_OP_MISMATCH) {
-                if (i < n && j < m) {
-                    if (lane == 0) {
-                        hi[i] = j;
-                        lo[i + 1] = j + 1;
-                    }
-                    i++;
-                    j++;
-                }
-            } else if (op == JTK_OP_DEL) {
-                if (i < n) {
-                    if (lane == 0) {
-                        hi[i] = j;
-                        lo[i + 1] = j;
-                    }
-                    i++;
-                }
-            } else if (j < m) {
-                j++;
-            }
-        }
-    }
-    {  // the rest: diagonally, then by Del, then by Ins
-        const uint32_t d = n - i < m - j ? n - i : m - j;
-        for (uint32_t row = i + lane; row <= n; row += 64) {
-            const uint32_t col = j + (row - i < d ? row - i : d);
-            if (row > i) lo[row] = col;
-            hi[row] = row == n ? m : col;
-        }
-    }
-    gp_wave_sync();
-    uint32_t carry = 0, widest = 0;
-    for (uint32_t base = 0; base <= n; base += 64) {
-        const uint32_t row = base + lane;
-        uint32_t width = 0, first = 0;
-        if (row <= n) {
-            const uint32_t l = lo[row], h = hi[row];
-            first = l > r ? l - r : 0;
-            const uint32_t last = h + r < m ? h + r : m;
-            width = last - first + 1;
-        }
-        uint32_t incl = width;
-#pragma unroll
-        for (uint32_t o = 1; o < 64; o <<= 1) {
-            const uint32_t u = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += u;
-        }
-        if (row <= n) {
-            lo[row] = first;
-            hi[row] = carry + incl - width;
-        }
-        carry += __shfl(incl, 63, 64);
-        widest = width > widest ? width : widest;
-    }
-    for (uint32_t o = 32; o; o >>= 1) {
-        const uint32_t u = __shfl_xor(widest, o, 64);
-        widest = u > widest ? u : widest;
-    }
-    if (lane == 0) hi[n + 1] = carry;
-    gp_wave_sync();
-    return widest;
-}
 
 // One read of one round.  ring: 4 rows of `stride` cells.
 __device__ void gp_read(const GpArgs &a, uint32_t r, const GpPile &pl, GpState *st, uint32_t n, const uint32_t *lo, const uint32_t *off,
@@ -222,7 +141,7 @@ __device__ void gp_read(const GpArgs &a, uint32_t r, const GpPile &pl, GpState *
                     f[(uint64_t)at + c] = v;
                 }
             }
-            gp_wave_sync();
+            jtk_wave_sync();
             prev_first = cb;
             prev_width = width;
         }
@@ -309,7 +228,7 @@ __device__ void gp_read(const GpArgs &a, uint32_t r, const GpPile &pl, GpState *
     }
     if (!vote) return;
     // ---- backward, row i into ring row i & 3, columns counted from the right; then the table entries of position i
-    gp_wave_sync();
+    jtk_wave_sync();
     int32_t *gain = a.gain + pl.gain_off;
     uint32_t *dead = a.dead + pl.gain_off;
     uint32_t *dbg = a.dbg_table ? a.dbg_table + ((uint64_t)rd.rank * (pl.tmpl_cap + 1)) * GP_ROWS : nullptr;
@@ -350,7 +269,7 @@ __device__ void gp_read(const GpArgs &a, uint32_t r, const GpPile &pl, GpState *
                 if (q < width) cur[c] = gp_sat(t + (int32_t)q);
             }
         }
-        gp_wave_sync();
+        jtk_wave_sync();
         {
             const uint32_t p = i;
             int32_t acc[GP_ROWS];
@@ -407,7 +326,7 @@ __device__ void gp_read(const GpArgs &a, uint32_t r, const GpPile &pl, GpState *
                 if (dbg) dbg[at] = mine >= GP_BIG ? GP_DEAD : (uint32_t)mine;
             }
         }
-        gp_wave_sync();  // ring row (i + 3) & 3 is the next row's
+        jtk_wave_sync();  // ring row (i + 3) & 3 is the next row's
         if (i == 0) break;
     }
 }
@@ -427,8 +346,10 @@ __global__ void __launch_bounds__(GP_WAVES * 64) gp_fill_kernel(GpArgs a) {
     const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)st->n);
     uint32_t *lo = a.tab + rd.tab_off, *off = lo + (n + 2);
     const GpReadState rs = a.rstate[r];
-    const uint32_t widest = gp_rows(n, rd.m, pl.radius, a.ops + rd.ops_off + rs.at, rs.len, lo, off, lane);
-    const uint32_t cells = off[n + 1];
+    uint32_t total = 0;
+    const uint32_t widest = jtk_band_rows(n, rd.m, pl.radius, a.ops + rd.ops_off + rs.at, rs.len, lo, off, lane, &total);
+    jtk_wave_sync();
+    const uint32_t cells = off[n + 1];  // (== total) read back behind the barrier, like the rows
     if (widest > GP_MAX_WIDTH || cells > rd.f_cap) {
         // the host's bound holds for every guide: the second case has never been seen
         if (lane == 0) atomicCAS(&st->status, 0, widest > GP_MAX_WIDTH ? (int)JTK_ERR_UNSUPPORTED : (int)JTK_ERR_INTERNAL);
@@ -689,15 +610,10 @@ uint64_t gp_cells_bound(uint32_t n, uint32_t m, uint32_t r) {
     return std::min({rows * ((uint64_t)m + 1), by_path, rows * GP_MAX_WIDTH});
 }
 
-struct GpStream {
-    hipStream_t st = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    uint32_t *h_count = nullptr;
-    ~GpStream() {
-        if (st) (void)hipStreamDestroy(st);
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        if (h_count) (void)hipHostFree(h_count);
+struct GpCount {  // the mapped host word gp_commit_kernel stores to
+    uint32_t *h = nullptr;
+    ~GpCount() {
+        if (h) (void)hipHostFree(h);
     }
 };
 
@@ -790,69 +706,77 @@ int gp_run(size_t n_chunks, const jtk_lc_chunk_t *chunks, const uint8_t *tmpl_ba
         }
         slice_first.push_back((uint32_t)n_reads);
     }
-    GpStream s;
-    JTK_HIP_TRY(hipStreamCreate(&s.st));
-    JTK_HIP_TRY(hipEventCreate(&s.ev0));
-    JTK_HIP_TRY(hipEventCreate(&s.ev1));
+    GpCount count;  // outlives the stream
+    DevStream s;
+    JTK_HIP_TRY(s.create(2));
     const uint32_t limit = table_out ? 1 : (max_rounds ? max_rounds : GP_DEFAULT_ROUNDS);
-    JTK_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s.h_count), sizeof(uint32_t), hipHostMallocMapped));
+    JTK_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&count.h), sizeof(uint32_t), hipHostMallocMapped));
     uint32_t *h_count_dev = nullptr;
-    JTK_HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&h_count_dev), s.h_count, 0));
-    s.h_count[0] = 0;  // every round waits for its count, so one slot serves them all
+    JTK_HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&h_count_dev), count.h, 0));
+    count.h[0] = 0;  // every round waits for its count, so one slot serves them all
     const hipStream_t st = s.st;
-    DevBuf d_piles, d_state, d_reads, d_rstate, d_t0, d_t1, d_y, d_ops, d_tab, d_f, d_ring, d_gain, d_dead, d_edits, d_cells, d_dbg;
+    DevArr<GpPile> d_piles;
+    DevArr<GpState> d_state;
+    DevArr<GpRead> d_reads;
+    DevArr<GpReadState> d_rstate;
+    DevArr<uint8_t> d_t0, d_t1, d_y, d_ops;
+    DevArr<uint32_t> d_tab, d_dead, d_dbg;
+    DevArr<uint16_t> d_f, d_ring;
+    DevArr<int32_t> d_gain;
+    DevArr<GpEdit> d_edits;
+    DevArr<unsigned long long> d_cells;
     {
         int rc;
         if ((rc = d_piles.upload(piles, st)) || (rc = d_state.upload(state, st)) || (rc = d_reads.upload(reads, st)) || (rc = d_rstate.upload(rstate, st)))
             return jtk_fail(rc, "device upload failed");
     }
-    JTK_HIP_TRY(d_t0.alloc(std::max<uint64_t>(tmpl_bytes, 1)));
-    JTK_HIP_TRY(d_t1.alloc(std::max<uint64_t>(tmpl_bytes, 1)));
-    JTK_HIP_TRY(d_y.alloc(std::max<uint64_t>(y_bytes, 1)));
-    JTK_HIP_TRY(d_ops.alloc(std::max<uint64_t>(ops_bytes, 1)));
-    JTK_HIP_TRY(d_tab.alloc(std::max<uint64_t>(tab_need, 1) * sizeof(uint32_t)));
-    JTK_HIP_TRY(d_f.alloc(std::max<uint64_t>(f_need, 1) * sizeof(uint16_t)));
-    JTK_HIP_TRY(d_ring.alloc(std::max<uint64_t>(ring_need, 1) * sizeof(uint16_t)));
-    JTK_HIP_TRY(d_gain.alloc(std::max<uint64_t>(gain_n, 1) * sizeof(int32_t)));
-    JTK_HIP_TRY(d_dead.alloc(std::max<uint64_t>(gain_n, 1) * sizeof(uint32_t)));
-    JTK_HIP_TRY(d_edits.alloc(std::max<uint64_t>(edit_n, 1) * sizeof(GpEdit)));
-    JTK_HIP_TRY(d_cells.alloc(2 * sizeof(unsigned long long)));
-    JTK_HIP_TRY(hipMemsetAsync(d_cells.p, 0, 2 * sizeof(unsigned long long), st));
+    JTK_HIP_TRY(d_t0.alloc(tmpl_bytes));
+    JTK_HIP_TRY(d_t1.alloc(tmpl_bytes));
+    JTK_HIP_TRY(d_y.alloc(y_bytes));
+    JTK_HIP_TRY(d_ops.alloc(ops_bytes));
+    JTK_HIP_TRY(d_tab.alloc(tab_need));
+    JTK_HIP_TRY(d_f.alloc(f_need));
+    JTK_HIP_TRY(d_ring.alloc(ring_need));
+    JTK_HIP_TRY(d_gain.alloc(gain_n));
+    JTK_HIP_TRY(d_dead.alloc(gain_n));
+    JTK_HIP_TRY(d_edits.alloc(edit_n));
+    JTK_HIP_TRY(d_cells.alloc(2));
+    JTK_HIP_TRY(d_cells.zero(2, st));
     uint64_t dbg_n = 0;
     if (table_out) {
         dbg_n = (uint64_t)n_reads * (piles[0].tmpl_cap + 1) * GP_ROWS;
-        JTK_HIP_TRY(d_dbg.alloc(std::max<uint64_t>(dbg_n, 1) * sizeof(uint32_t)));
-        JTK_HIP_TRY(hipMemsetAsync(d_dbg.p, 0xff, std::max<uint64_t>(dbg_n, 1) * sizeof(uint32_t), st));
+        JTK_HIP_TRY(d_dbg.alloc(dbg_n));
+        JTK_HIP_TRY(hipMemsetAsync(d_dbg.get(), 0xff, std::max<uint64_t>(dbg_n, 1) * sizeof(uint32_t), st));
     }
     for (size_t c = 0; c < n_chunks; c++)
         if (state[c].status == 0 && chunks[c].tmpl_len)
-            JTK_HIP_TRY(hipMemcpyAsync((uint8_t *)d_t0.p + piles[c].tmpl_off, tmpl_bases + chunks[c].tmpl_off, chunks[c].tmpl_len, hipMemcpyHostToDevice, st));
-    if (y_bytes) JTK_HIP_TRY(hipMemcpyAsync(d_y.p, read_bases, y_bytes, hipMemcpyHostToDevice, st));
+            JTK_HIP_TRY(hipMemcpyAsync(d_t0.get() + piles[c].tmpl_off, tmpl_bases + chunks[c].tmpl_off, chunks[c].tmpl_len, hipMemcpyHostToDevice, st));
+    if (y_bytes) JTK_HIP_TRY(hipMemcpyAsync(d_y.get(), read_bases, y_bytes, hipMemcpyHostToDevice, st));
     {
         // the input ops of every read into the first half of its share: gathered on the host, one copy
         std::vector<uint8_t> init(ops_bytes, 0);
         for (uint64_t r = 0; r < n_reads; r++)
             if (rstate[r].len) std::memcpy(init.data() + reads[r].ops_off, ops + ops_off[r], rstate[r].len);
-        if (ops_bytes) JTK_HIP_TRY(hipMemcpyAsync(d_ops.p, init.data(), ops_bytes, hipMemcpyHostToDevice, st));
+        if (ops_bytes) JTK_HIP_TRY(hipMemcpyAsync(d_ops.get(), init.data(), ops_bytes, hipMemcpyHostToDevice, st));
         JTK_HIP_TRY(hipStreamSynchronize(st));  // `init` goes with this scope
     }
     GpArgs a{};
-    a.piles = (const GpPile *)d_piles.p;
-    a.state = (GpState *)d_state.p;
-    a.reads = (const GpRead *)d_reads.p;
-    a.rstate = (GpReadState *)d_rstate.p;
-    a.tmpl[0] = (uint8_t *)d_t0.p;
-    a.tmpl[1] = (uint8_t *)d_t1.p;
-    a.y = (const uint8_t *)d_y.p;
-    a.ops = (uint8_t *)d_ops.p;
-    a.tab = (uint32_t *)d_tab.p;
-    a.f = (uint16_t *)d_f.p;
-    a.ring = (uint16_t *)d_ring.p;
-    a.gain = (int32_t *)d_gain.p;
-    a.dead = (uint32_t *)d_dead.p;
-    a.edits = (GpEdit *)d_edits.p;
-    a.dbg_table = (uint32_t *)d_dbg.p;
-    a.cells = (unsigned long long *)d_cells.p;
+    a.piles = d_piles.cget();
+    a.state = d_state.get();
+    a.reads = d_reads.cget();
+    a.rstate = d_rstate.get();
+    a.tmpl[0] = d_t0.get();
+    a.tmpl[1] = d_t1.get();
+    a.y = d_y.cget();
+    a.ops = d_ops.get();
+    a.tab = d_tab.get();
+    a.f = d_f.get();
+    a.ring = d_ring.get();
+    a.gain = d_gain.get();
+    a.dead = d_dead.get();
+    a.edits = d_edits.get();
+    a.dbg_table = d_dbg.get();
+    a.cells = d_cells.get();
     a.take_num = take_num;
     a.ignore_edge = ignore_edge;
     const size_t fill_lds = GP_WAVES * 4 * GP_LDS_WIDTH * sizeof(uint16_t);
@@ -871,7 +795,7 @@ int gp_run(size_t n_chunks, const jtk_lc_chunk_t *chunks, const uint8_t *tmpl_ba
     uint32_t rounds_run = 0;
     const uint32_t nc = (uint32_t)n_chunks, nr = (uint32_t)n_reads;
     for (uint32_t t = 0; t < limit && nc; t++) {
-        JTK_HIP_TRY(hipEventRecord(s.ev0, st));
+        JTK_HIP_TRY(hipEventRecord(s.ev[0], st));
         gp_begin_kernel<<<nc, 256, 0, st>>>(a.piles, a.state, a.gain, a.dead, ignore_edge, table_out ? 0 : 1);
         JTK_HIP_TRY(hipGetLastError());
         if (int rc = fill(0)) return rc;
@@ -886,29 +810,29 @@ int gp_run(size_t n_chunks, const jtk_lc_chunk_t *chunks, const uint8_t *tmpl_ba
             gp_commit_kernel<<<1, 256, 0, st>>>(nc, a.state, h_count_dev);
             JTK_HIP_TRY(hipGetLastError());
         }
-        JTK_HIP_TRY(hipEventRecord(s.ev1, st));
+        JTK_HIP_TRY(hipEventRecord(s.ev[1], st));
         JTK_HIP_TRY(hipStreamSynchronize(st));
         JTK_HIP_TRY(hipGetLastError());
         float ms = 0.f;
-        JTK_HIP_TRY(hipEventElapsedTime(&ms, s.ev0, s.ev1));
+        JTK_HIP_TRY(s.elapsed(0, 1, &ms));
         kernel_ms += ms;
         rounds_run++;
-        if (table_out || __atomic_load_n(&s.h_count[0], __ATOMIC_RELAXED) == 0) break;
+        if (table_out || __atomic_load_n(&count.h[0], __ATOMIC_RELAXED) == 0) break;
     }
     if (!table_out && nc) {  // ops and distances of the pile-ups that stopped on a template no fill has seen
-        JTK_HIP_TRY(hipEventRecord(s.ev0, st));
+        JTK_HIP_TRY(hipEventRecord(s.ev[0], st));
         if (int rc = fill(1)) return rc;
-        JTK_HIP_TRY(hipEventRecord(s.ev1, st));
+        JTK_HIP_TRY(hipEventRecord(s.ev[1], st));
         JTK_HIP_TRY(hipStreamSynchronize(st));
         JTK_HIP_TRY(hipGetLastError());
         float ms = 0.f;
-        JTK_HIP_TRY(hipEventElapsedTime(&ms, s.ev0, s.ev1));
+        JTK_HIP_TRY(s.elapsed(0, 1, &ms));
         kernel_ms += ms;
     }
-    if (nc) JTK_HIP_TRY(hipMemcpyAsync(state.data(), d_state.p, n_chunks * sizeof(GpState), hipMemcpyDeviceToHost, st));
-    if (nr) JTK_HIP_TRY(hipMemcpyAsync(rstate.data(), d_rstate.p, n_reads * sizeof(GpReadState), hipMemcpyDeviceToHost, st));
+    if (nc) JTK_HIP_TRY(d_state.download(state.data(), n_chunks, st));
+    if (nr) JTK_HIP_TRY(d_rstate.download(rstate.data(), n_reads, st));
     unsigned long long cells[2] = {0, 0};
-    JTK_HIP_TRY(hipMemcpyAsync(cells, d_cells.p, sizeof cells, hipMemcpyDeviceToHost, st));
+    JTK_HIP_TRY(d_cells.download(cells, 2, st));
     JTK_HIP_TRY(hipStreamSynchronize(st));
     g_gpolish_timing[0] = (double)n_chunks;
     g_gpolish_timing[1] = (double)n_reads;
@@ -926,7 +850,7 @@ int gp_run(size_t n_chunks, const jtk_lc_chunk_t *chunks, const uint8_t *tmpl_ba
     if (table_out) {
         if (rc) return jtk_fail(JTK_ERR_UNSUPPORTED, "the pile-up is beyond the limits of the guided polish");
         for (uint64_t r = 0; r < n_reads; r++) dist_out[r] = rstate[r].dist;
-        if (dbg_n) JTK_HIP_TRY(hipMemcpy(table_out, d_dbg.p, dbg_n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (dbg_n) JTK_HIP_TRY(hipMemcpy(table_out, d_dbg.cget(), dbg_n * sizeof(uint32_t), hipMemcpyDeviceToHost));
         return 0;
     }
     std::vector<uint64_t> ops_dst(n_reads + 1, 0), cons_dst(n_chunks + 1, 0);
@@ -945,16 +869,17 @@ int gp_run(size_t n_chunks, const jtk_lc_chunk_t *chunks, const uint8_t *tmpl_ba
     if (cons_total > cons_cap) return jtk_fail(JTK_ERR_INVALID_ARG, "cons_cap is smaller than the consensus sequences of the batch");
     if (ops_total > ops_cap) return jtk_fail(JTK_ERR_INVALID_ARG, "ops_cap is smaller than the ops of the batch");
     if (ops_total + cons_total) {
-        DevBuf d_od, d_cd, d_oo, d_co;
+        DevArr<uint64_t> d_od, d_cd;
+        DevArr<uint8_t> d_oo, d_co;
         int rc2;
         if ((rc2 = d_od.upload(ops_dst, st)) || (rc2 = d_cd.upload(cons_dst, st))) return jtk_fail(rc2, "device upload failed");
-        JTK_HIP_TRY(d_oo.alloc(std::max<uint64_t>(ops_total, 1)));
-        JTK_HIP_TRY(d_co.alloc(std::max<uint64_t>(cons_total, 1)));
-        gp_pack_kernel<<<nr + nc, 256, 0, st>>>(nr, nc, a.piles, a.state, a.reads, a.rstate, a.tmpl[0], a.tmpl[1], a.ops, (const uint64_t *)d_od.p,
-                                                (const uint64_t *)d_cd.p, (uint8_t *)d_oo.p, (uint8_t *)d_co.p);
+        JTK_HIP_TRY(d_oo.alloc(ops_total));
+        JTK_HIP_TRY(d_co.alloc(cons_total));
+        gp_pack_kernel<<<nr + nc, 256, 0, st>>>(nr, nc, a.piles, a.state, a.reads, a.rstate, a.tmpl[0], a.tmpl[1], a.ops, d_od.cget(), d_cd.cget(),
+                                                d_oo.get(), d_co.get());
         JTK_HIP_TRY(hipGetLastError());
-        if (ops_total) JTK_HIP_TRY(hipMemcpyAsync(ops_out, d_oo.p, ops_total, hipMemcpyDeviceToHost, st));
-        if (cons_total) JTK_HIP_TRY(hipMemcpyAsync(cons_out, d_co.p, cons_total, hipMemcpyDeviceToHost, st));
+        if (ops_total) JTK_HIP_TRY(d_oo.download(ops_out, ops_total, st));
+        if (cons_total) JTK_HIP_TRY(d_co.download(cons_out, cons_total, st));
         JTK_HIP_TRY(hipStreamSynchronize(st));
         JTK_HIP_TRY(hipGetLastError());
     }

@@ -26,8 +26,8 @@
 
 #include "device_common.h"
 #include "guided_internal.h"
-#include "host_common.h"
 #include "jtk_lc_debug.h"
+#include "wave_util.h"
 
 namespace {
 
@@ -60,12 +60,6 @@ struct GdArgs {
     int infix;
 };
 
-// memory written by some lanes of the wave, read by others
-__device__ __forceinline__ void gd_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 __device__ __forceinline__ int32_t gd_max(int32_t a, int32_t b) { return a > b ? a : b; }
 
 // The guide's path and the band of one pair: tab[i] = first column of row i, tab[n + 2 + i] = cells in the rows above it.
@@ -81,77 +75,10 @@ __global__ void __launch_bounds__(GD_WAVES * 64) guided_rows_kernel(GdArgs a) {
     const jtk_guided_pair_t pr = a.pairs[p];
     const GdWork wk = a.work[p];
     const uint32_t n = pr.x_len, m = pr.y_len;
-    const uint32_t longest = n > m ? n : m;
-    const uint32_t r = pr.radius > longest ? longest + 1 : pr.radius;  // wider changes nothing
     uint32_t *lo = a.tab + wk.tab_off, *hi = lo + (n + 2);
-    // ---- the walk; row i is opened with lo[i] when the path enters it and closed with hi[i] when it leaves
-    uint32_t i = 0, j = 0;
-    if (lane == 0) lo[0] = 0;
-    for (uint32_t base = 0; base < pr.guide_len; base += 64) {
-        const uint32_t cnt = pr.guide_len - base < 64u ? pr.guide_len - base : 64u;
-        const int mine = lane < cnt ? (int)a.guide[pr.guide_off + base + lane] : 2;
-        for (uint32_t t = 0; t < cnt; t++) {
-            const int op = __shfl(mine, (int)t, 64);
-            if (op <= JTK_OP_MISMATCH) {
-                if (i < n && j < m) {
-                    if (lane == 0) {
-                        hi[i] = j;
-                        lo[i + 1] = j + 1;
-                    }
-                    i++;
-                    j++;
-                }
-            } else if (op == JTK_OP_DEL) {
-                if (i < n) {
-                    if (lane == 0) {
-                        hi[i] = j;
-                        lo[i + 1] = j;
-                    }
-                    i++;
-                }
-            } else if (j < m) {
-                j++;
-            }
-        }
-    }
-    {  // the rest: diagonally, then by Del, then by Ins
-        const uint32_t d = n - i < m - j ? n - i : m - j;
-        for (uint32_t row = i + lane; row <= n; row += 64) {
-            const uint32_t col = j + (row - i < d ? row - i : d);
-            if (row > i) lo[row] = col;
-            hi[row] = row == n ? m : col;
-        }
-    }
-    gd_wave_sync();
-    // ---- the band and the prefix sum of its widths
-    uint32_t carry = 0, widest = 0;
-    for (uint32_t base = 0; base <= n; base += 64) {
-        const uint32_t row = base + lane;
-        uint32_t width = 0, first = 0;
-        if (row <= n) {
-            const uint32_t l = lo[row], h = hi[row];
-            first = l > r ? l - r : 0;
-            const uint32_t last = h + r < m ? h + r : m;
-            width = last - first + 1;
-        }
-        uint32_t incl = width;
-        for (uint32_t o = 1; o < 64; o <<= 1) {
-            const uint32_t u = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += u;
-        }
-        if (row <= n) {
-            lo[row] = first;
-            hi[row] = carry + incl - width;
-        }
-        carry += __shfl(incl, 63, 64);
-        widest = width > widest ? width : widest;
-    }
-    for (uint32_t o = 32; o; o >>= 1) {
-        const uint32_t u = __shfl_xor(widest, o, 64);
-        widest = u > widest ? u : widest;
-    }
+    uint32_t carry = 0;
+    const uint32_t widest = jtk_band_rows(n, m, pr.radius, a.guide + pr.guide_off, pr.guide_len, lo, hi, lane, &carry);
     if (lane == 0) {
-        hi[n + 1] = carry;
         int32_t st = 0;
         if (widest > GD_MAX_WIDTH)
             st = JTK_ERR_UNSUPPORTED;
@@ -248,7 +175,7 @@ __device__ void gd_pair(const GdArgs &a, uint32_t p, uint32_t stride, int32_t *r
                 tb[(uint64_t)off + c] = (uint8_t)bits;
             }
         }
-        gd_wave_sync();
+        jtk_wave_sync();
         if (cb + width - 1 == m && (a.infix || i == n)) {  // an end cell; the first row that holds the maximum keeps it
             const int32_t e0 = cur[width - 1], e1 = cur[stride + width - 1], e2 = cur[2 * stride + width - 1];
             const int32_t ev = gd_max(e0, gd_max(e1, e2));
@@ -321,7 +248,7 @@ __device__ void gd_pair(const GdArgs &a, uint32_t p, uint32_t stride, int32_t *r
         a.end[p] = best_row;
         a.nops[p] = lost ? 0u : k;
     }
-    gd_wave_sync();  // the rows are the next pair's
+    jtk_wave_sync();  // the rows are the next pair's
 }
 
 // LARGE == false: the pairs whose widest row fits the wave's LDS; true: the others, rows in the global area of a few waves.
@@ -398,18 +325,18 @@ int guided_plan(const GuidedBatch &b, GuidedRun &run) {
 }
 
 int guided_reserve(GuidedArea &area, const GuidedRun &run) {
-    if (run.tab_need > area.tab_have || !area.tab.p) {
+    if (run.tab_need > area.tab_have || !area.tab.get()) {
         area.tab_have = 0;
-        JTK_HIP_TRY(area.tab.alloc(std::max<uint64_t>(run.tab_need, 1) * sizeof(uint32_t)));
+        JTK_HIP_TRY(area.tab.alloc(run.tab_need));
         area.tab_have = run.tab_need;
     }
-    if (run.tb_need > area.tb_have || !area.tb.p) {
+    if (run.tb_need > area.tb_have || !area.tb.get()) {
         area.tb_have = 0;
-        JTK_HIP_TRY(area.tb.alloc(std::max<uint64_t>(run.tb_need, 1)));
+        JTK_HIP_TRY(area.tb.alloc(run.tb_need));
         area.tb_have = run.tb_need;
     }
     if (run.any_large && !area.rows_have) {
-        JTK_HIP_TRY(area.rows.alloc((uint64_t)GD_LARGE_WAVES * 6 * GD_MAX_WIDTH * sizeof(int32_t)));
+        JTK_HIP_TRY(area.rows.alloc((uint64_t)GD_LARGE_WAVES * 6 * GD_MAX_WIDTH));
         area.rows_have = true;
     }
     return 0;
@@ -422,21 +349,20 @@ int guided_enqueue(const GuidedBatch &b, GuidedRun &run, GuidedArea &area, hipSt
         return jtk_fail(JTK_ERR_INTERNAL, "guided: the batch was not planned or its work area not reserved");
     // run.work stays with the caller until the stream has been synchronised: the copy below reads it when the stream gets there
     if (int rc = run.d_work.upload(run.work, st)) return jtk_fail(rc, "device upload failed");
-    JTK_HIP_TRY(run.maxw.alloc(b.n * sizeof(uint32_t)));
-    JTK_HIP_TRY(run.cells.alloc(sizeof(unsigned long long)));
-    JTK_HIP_TRY(hipMemsetAsync(run.cells.p, 0, sizeof(unsigned long long), st));
-    if (!run.ev0) JTK_HIP_TRY(hipEventCreate(&run.ev0));
-    if (!run.ev1) JTK_HIP_TRY(hipEventCreate(&run.ev1));
+    JTK_HIP_TRY(run.maxw.alloc(b.n));
+    JTK_HIP_TRY(run.cells.alloc(1));
+    JTK_HIP_TRY(run.cells.zero(1, st));
+    JTK_HIP_TRY(run.ev.create(2));
     GdArgs a{};
     a.pairs = b.d_pairs;
-    a.work = (const GdWork *)run.d_work.p;
+    a.work = run.d_work.cget();
     a.x = b.d_x;
     a.y = b.d_y;
     a.guide = b.d_guide;
-    a.tab = (uint32_t *)area.tab.p;
-    a.tb = (uint8_t *)area.tb.p;
-    a.rows = (int32_t *)area.rows.p;
-    a.maxw = (uint32_t *)run.maxw.p;
+    a.tab = area.tab.get();
+    a.tb = area.tb.get();
+    a.rows = area.rows.get();
+    a.maxw = run.maxw.get();
     a.score = b.d_score;
     a.status = b.d_status;
     a.start = b.d_start;
@@ -444,13 +370,13 @@ int guided_enqueue(const GuidedBatch &b, GuidedRun &run, GuidedArea &area, hipSt
     a.nops = b.d_nops;
     a.slots = b.d_slots;
     a.slot_end = b.d_slot_end;
-    a.cells = (unsigned long long *)run.cells.p;
+    a.cells = run.cells.get();
     a.match = b.match;
     a.mismatch = b.mismatch;
     a.gap_open = b.gap_open;
     a.gap_ext = b.gap_ext;
     a.infix = b.infix;
-    JTK_HIP_TRY(hipEventRecord(run.ev0, st));
+    JTK_HIP_TRY(hipEventRecord(run.ev[0], st));
     for (size_t s = 0; s + 1 < run.slice_first.size(); s++) {
         a.first = run.slice_first[s];
         a.count = run.slice_first[s + 1] - run.slice_first[s];
@@ -465,7 +391,7 @@ int guided_enqueue(const GuidedBatch &b, GuidedRun &run, GuidedArea &area, hipSt
         }
         run.slices++;
     }
-    JTK_HIP_TRY(hipEventRecord(run.ev1, st));
+    JTK_HIP_TRY(hipEventRecord(run.ev[1], st));
     return 0;
 }
 
@@ -473,9 +399,9 @@ int guided_elapsed(const GuidedRun &keep, double *ms, double *cells) {
     *ms = *cells = 0;
     if (!keep.slices) return 0;
     float f = 0.f;
-    JTK_HIP_TRY(hipEventElapsedTime(&f, keep.ev0, keep.ev1));
+    JTK_HIP_TRY(keep.ev.elapsed(0, 1, &f));
     unsigned long long c = 0;
-    JTK_HIP_TRY(hipMemcpy(&c, keep.cells.p, sizeof(c), hipMemcpyDeviceToHost));
+    JTK_HIP_TRY(hipMemcpy(&c, keep.cells.cget(), sizeof(c), hipMemcpyDeviceToHost));
     *ms = f;
     *cells = (double)c;
     return 0;
@@ -553,15 +479,14 @@ extern "C" int jtk_lc_align_guided(size_t n_pairs, const jtk_guided_pair_t *pair
             slot += (uint64_t)xlen[p] + ylen[p];
         slot_end[p] = slot;
     }
-    struct Stream {
-        hipStream_t st = nullptr;
-        ~Stream() {
-            if (st) (void)hipStreamDestroy(st);
-        }
-    } s;
-    JTK_HIP_TRY(hipStreamCreate(&s.st));
+    DevStream s;
+    JTK_HIP_TRY(s.create());
     const hipStream_t st = s.st;
-    DevBuf d_pairs, d_x, d_y, d_g, d_score, d_status, d_start, d_end, d_nops, d_slots, d_slot_end;
+    DevArr<jtk_guided_pair_t> d_pairs;
+    DevArr<uint8_t> d_x, d_y, d_g, d_slots;
+    DevArr<int32_t> d_score, d_status;
+    DevArr<uint32_t> d_start, d_end, d_nops;
+    DevArr<uint64_t> d_slot_end;
     {
         const std::vector<jtk_guided_pair_t> pv(pairs, pairs + n_pairs);
         const std::vector<uint8_t> xv(x_bases, x_bases + x_bytes), yv(y_bases, y_bases + y_bytes), gv(guide_ops, guide_ops + g_bytes);
@@ -571,21 +496,21 @@ extern "C" int jtk_lc_align_guided(size_t n_pairs, const jtk_guided_pair_t *pair
             return jtk_fail(rc, "device upload failed");
         JTK_HIP_TRY(hipStreamSynchronize(st));  // the vectors go with this scope
     }
-    JTK_HIP_TRY(d_score.alloc(n_pairs * sizeof(int32_t)));
-    JTK_HIP_TRY(d_start.alloc(n_pairs * sizeof(uint32_t)));
-    JTK_HIP_TRY(d_end.alloc(n_pairs * sizeof(uint32_t)));
-    JTK_HIP_TRY(d_nops.alloc(n_pairs * sizeof(uint32_t)));
+    JTK_HIP_TRY(d_score.alloc(n_pairs));
+    JTK_HIP_TRY(d_start.alloc(n_pairs));
+    JTK_HIP_TRY(d_end.alloc(n_pairs));
+    JTK_HIP_TRY(d_nops.alloc(n_pairs));
     JTK_HIP_TRY(d_slots.alloc(slot + 1));
-    JTK_HIP_TRY(hipMemsetAsync(d_score.p, 0, n_pairs * sizeof(int32_t), st));
-    JTK_HIP_TRY(hipMemsetAsync(d_start.p, 0, n_pairs * sizeof(uint32_t), st));
-    JTK_HIP_TRY(hipMemsetAsync(d_end.p, 0, n_pairs * sizeof(uint32_t), st));
-    JTK_HIP_TRY(hipMemsetAsync(d_nops.p, 0, n_pairs * sizeof(uint32_t), st));
+    JTK_HIP_TRY(d_score.zero(n_pairs, st));
+    JTK_HIP_TRY(d_start.zero(n_pairs, st));
+    JTK_HIP_TRY(d_end.zero(n_pairs, st));
+    JTK_HIP_TRY(d_nops.zero(n_pairs, st));
     GuidedBatch b;
     b.n = n_pairs;
-    b.d_pairs = (const jtk_guided_pair_t *)d_pairs.p;
-    b.d_x = (const uint8_t *)d_x.p;
-    b.d_y = (const uint8_t *)d_y.p;
-    b.d_guide = (const uint8_t *)d_g.p;
+    b.d_pairs = d_pairs.cget();
+    b.d_x = d_x.cget();
+    b.d_y = d_y.cget();
+    b.d_guide = d_g.cget();
     b.infix = mode == JTK_ALIGN_INFIX;
     b.match = match;
     b.mismatch = mismatch;
@@ -594,13 +519,13 @@ extern "C" int jtk_lc_align_guided(size_t n_pairs, const jtk_guided_pair_t *pair
     b.h_xlen = xlen.data();
     b.h_ylen = ylen.data();
     b.h_radius = radius.data();
-    b.d_score = (int32_t *)d_score.p;
-    b.d_status = (int32_t *)d_status.p;
-    b.d_start = (uint32_t *)d_start.p;
-    b.d_end = (uint32_t *)d_end.p;
-    b.d_nops = (uint32_t *)d_nops.p;
-    b.d_slots = (uint8_t *)d_slots.p;
-    b.d_slot_end = (const uint64_t *)d_slot_end.p;
+    b.d_score = d_score.get();
+    b.d_status = d_status.get();
+    b.d_start = d_start.get();
+    b.d_end = d_end.get();
+    b.d_nops = d_nops.get();
+    b.d_slots = d_slots.get();
+    b.d_slot_end = d_slot_end.cget();
     GuidedRun run;
     GuidedArea area;
     if (int rc = guided_plan(b, run)) return rc;
@@ -608,11 +533,11 @@ extern "C" int jtk_lc_align_guided(size_t n_pairs, const jtk_guided_pair_t *pair
     if (int rc = guided_enqueue(b, run, area, st)) return rc;
     std::vector<uint32_t> nops(n_pairs), start_v(n_pairs), end_v(n_pairs);
     std::vector<int32_t> score_v(n_pairs);
-    JTK_HIP_TRY(hipMemcpyAsync(nops.data(), d_nops.p, n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    JTK_HIP_TRY(hipMemcpyAsync(start_v.data(), d_start.p, n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    JTK_HIP_TRY(hipMemcpyAsync(end_v.data(), d_end.p, n_pairs * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    JTK_HIP_TRY(hipMemcpyAsync(score_v.data(), d_score.p, n_pairs * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    JTK_HIP_TRY(hipMemcpyAsync(st_v.data(), d_status.p, n_pairs * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    JTK_HIP_TRY(d_nops.download(nops.data(), n_pairs, st));
+    JTK_HIP_TRY(d_start.download(start_v.data(), n_pairs, st));
+    JTK_HIP_TRY(d_end.download(end_v.data(), n_pairs, st));
+    JTK_HIP_TRY(d_score.download(score_v.data(), n_pairs, st));
+    JTK_HIP_TRY(d_status.download(st_v.data(), n_pairs, st));
     JTK_HIP_TRY(hipStreamSynchronize(st));
     JTK_HIP_TRY(hipGetLastError());
     {
@@ -636,13 +561,12 @@ extern "C" int jtk_lc_align_guided(size_t n_pairs, const jtk_guided_pair_t *pair
     const uint64_t total = dst_off[n_pairs];
     if (total > ops_cap || (total && !ops_out)) return jtk_fail(JTK_ERR_INVALID_ARG, "ops_cap is smaller than the ops of the batch");
     if (total) {
-        DevBuf d_off, d_out;
+        DevArr<uint64_t> d_off;
+        DevArr<uint8_t> d_out;
         if (int rc2 = d_off.upload(dst_off, st)) return jtk_fail(rc2, "device upload failed");
         JTK_HIP_TRY(d_out.alloc(total));
-        if (int rc2 = guided_pack(n_pairs, (const uint8_t *)d_slots.p, (const uint64_t *)d_slot_end.p, (const uint32_t *)d_nops.p,
-                                  (const uint64_t *)d_off.p, (uint8_t *)d_out.p, st))
-            return rc2;
-        JTK_HIP_TRY(hipMemcpyAsync(ops_out, d_out.p, total, hipMemcpyDeviceToHost, st));
+        if (int rc2 = guided_pack(n_pairs, d_slots.cget(), d_slot_end.cget(), d_nops.cget(), d_off.cget(), d_out.get(), st)) return rc2;
+        JTK_HIP_TRY(d_out.download(ops_out, total, st));
         JTK_HIP_TRY(hipStreamSynchronize(st));
         JTK_HIP_TRY(hipGetLastError());
     }

@@ -3,7 +3,7 @@
 #pragma once
 #include <vector>
 
-#include "host_common.h"
+#include "prim_host.h"
 
 // One batch of pairs on the device.  The host knows an upper bound of every pair's lengths (exact ones where it made the
 // descriptors itself); the work area is budgeted from those, so descriptors a kernel wrote need no trip to the host.
@@ -32,7 +32,9 @@ struct GuidedWork {
 // The work area: row tables, traceback bytes, and the rows of the waves that keep theirs in global memory.  Batches that run
 // behind each other on one stream share one; it is grown (guided_reserve) before anything that uses it is enqueued.
 struct GuidedArea {
-    DevBuf tab, tb, rows;
+    DevArr<uint32_t> tab;
+    DevArr<uint8_t> tb;
+    DevArr<int32_t> rows;
     uint64_t tab_have = 0, tb_have = 0;
     bool rows_have = false;
 };
@@ -44,16 +46,11 @@ struct GuidedRun {
     std::vector<uint32_t> slice_first;  // first pair of every slice, then n
     uint64_t tab_need = 0, tb_need = 0; // of the largest slice: uint32 entries, bytes
     bool any_large = false;
-    DevBuf d_work, maxw, cells;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    DevArr<GuidedWork> d_work;
+    DevArr<uint32_t> maxw;
+    DevArr<unsigned long long> cells;
+    DevEvents ev;                       // around the batch's kernels
     uint32_t slices = 0;
-    GuidedRun() = default;
-    GuidedRun(const GuidedRun &) = delete;
-    GuidedRun &operator=(const GuidedRun &) = delete;
-    ~GuidedRun() {
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-    }
 };
 // host only: the shares of the work area and the slices the budget asks for
 int guided_plan(const GuidedBatch &b, GuidedRun &run);

@@ -16,15 +16,14 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <memory>
 #include <string>
 #include <vector>
 
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "device_common.h"
-#include "host_common.h"
 #include "jtk_lc_debug.h"
+#include "prim_host.h"
 
 namespace {
 
@@ -178,32 +177,15 @@ __global__ void square_kernel(uint32_t n, const uint32_t *slot, const uint32_t *
     }
 }
 
-uint32_t pg_blocks(uint64_t n, uint32_t per, uint32_t cap) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n + per - 1) / per, 1), cap); }
-
-struct Stream {  // a stream and two pairs of events that go with their owner
-    hipStream_t st = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~Stream() {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        if (st) (void)hipStreamDestroy(st);
-    }
-    int create() {
-        JTK_HIP_TRY(hipStreamCreate(&st));
-        for (hipEvent_t &e : ev) JTK_HIP_TRY(hipEventCreate(&e));
-        return 0;
-    }
-};
-
 // the value at `idx` of the ascending order of n non-negative doubles (their bit patterns sort as unsigned integers)
-int pg_select(const Stream &s, uint32_t n, const double *d_vals, uint32_t idx, double *out) {
-    DevBuf d_sorted, d_tmp;
-    JTK_HIP_TRY(d_sorted.alloc((size_t)n * sizeof(uint64_t)));
-    size_t need = 0;
-    JTK_HIP_TRY(rocprim::radix_sort_keys(nullptr, need, (const uint64_t *)d_vals, (uint64_t *)d_sorted.p, (size_t)n, 0u, 64u, s.st));
-    JTK_HIP_TRY(d_tmp.alloc(std::max<size_t>(need, 1)));
-    JTK_HIP_TRY(rocprim::radix_sort_keys(d_tmp.p, need, (const uint64_t *)d_vals, (uint64_t *)d_sorted.p, (size_t)n, 0u, 64u, s.st));
-    JTK_HIP_TRY(hipMemcpyAsync(out, (const uint64_t *)d_sorted.p + idx, sizeof(double), hipMemcpyDeviceToHost, s.st));
+int pg_select(const DevStream &s, uint32_t n, const double *d_vals, uint32_t idx, double *out) {
+    DevArr<uint64_t> d_sorted;
+    RocTemp tmp;
+    JTK_HIP_TRY(d_sorted.alloc(n));
+    JTK_HIP_TRY(tmp.run([&](void *t, size_t &bytes) {
+        return rocprim::radix_sort_keys(t, bytes, (const uint64_t *)d_vals, d_sorted.get(), (size_t)n, 0u, 64u, s.st);
+    }));
+    JTK_HIP_TRY(d_sorted.download((uint64_t *)out, 1, s.st, idx));
     JTK_HIP_TRY(hipStreamSynchronize(s.st));
     JTK_HIP_TRY(hipGetLastError());
     return 0;
@@ -244,17 +226,12 @@ int pg_check_offsets(size_t n, const uint64_t *off, const char *what) {
     return 0;
 }
 
-int pg_upload(DevBuf &d, const void *src, size_t bytes, hipStream_t st) {
-    if (d.alloc(std::max<size_t>(bytes, 1)) != hipSuccess) return JTK_ERR_ALLOC;
-    if (bytes && hipMemcpyAsync(d.p, src, bytes, hipMemcpyHostToDevice, st) != hipSuccess) return JTK_ERR_NO_DEVICE;
-    return 0;
-}
-
 // What the device holds between the steps of one call.
 struct Work {
-    Stream s;
+    DevStream s;  // two pairs of events: create(4)
     uint32_t n_nodes = 0, n_reads = 0;
-    DevBuf d_num, d_len, d_rate;
+    DevArr<uint32_t> d_num, d_len;
+    DevArr<double> d_rate;
     std::vector<uint32_t> cidx;  // per node: index into chunks[], PG_NONE for an id that is not there
 };
 
@@ -262,44 +239,46 @@ struct Work {
 int pg_walk(Work &w, size_t n_chunks, const uint8_t *seq_bases, const uint64_t *seq_off, const uint8_t *ops, const uint64_t *ops_off,
             const uint8_t *tmpl_bases, const uint64_t *tmpl_off, std::vector<uint32_t> &num, std::vector<uint32_t> &len, std::vector<int32_t> &status) {
     const uint32_t n = w.n_nodes;
-    DevBuf d_cidx, d_seq_off, d_ops_off, d_tmpl_off, d_seq, d_ops, d_tmpl, d_status;
+    DevArr<uint32_t> d_cidx;
+    DevArr<uint64_t> d_seq_off, d_ops_off, d_tmpl_off;
+    DevArr<uint8_t> d_seq, d_ops, d_tmpl;
+    DevArr<int32_t> d_status;
     JTK_HIP_TRY(hipEventRecord(w.s.ev[0], w.s.st));
     {  // straight from the caller's arrays: about a gigabyte at the headline's size
         int rc;
-        if ((rc = d_cidx.upload(w.cidx, w.s.st)) || (rc = pg_upload(d_seq_off, seq_off, ((size_t)n + 1) * sizeof(uint64_t), w.s.st)) ||
-            (rc = pg_upload(d_ops_off, ops_off, ((size_t)n + 1) * sizeof(uint64_t), w.s.st)) ||
-            (rc = pg_upload(d_tmpl_off, tmpl_off, (n_chunks + 1) * sizeof(uint64_t), w.s.st)) || (rc = pg_upload(d_seq, seq_bases, seq_off[n], w.s.st)) ||
-            (rc = pg_upload(d_ops, ops, ops_off[n], w.s.st)) || (rc = pg_upload(d_tmpl, tmpl_bases, tmpl_off[n_chunks], w.s.st)))
+        if ((rc = d_cidx.upload(w.cidx, w.s.st)) || (rc = d_seq_off.upload(seq_off, (size_t)n + 1, w.s.st)) ||
+            (rc = d_ops_off.upload(ops_off, (size_t)n + 1, w.s.st)) || (rc = d_tmpl_off.upload(tmpl_off, n_chunks + 1, w.s.st)) ||
+            (rc = d_seq.upload(seq_bases, seq_off[n], w.s.st)) || (rc = d_ops.upload(ops, ops_off[n], w.s.st)) ||
+            (rc = d_tmpl.upload(tmpl_bases, tmpl_off[n_chunks], w.s.st)))
             return jtk_fail(rc, "device upload failed");
         JTK_HIP_TRY(hipStreamSynchronize(w.s.st));
     }
-    JTK_HIP_TRY(w.d_num.alloc((size_t)n * sizeof(uint32_t)));
-    JTK_HIP_TRY(w.d_len.alloc((size_t)n * sizeof(uint32_t)));
-    JTK_HIP_TRY(d_status.alloc((size_t)n * sizeof(int32_t)));
+    JTK_HIP_TRY(w.d_num.alloc(n));
+    JTK_HIP_TRY(w.d_len.alloc(n));
+    JTK_HIP_TRY(d_status.alloc(n));
     JTK_HIP_TRY(hipEventRecord(w.s.ev[1], w.s.st));
-    node_errors_kernel<<<pg_blocks(n, 4, PG_WALK_GRID), 256, 0, w.s.st>>>(n, (const uint32_t *)d_cidx.p, (const uint64_t *)d_seq_off.p, (const uint64_t *)d_ops_off.p,
-                                                                        (const uint64_t *)d_tmpl_off.p, (const uint8_t *)d_seq.p, (const uint8_t *)d_ops.p,
-                                                                        (const uint8_t *)d_tmpl.p, (uint32_t *)w.d_num.p, (uint32_t *)w.d_len.p, (int32_t *)d_status.p);
+    node_errors_kernel<<<jtk_blocks(n, 4, PG_WALK_GRID), 256, 0, w.s.st>>>(n, d_cidx.cget(), d_seq_off.cget(), d_ops_off.cget(), d_tmpl_off.cget(), d_seq.cget(),
+                                                                         d_ops.cget(), d_tmpl.cget(), w.d_num.get(), w.d_len.get(), d_status.get());
     JTK_HIP_TRY(hipEventRecord(w.s.ev[2], w.s.st));
     num.resize(n);
     len.resize(n);
     status.resize(n);
-    JTK_HIP_TRY(hipMemcpyAsync(num.data(), w.d_num.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, w.s.st));
-    JTK_HIP_TRY(hipMemcpyAsync(len.data(), w.d_len.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, w.s.st));
-    JTK_HIP_TRY(hipMemcpyAsync(status.data(), d_status.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, w.s.st));
+    JTK_HIP_TRY(w.d_num.download(num.data(), n, w.s.st));
+    JTK_HIP_TRY(w.d_len.download(len.data(), n, w.s.st));
+    JTK_HIP_TRY(d_status.download(status.data(), n, w.s.st));
     JTK_HIP_TRY(hipStreamSynchronize(w.s.st));
     JTK_HIP_TRY(hipGetLastError());
     float ms = 0.f;
-    JTK_HIP_TRY(hipEventElapsedTime(&ms, w.s.ev[0], w.s.ev[1]));
+    JTK_HIP_TRY(w.s.elapsed(0, 1, &ms));
     g_purge_timing[0] = ms;
-    JTK_HIP_TRY(hipEventElapsedTime(&ms, w.s.ev[1], w.s.ev[2]));
+    JTK_HIP_TRY(w.s.elapsed(1, 2, &ms));
     g_purge_timing[1] = ms;
     return 0;
 }
 
 int pg_rates(Work &w) {  // d_num, d_len -> d_rate
-    JTK_HIP_TRY(w.d_rate.alloc((size_t)w.n_nodes * sizeof(double)));
-    rate_kernel<<<pg_blocks(w.n_nodes, 256, PG_GRID), 256, 0, w.s.st>>>(w.n_nodes, (const uint32_t *)w.d_num.p, (const uint32_t *)w.d_len.p, (double *)w.d_rate.p);
+    JTK_HIP_TRY(w.d_rate.alloc(w.n_nodes));
+    rate_kernel<<<jtk_blocks(w.n_nodes, 256, PG_GRID), 256, 0, w.s.st>>>(w.n_nodes, w.d_num.cget(), w.d_len.cget(), w.d_rate.get());
     return 0;
 }
 
@@ -338,7 +317,10 @@ int pg_fit(Work &w, const uint64_t *node_off, const std::vector<uint32_t> &sorte
     for (const uint32_t c : sorted)
         for (uint64_t s = f.slot_off[c]; s < f.slot_off[c + 1]; s++) reg_order.push_back((uint32_t)s);
     const hipStream_t st = w.s.st;
-    DevBuf d_off, d_slot, d_read_of, d_start, d_reg, d_iota, d_slot_s, d_order, d_tmp, d_read_err, d_chunk_err, d_term, d_resid, d_sq;
+    DevArr<uint64_t> d_off;
+    DevArr<uint32_t> d_slot, d_read_of, d_start, d_reg, d_iota, d_slot_s, d_order;
+    DevArr<double> d_read_err, d_chunk_err, d_term, d_resid, d_sq;
+    RocTemp tmp;
     {
         int rc;
         const std::vector<uint64_t> off_v(node_off, node_off + n_reads + 1);
@@ -347,33 +329,30 @@ int pg_fit(Work &w, const uint64_t *node_off, const std::vector<uint32_t> &sorte
             return jtk_fail(rc, "device upload failed");
         JTK_HIP_TRY(hipStreamSynchronize(st));
     }
-    JTK_HIP_TRY(d_iota.alloc((size_t)n * sizeof(uint32_t)));
-    JTK_HIP_TRY(d_slot_s.alloc((size_t)n * sizeof(uint32_t)));
-    JTK_HIP_TRY(d_order.alloc((size_t)n * sizeof(uint32_t)));
-    JTK_HIP_TRY(d_read_err.alloc(std::max<size_t>(n_reads, 1) * sizeof(double)));
-    JTK_HIP_TRY(d_chunk_err.alloc(std::max<size_t>(n_slots, 1) * sizeof(double)));
-    JTK_HIP_TRY(d_term.alloc(std::max<size_t>(n_reads, 1) * sizeof(double)));
-    JTK_HIP_TRY(d_resid.alloc(sizeof(double)));
-    JTK_HIP_TRY(d_sq.alloc((size_t)n * sizeof(double)));
-    const uint32_t node_grid = pg_blocks(n, 256, PG_GRID), read_grid = pg_blocks(n_reads, 256, PG_GRID), slot_grid = pg_blocks(n_slots, 256, PG_GRID);
-    iota_kernel<<<node_grid, 256, 0, st>>>(n, (uint32_t *)d_iota.p);
+    JTK_HIP_TRY(d_iota.alloc(n));
+    JTK_HIP_TRY(d_slot_s.alloc(n));
+    JTK_HIP_TRY(d_order.alloc(n));
+    JTK_HIP_TRY(d_read_err.alloc(n_reads));
+    JTK_HIP_TRY(d_chunk_err.alloc(n_slots));
+    JTK_HIP_TRY(d_term.alloc(n_reads));
+    JTK_HIP_TRY(d_resid.alloc(1));
+    JTK_HIP_TRY(d_sq.alloc(n));
+    const uint32_t node_grid = jtk_blocks(n, 256, PG_GRID), read_grid = jtk_blocks(n_reads, 256, PG_GRID), slot_grid = jtk_blocks(n_slots, 256, PG_GRID);
+    iota_kernel<<<node_grid, 256, 0, st>>>(n, d_iota.get());
     {  // the nodes by slot, once: the radix sort is stable, so a slot's run lists its nodes in read order, then node order
         unsigned end_bit = 1;
         while (end_bit < 32 && (n_slots >> end_bit)) end_bit++;
-        size_t need = 0;
-        JTK_HIP_TRY(rocprim::radix_sort_pairs(nullptr, need, (const uint32_t *)d_slot.p, (uint32_t *)d_slot_s.p, (const uint32_t *)d_iota.p,
-                                              (uint32_t *)d_order.p, (size_t)n, 0u, end_bit, st));
-        JTK_HIP_TRY(d_tmp.alloc(std::max<size_t>(need, 1)));
-        JTK_HIP_TRY(rocprim::radix_sort_pairs(d_tmp.p, need, (const uint32_t *)d_slot.p, (uint32_t *)d_slot_s.p, (const uint32_t *)d_iota.p,
-                                              (uint32_t *)d_order.p, (size_t)n, 0u, end_bit, st));
+        JTK_HIP_TRY(tmp.run([&](void *t, size_t &bytes) {
+            return rocprim::radix_sort_pairs(t, bytes, d_slot.cget(), d_slot_s.get(), d_iota.cget(), d_order.get(), (size_t)n, 0u, end_bit, st);
+        }));
     }
-    const uint32_t *slot = (const uint32_t *)d_slot.p, *rd_of = (const uint32_t *)d_read_of.p;
-    const double *rate = (const double *)w.d_rate.p;
-    double *read_err = (double *)d_read_err.p, *chunk_err = (double *)d_chunk_err.p, *term = (double *)d_term.p;
+    const uint32_t *slot = d_slot.cget(), *rd_of = d_read_of.cget();
+    const double *rate = w.d_rate.cget();
+    double *read_err = d_read_err.get(), *chunk_err = d_chunk_err.get(), *term = d_term.get();
     auto residual = [&](int update, double *out) -> int {
-        read_kernel<<<read_grid, 256, 0, st>>>(n_reads, (const uint64_t *)d_off.p, slot, rate, chunk_err, read_err, term, update);
-        resid_kernel<<<1, 64, 0, st>>>(n_reads, term, n_slots, (const uint32_t *)d_reg.p, chunk_err, (double *)d_resid.p);
-        JTK_HIP_TRY(hipMemcpyAsync(out, d_resid.p, sizeof(double), hipMemcpyDeviceToHost, st));
+        read_kernel<<<read_grid, 256, 0, st>>>(n_reads, d_off.cget(), slot, rate, chunk_err, read_err, term, update);
+        resid_kernel<<<1, 64, 0, st>>>(n_reads, term, n_slots, d_reg.cget(), chunk_err, d_resid.get());
+        JTK_HIP_TRY(d_resid.download(out, 1, st));
         JTK_HIP_TRY(hipStreamSynchronize(st));
         JTK_HIP_TRY(hipGetLastError());
         return 0;
@@ -385,20 +364,20 @@ int pg_fit(Work &w, const uint64_t *node_off, const std::vector<uint32_t> &sorte
     for (f.n_iter = 0;;) {
         if (f.n_iter == PG_MAX_ITER) return jtk_fail(JTK_ERR_CHUNK_FAILED, "estimate_error_rate: no convergence in 100,000 iterations");
         f.n_iter++;
-        slot_kernel<<<slot_grid, 256, 0, st>>>(n_slots, (const uint32_t *)d_start.p, (const uint32_t *)d_order.p, rate, rd_of, read_err, chunk_err);
+        slot_kernel<<<slot_grid, 256, 0, st>>>(n_slots, d_start.cget(), d_order.cget(), rate, rd_of, read_err, chunk_err);
         double resid = 0.0;
         if (int rc = residual(1, &resid)) return rc;
         if (std::fabs(current - resid) < 0.00001) break;  // :104
         current = resid;
     }
-    square_kernel<<<node_grid, 256, 0, st>>>(n, slot, rd_of, rate, chunk_err, read_err, (double *)d_sq.p);
+    square_kernel<<<node_grid, 256, 0, st>>>(n, slot, rd_of, rate, chunk_err, read_err, d_sq.get());
     double sq = 0.0;
-    if (int rc = pg_select(w.s, n, (const double *)d_sq.p, n / 2, &sq)) return rc;  // :123-127
+    if (int rc = pg_select(w.s, n, d_sq.cget(), n / 2, &sq)) return rc;  // :123-127
     f.median = std::sqrt(sq);
     f.read_err.resize(n_reads);
     f.chunk_err.resize(n_slots);
-    if (n_reads) JTK_HIP_TRY(hipMemcpyAsync(f.read_err.data(), read_err, (size_t)n_reads * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (n_slots) JTK_HIP_TRY(hipMemcpyAsync(f.chunk_err.data(), chunk_err, (size_t)n_slots * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (n_reads) JTK_HIP_TRY(d_read_err.download(f.read_err.data(), n_reads, st));
+    if (n_slots) JTK_HIP_TRY(d_chunk_err.download(f.chunk_err.data(), n_slots, st));
     JTK_HIP_TRY(hipStreamSynchronize(st));
     JTK_HIP_TRY(hipGetLastError());
     return 0;
@@ -432,7 +411,7 @@ int pg_total_ms(Work &w) {  // ev[0] (the upload's start, or this call's) to now
     JTK_HIP_TRY(hipEventRecord(w.s.ev[3], w.s.st));
     JTK_HIP_TRY(hipEventSynchronize(w.s.ev[3]));
     float ms = 0.f;
-    JTK_HIP_TRY(hipEventElapsedTime(&ms, w.s.ev[0], w.s.ev[3]));
+    JTK_HIP_TRY(w.s.elapsed(0, 3, &ms));
     g_purge_timing[2] = ms;
     return 0;
 }
@@ -455,7 +434,7 @@ extern "C" int jtk_lc_node_errors(size_t n_reads, const uint64_t *node_off, cons
     if (w.n_nodes && (!err_num || !err_len || !status)) return jtk_fail(JTK_ERR_INVALID_ARG, "null argument");
     if (int rc = jtk_require_device(device)) return rc;
     if (!w.n_nodes) return 0;
-    if (int rc = w.s.create()) return rc;
+    JTK_HIP_TRY(w.s.create(4));
     std::vector<uint32_t> num, len;
     std::vector<int32_t> st;
     if (int rc = pg_walk(w, n_chunks, seq_bases, seq_off, ops, ops_off, tmpl_bases, tmpl_off, num, len, st)) return rc;
@@ -479,7 +458,7 @@ extern "C" int jtk_lc_error_quantile(size_t n_nodes, const uint32_t *err_num, co
     if (int rc = jtk_require_device(device)) return rc;
     Work w;
     w.n_nodes = (uint32_t)n_nodes;
-    if (int rc = w.s.create()) return rc;
+    JTK_HIP_TRY(w.s.create(4));
     {
         int rc;
         const std::vector<uint32_t> nv(err_num, err_num + n_nodes), lv(err_len, err_len + n_nodes);
@@ -488,7 +467,7 @@ extern "C" int jtk_lc_error_quantile(size_t n_nodes, const uint32_t *err_num, co
     }
     if (int rc = pg_rates(w)) return rc;
     double v = 0.0;
-    if (int rc = pg_select(w.s, w.n_nodes, (const double *)w.d_rate.p, pg_quantile_index(w.n_nodes, quantile), &v)) return rc;
+    if (int rc = pg_select(w.s, w.n_nodes, w.d_rate.cget(), pg_quantile_index(w.n_nodes, quantile), &v)) return rc;
     *out = v;
     return 0;
 }
@@ -510,7 +489,7 @@ extern "C" int jtk_lc_estimate_error_rate(size_t n_reads, const uint64_t *node_o
     if (int rc = pg_slots(w, nodes, n_chunks, chunks, f)) return rc;
     if (f.slot_off.back() > chunk_err_cap || (f.slot_off.back() && !chunk_err)) return jtk_fail(JTK_ERR_INVALID_ARG, "chunk_err_cap is too small");
     if (int rc = jtk_require_device(device)) return rc;
-    if (int rc = w.s.create()) return rc;
+    JTK_HIP_TRY(w.s.create(4));
     JTK_HIP_TRY(hipEventRecord(w.s.ev[0], w.s.st));
     {
         int rc;
@@ -548,7 +527,7 @@ extern "C" int jtk_lc_purge_diverged(size_t n_reads, const uint64_t *node_off, c
             return jtk_fail(JTK_ERR_INVALID_ARG, "a node's posterior lies outside n_post");
     if (w.n_nodes == 0) return jtk_fail(JTK_ERR_INVALID_ARG, "no nodes (the reference indexes an empty list)");
     if (int rc = jtk_require_device(device)) return rc;
-    if (int rc = w.s.create()) return rc;
+    JTK_HIP_TRY(w.s.create(4));
     // ---- get_diverged_clusters :299-309 on the device: the rates, their 0.5 quantile, the fit
     std::vector<uint32_t> num, len;
     std::vector<int32_t> st;
@@ -561,7 +540,7 @@ extern "C" int jtk_lc_purge_diverged(size_t n_reads, const uint64_t *node_off, c
     if (n_slots > slot_cap || (n_slots && !diverged)) return jtk_fail(JTK_ERR_INVALID_ARG, "slot_cap is too small");
     if (int rc = pg_rates(w)) return rc;
     double fallback = 0.0;
-    if (int rc = pg_select(w.s, w.n_nodes, (const double *)w.d_rate.p, pg_quantile_index(w.n_nodes, 0.5), &fallback)) return rc;  // :301
+    if (int rc = pg_select(w.s, w.n_nodes, w.d_rate.cget(), pg_quantile_index(w.n_nodes, 0.5), &fallback)) return rc;  // :301
     if (int rc = pg_fit(w, node_off, sorted, fallback, f)) return rc;
     if (int rc = pg_total_ms(w)) return rc;
     g_purge_timing[3] = f.n_iter;

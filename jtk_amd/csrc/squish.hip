@@ -17,7 +17,6 @@
 // (u1, u2) -- the order the sort leaves them in.
 #include <algorithm>
 #include <cstring>
-#include <memory>
 #include <string>
 #include <type_traits>
 #include <unordered_map>
@@ -28,7 +27,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "device_common.h"
-#include "host_common.h"
+#include "prim_host.h"
 
 namespace {
 
@@ -340,11 +339,6 @@ int check_config(const jtk_squish_config_t *cfg) {
     return 0;
 }
 
-struct TempStorage {  // rocprim's two-call protocol on a DevBuf
-    DevBuf buf;
-    size_t bytes = 0;
-};
-
 }  // namespace
 
 extern "C" int jtk_lc_squish_classify(size_t n_pairs, const uint64_t *u1, const uint64_t *u2, const double *ari, const uint64_t *count,
@@ -405,11 +399,15 @@ extern "C" int jtk_lc_squish_clusters(size_t n_reads, const uint64_t *node_off, 
     std::vector<double> p_ari;
     std::vector<uint64_t> p_len;
     if (n_nodes) {
-        hipStream_t st = nullptr;
-        std::unique_ptr<void, void (*)(void *)> st_guard(nullptr, [](void *s) { if (s) (void)hipStreamDestroy((hipStream_t)s); });
-        JTK_HIP_TRY(hipStreamCreate(&st));
-        st_guard.reset(st);
-        DevBuf d_off, d_nodes, d_post, d_rank, d_rank_k, d_bkey, d_reps, d_nd, d_nrec, d_recoff, d_flags;
+        DevStream s;
+        JTK_HIP_TRY(s.create());
+        const hipStream_t st = s.st;
+        DevArr<uint64_t> d_off, d_nrec, d_recoff;
+        DevArr<jtk_cc_node_t> d_nodes;
+        DevArr<double> d_post;
+        DevArr<uint32_t> d_rank, d_rank_k, d_bkey, d_nd;
+        DevArr<uint2> d_reps;
+        DevArr<int> d_flags;
         {
             std::vector<uint64_t> off_v(node_off, node_off + n_reads + 1);
             std::vector<jtk_cc_node_t> node_v(nodes, nodes + n_nodes);
@@ -420,106 +418,90 @@ extern "C" int jtk_lc_squish_clusters(size_t n_reads, const uint64_t *node_off, 
                 return jtk_fail(rc, "device upload failed");
             JTK_HIP_TRY(hipStreamSynchronize(st));  // the staging vectors go out of scope
         }
-        JTK_HIP_TRY(d_bkey.alloc(n_nodes * sizeof(uint32_t)));
-        JTK_HIP_TRY(d_reps.alloc(n_nodes * sizeof(uint2)));
-        JTK_HIP_TRY(d_nd.alloc(n_reads * sizeof(uint32_t)));
-        JTK_HIP_TRY(d_nrec.alloc((n_reads + 1) * sizeof(uint64_t)));
-        JTK_HIP_TRY(d_recoff.alloc((n_reads + 1) * sizeof(uint64_t)));
-        JTK_HIP_TRY(d_flags.alloc(sizeof(int)));
-        JTK_HIP_TRY(hipMemsetAsync(d_flags.p, 0, sizeof(int), st));
-        JTK_HIP_TRY(hipMemsetAsync(d_nrec.p, 0, (n_reads + 1) * sizeof(uint64_t), st));
-        auto blocks = [](uint64_t n, uint32_t per, uint32_t cap) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n + per - 1) / per, 1), cap); };
-        biased_kernel<<<blocks(n_nodes, 256, 4096), 256, 0, st>>>(n_nodes, (const jtk_cc_node_t *)d_nodes.p, (const double *)d_post.p,
-                                                                 (const uint32_t *)d_rank.p, (uint32_t *)d_bkey.p);
-        const uint32_t read_grid = blocks(n_reads, 1, SQ_READ_GRID);
-        distinct_kernel<<<read_grid, 256, 0, st>>>((uint32_t)n_reads, (const uint64_t *)d_off.p, (const jtk_cc_node_t *)d_nodes.p,
-                                                   (const uint32_t *)d_bkey.p, (uint2 *)d_reps.p, (uint32_t *)d_nd.p, (uint64_t *)d_nrec.p);
-        TempStorage tmp;
-        auto scan = [&](auto *in, auto *out, size_t n) -> int {  // exclusive prefix sum of n entries
+        JTK_HIP_TRY(d_bkey.alloc(n_nodes));
+        JTK_HIP_TRY(d_reps.alloc(n_nodes));
+        JTK_HIP_TRY(d_nd.alloc(n_reads));
+        JTK_HIP_TRY(d_nrec.alloc(n_reads + 1));
+        JTK_HIP_TRY(d_recoff.alloc(n_reads + 1));
+        JTK_HIP_TRY(d_flags.alloc(1));
+        JTK_HIP_TRY(d_flags.zero(1, st));
+        JTK_HIP_TRY(d_nrec.zero(n_reads + 1, st));
+        biased_kernel<<<jtk_blocks(n_nodes, 256, 4096), 256, 0, st>>>(n_nodes, d_nodes.cget(), d_post.cget(), d_rank.cget(), d_bkey.get());
+        const uint32_t read_grid = jtk_blocks(n_reads, 1, SQ_READ_GRID);
+        distinct_kernel<<<read_grid, 256, 0, st>>>((uint32_t)n_reads, d_off.cget(), d_nodes.cget(), d_bkey.cget(), d_reps.get(), d_nd.get(), d_nrec.get());
+        RocTemp tmp;
+        auto scan = [&](auto *in, auto *out, size_t n) {  // exclusive prefix sum of n entries
             using T = std::remove_pointer_t<decltype(out)>;
-            size_t need = 0;
-            JTK_HIP_TRY(rocprim::exclusive_scan(nullptr, need, in, out, T(0), n, rocprim::plus<T>(), st));
-            if (need > tmp.bytes) {
-                JTK_HIP_TRY(tmp.buf.alloc(need));
-                tmp.bytes = need;
-            }
-            JTK_HIP_TRY(rocprim::exclusive_scan(tmp.buf.p, need, in, out, T(0), n, rocprim::plus<T>(), st));
-            return 0;
+            return tmp.run([&](void *t, size_t &bytes) { return rocprim::exclusive_scan(t, bytes, in, out, T(0), n, rocprim::plus<T>(), st); });
         };
-        if (int rc = scan((const uint64_t *)d_nrec.p, (uint64_t *)d_recoff.p, n_reads + 1)) return rc;
+        JTK_HIP_TRY(scan(d_nrec.cget(), d_recoff.get(), n_reads + 1));
         uint64_t n_rec = 0;
-        JTK_HIP_TRY(hipMemcpyAsync(&n_rec, (const uint64_t *)d_recoff.p + n_reads, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        JTK_HIP_TRY(d_recoff.download(&n_rec, 1, st, n_reads));
         JTK_HIP_TRY(hipStreamSynchronize(st));
         JTK_HIP_TRY(hipGetLastError());
         if (n_rec >= 0x7fffffffull) return jtk_fail(JTK_ERR_UNSUPPORTED, "2^31 - 1 or more chunk-pair records");
         if (n_rec) {
-            DevBuf d_keys, d_vals, d_keys_s, d_vals_s, d_head, d_segof, d_segstart;
-            JTK_HIP_TRY(d_keys.alloc(n_rec * sizeof(uint64_t)));
-            JTK_HIP_TRY(d_vals.alloc(n_rec * sizeof(uint64_t)));
-            JTK_HIP_TRY(d_keys_s.alloc(n_rec * sizeof(uint64_t)));
-            JTK_HIP_TRY(d_vals_s.alloc(n_rec * sizeof(uint64_t)));
-            emit_kernel<<<read_grid, 64, 0, st>>>((uint32_t)n_reads, (const uint64_t *)d_off.p, (const uint2 *)d_reps.p, (const uint32_t *)d_nd.p,
-                                                  (const uint64_t *)d_recoff.p, n_ranks, (uint64_t *)d_keys.p, (uint64_t *)d_vals.p);
+            DevArr<uint64_t> d_keys, d_vals, d_keys_s, d_vals_s;
+            DevArr<uint32_t> d_head, d_segof, d_segstart;
+            JTK_HIP_TRY(d_keys.alloc(n_rec));
+            JTK_HIP_TRY(d_vals.alloc(n_rec));
+            JTK_HIP_TRY(d_keys_s.alloc(n_rec));
+            JTK_HIP_TRY(d_vals_s.alloc(n_rec));
+            emit_kernel<<<read_grid, 64, 0, st>>>((uint32_t)n_reads, d_off.cget(), d_reps.cget(), d_nd.cget(), d_recoff.cget(), n_ranks, d_keys.get(),
+                                                  d_vals.get());
             {  // the key's significant bits only
                 const unsigned __int128 top = (unsigned __int128)n_ranks * n_ranks - 1;
                 unsigned end_bit = 1;
                 while (end_bit < 64 && (top >> end_bit)) end_bit++;
-                size_t need = 0;
-                JTK_HIP_TRY(rocprim::radix_sort_pairs(nullptr, need, (const uint64_t *)d_keys.p, (uint64_t *)d_keys_s.p, (const uint64_t *)d_vals.p,
-                                                      (uint64_t *)d_vals_s.p, (size_t)n_rec, 0u, end_bit, st));
-                if (need > tmp.bytes) {
-                    JTK_HIP_TRY(tmp.buf.alloc(need));
-                    tmp.bytes = need;
-                }
-                JTK_HIP_TRY(rocprim::radix_sort_pairs(tmp.buf.p, need, (const uint64_t *)d_keys.p, (uint64_t *)d_keys_s.p, (const uint64_t *)d_vals.p,
-                                                      (uint64_t *)d_vals_s.p, (size_t)n_rec, 0u, end_bit, st));
+                JTK_HIP_TRY(tmp.run([&](void *t, size_t &bytes) {
+                    return rocprim::radix_sort_pairs(t, bytes, d_keys.cget(), d_keys_s.get(), d_vals.cget(), d_vals_s.get(), (size_t)n_rec, 0u, end_bit, st);
+                }));
             }
-            const uint64_t *ks = (const uint64_t *)d_keys_s.p, *vs = (const uint64_t *)d_vals_s.p;
-            JTK_HIP_TRY(d_head.alloc((n_rec + 1) * sizeof(uint32_t)));
-            JTK_HIP_TRY(d_segof.alloc((n_rec + 1) * sizeof(uint32_t)));
-            JTK_HIP_TRY(hipMemsetAsync(d_head.p, 0, (n_rec + 1) * sizeof(uint32_t), st));
-            const uint32_t rec_grid = blocks(n_rec, 256, 4096);
-            head_kernel<<<rec_grid, 256, 0, st>>>(n_rec, ks, (uint32_t *)d_head.p);
-            if (int rc = scan((const uint32_t *)d_head.p, (uint32_t *)d_segof.p, n_rec + 1)) return rc;
+            const uint64_t *ks = d_keys_s.cget(), *vs = d_vals_s.cget();
+            JTK_HIP_TRY(d_head.alloc(n_rec + 1));
+            JTK_HIP_TRY(d_segof.alloc(n_rec + 1));
+            JTK_HIP_TRY(d_head.zero(n_rec + 1, st));
+            const uint32_t rec_grid = jtk_blocks(n_rec, 256, 4096);
+            head_kernel<<<rec_grid, 256, 0, st>>>(n_rec, ks, d_head.get());
+            JTK_HIP_TRY(scan(d_head.cget(), d_segof.get(), n_rec + 1));
             uint32_t n_segs = 0;
-            JTK_HIP_TRY(hipMemcpyAsync(&n_segs, (const uint32_t *)d_segof.p + n_rec, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            JTK_HIP_TRY(d_segof.download(&n_segs, 1, st, n_rec));
             JTK_HIP_TRY(hipStreamSynchronize(st));
             JTK_HIP_TRY(hipGetLastError());
-            DevBuf d_survive, d_survidx, d_pairseg;
-            JTK_HIP_TRY(d_segstart.alloc(((size_t)n_segs + 1) * sizeof(uint32_t)));
-            JTK_HIP_TRY(d_survive.alloc(((size_t)n_segs + 1) * sizeof(uint32_t)));
-            JTK_HIP_TRY(d_survidx.alloc(((size_t)n_segs + 1) * sizeof(uint32_t)));
-            JTK_HIP_TRY(hipMemsetAsync(d_survive.p, 0, ((size_t)n_segs + 1) * sizeof(uint32_t), st));
-            seg_start_kernel<<<rec_grid, 256, 0, st>>>(n_rec, n_segs, (const uint32_t *)d_head.p, (const uint32_t *)d_segof.p, (uint32_t *)d_segstart.p);
-            retain_kernel<<<blocks(n_segs, 4, 4096), 256, 0, st>>>(n_segs, (const uint32_t *)d_segstart.p, ks, vs, n_ranks, (const uint32_t *)d_rank_k.p,
-                                                                   cfg->count_thr, (uint32_t *)d_survive.p, (int *)d_flags.p);
-            if (int rc = scan((const uint32_t *)d_survive.p, (uint32_t *)d_survidx.p, (size_t)n_segs + 1)) return rc;
+            DevArr<uint32_t> d_survive, d_survidx, d_pairseg;
+            JTK_HIP_TRY(d_segstart.alloc((size_t)n_segs + 1));
+            JTK_HIP_TRY(d_survive.alloc((size_t)n_segs + 1));
+            JTK_HIP_TRY(d_survidx.alloc((size_t)n_segs + 1));
+            JTK_HIP_TRY(d_survive.zero((size_t)n_segs + 1, st));
+            seg_start_kernel<<<rec_grid, 256, 0, st>>>(n_rec, n_segs, d_head.cget(), d_segof.cget(), d_segstart.get());
+            retain_kernel<<<jtk_blocks(n_segs, 4, 4096), 256, 0, st>>>(n_segs, d_segstart.cget(), ks, vs, n_ranks, d_rank_k.cget(), cfg->count_thr,
+                                                                       d_survive.get(), d_flags.get());
+            JTK_HIP_TRY(scan(d_survive.cget(), d_survidx.get(), (size_t)n_segs + 1));
             uint32_t n_surv = 0;
             int flags = 0;
-            JTK_HIP_TRY(hipMemcpyAsync(&n_surv, (const uint32_t *)d_survidx.p + n_segs, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            JTK_HIP_TRY(hipMemcpyAsync(&flags, d_flags.p, sizeof(int), hipMemcpyDeviceToHost, st));
+            JTK_HIP_TRY(d_survidx.download(&n_surv, 1, st, n_segs));
+            JTK_HIP_TRY(d_flags.download(&flags, 1, st));
             JTK_HIP_TRY(hipStreamSynchronize(st));
             JTK_HIP_TRY(hipGetLastError());
             if (flags & SQ_FLAG_PANIC)
                 return jtk_fail(JTK_ERR_CHUNK_FAILED, "a chunk pair above count_thr names a chunk id that is not in chunks[]");
             if (n_surv) {
-                DevBuf d_pkey, d_pari, d_plen;
-                JTK_HIP_TRY(d_pairseg.alloc((size_t)n_surv * sizeof(uint32_t)));
-                JTK_HIP_TRY(d_pkey.alloc((size_t)n_surv * sizeof(uint64_t)));
-                JTK_HIP_TRY(d_pari.alloc((size_t)n_surv * sizeof(double)));
-                JTK_HIP_TRY(d_plen.alloc((size_t)n_surv * sizeof(uint64_t)));
-                compact_kernel<<<blocks(n_segs, 256, 4096), 256, 0, st>>>(n_segs, (const uint32_t *)d_survive.p, (const uint32_t *)d_survidx.p,
-                                                                         (uint32_t *)d_pairseg.p);
-                table_kernel<<<blocks(n_surv, 1, SQ_TABLE_GRID), 256, 0, st>>>(n_surv, (const uint32_t *)d_pairseg.p, (const uint32_t *)d_segstart.p, ks, vs,
-                                                                               n_ranks, (const uint32_t *)d_rank_k.p, (uint64_t *)d_pkey.p,
-                                                                               (double *)d_pari.p, (uint64_t *)d_plen.p, (int *)d_flags.p);
+                DevArr<uint64_t> d_pkey, d_plen;
+                DevArr<double> d_pari;
+                JTK_HIP_TRY(d_pairseg.alloc(n_surv));
+                JTK_HIP_TRY(d_pkey.alloc(n_surv));
+                JTK_HIP_TRY(d_pari.alloc(n_surv));
+                JTK_HIP_TRY(d_plen.alloc(n_surv));
+                compact_kernel<<<jtk_blocks(n_segs, 256, 4096), 256, 0, st>>>(n_segs, d_survive.cget(), d_survidx.cget(), d_pairseg.get());
+                table_kernel<<<jtk_blocks(n_surv, 1, SQ_TABLE_GRID), 256, 0, st>>>(n_surv, d_pairseg.cget(), d_segstart.cget(), ks, vs, n_ranks, d_rank_k.cget(),
+                                                                                   d_pkey.get(), d_pari.get(), d_plen.get(), d_flags.get());
                 p_key.resize(n_surv);
                 p_ari.resize(n_surv);
                 p_len.resize(n_surv);
-                JTK_HIP_TRY(hipMemcpyAsync(p_key.data(), d_pkey.p, (size_t)n_surv * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-                JTK_HIP_TRY(hipMemcpyAsync(p_ari.data(), d_pari.p, (size_t)n_surv * sizeof(double), hipMemcpyDeviceToHost, st));
-                JTK_HIP_TRY(hipMemcpyAsync(p_len.data(), d_plen.p, (size_t)n_surv * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-                JTK_HIP_TRY(hipMemcpyAsync(&flags, d_flags.p, sizeof(int), hipMemcpyDeviceToHost, st));
+                JTK_HIP_TRY(d_pkey.download(p_key.data(), n_surv, st));
+                JTK_HIP_TRY(d_pari.download(p_ari.data(), n_surv, st));
+                JTK_HIP_TRY(d_plen.download(p_len.data(), n_surv, st));
+                JTK_HIP_TRY(d_flags.download(&flags, 1, st));
                 JTK_HIP_TRY(hipStreamSynchronize(st));
                 JTK_HIP_TRY(hipGetLastError());
                 if (flags & SQ_FLAG_PANIC) return jtk_fail(JTK_ERR_CHUNK_FAILED, "adjusted_rand_index: both_match above the mean of the marginals");
