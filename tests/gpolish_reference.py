@@ -197,8 +197,9 @@ def select(gain, dead, ignore_edge, t, n):
     return edits
 
 
-def polish(tmpl, reads, opss, radius, take_num=0, ignore_edge=0, max_rounds=0):
-    """-> (consensus, ops of every read, dist of every read, rounds)"""
+def polish(tmpl, reads, opss, radius, take_num=0, ignore_edge=0, max_rounds=0, log=None):
+    """-> (consensus, ops of every read, dist of every read, rounds); log: a list that gets (t, n, gain, dead, edits) of every
+    round that scanned"""
     cur = as_seq(tmpl).copy()
     reads = [as_seq(r) for r in reads]
     opss = [np.asarray(o, dtype=np.uint8).copy() for o in opss]
@@ -211,6 +212,8 @@ def polish(tmpl, reads, opss, radius, take_num=0, ignore_edge=0, max_rounds=0):
         gain, dead, opss, dists = gains(cur, reads, opss, radius, take_num)
         stale = False
         edits = select(gain, dead, ignore_edge, t, len(cur))
+        if log is not None:
+            log.append((t, len(cur), gain, dead, list(edits)))
         if not edits:
             break
         nxt = apply_edits(cur, edits)

@@ -120,6 +120,67 @@ def _cases():
     c["infix_free_ends"] = case(random_seq(rng, 25) + core + random_seq(rng, 17), y, [D] * 25 + guide + [D] * 17, 6, True)
     c["infix_no_leading_dels_radius2"] = case(random_seq(rng, 10) + core, y, guide, 2, True)   # only rows 0 ..= 2 are free starts
     c["infix_no_leading_dels_radius12"] = case(random_seq(rng, 10) + core, y, guide, 12, True)
+    # ---- global rows at their piece and stride boundaries, up to the cap: three bases against m at a radius beyond the matrix,
+    # so that each of the four rows is m + 1 cells wide (the 4,097-cell pair that is refused is over_cap_pair)
+    rng = np.random.default_rng(7306)
+    for width in (1024, 1025, 2047, 2048, 2049, 4096):
+        for infix in (False, True):
+            x = random_seq(rng, 3)
+            y = random_seq(rng, width - 1, alphabet=2)
+            c["rows_of_%d_%s" % (width, "infix" if infix else "global")] = case(x, y, [M] * 3, width + 5, infix)
+    # ---- the 64-op loads of the band walk: the op that ends a load (index 63, 127) and the last op do not fit and are skipped.
+    # x is used up after five ops, so every later M and D is skipped, and after 35 more every I
+    x = random_seq(rng, 5)
+    y = random_seq(rng, 40)
+    filler = [M, D, I, D, M, I, I, D] * 16
+    for length in (63, 64, 65, 128):
+        for last in (M, D, I):
+            guide = [M] * 5 + [I] * 35 + filler[:length - 40]
+            guide[length - 1] = last
+            if length > 64:
+                guide[63] = last
+            c["guide_of_%d_ends_in_skipped_%s" % (length, "MDI"[(M, D, I).index(last)])] = case(x, y, guide, 2)
+    # the skipped op in the middle of a guide that goes on: y is used up by a 20-op Ins run in row 0, the M at index 63 of the
+    # load does not fit, and the Dels behind it do
+    x = random_seq(rng, 50)
+    c["skipped_match_then_dels"] = case(x, x[:20], [I] * 20 + [D] * 43 + [M] + [D] * 7, 1)
+    c["skipped_match_then_dels_infix"] = case(x, x[:20], [I] * 20 + [D] * 43 + [M] + [D] * 7, 1, True)
+    # ---- n + 1 = 63, 64, 65, 128, 129 rows: the carry of the prefix sum over the rows' widths
+    for rows in (63, 64, 65, 128, 129):
+        x = random_seq(rng, rows - 1)
+        y, guide = mutate_with_guide(rng, x, 0.1)
+        c["rows%d" % rows] = case(x, y, guide, 3, rows % 2 == 0)
+    # ---- exactly 64 and 128 ops: the walk back flushes its last 64 ops in the loop and nothing behind it
+    x = random_seq(rng, 64)
+    c["nops64"] = case(x, x, [M] * 64, 2)
+    x = random_seq(rng, 120)
+    c["nops128"] = case(x, x[:60] + random_seq(rng, 8) + x[60:], [M] * 60 + [I] * 8 + [M] * 60, 2)
+    x = random_seq(rng, 100)
+    c["nops128_infix"] = case(random_seq(rng, 17) + x + random_seq(rng, 11), x, [D] * 17 + [M] * 100 + [D] * 11, 3, True)
+    # ---- free runs of 63, 64 and 65 Dels in front of and behind an infix placement
+    core = random_seq(rng, 30)
+    for run in (63, 64, 65):
+        c["free_runs_of_%d" % run] = case(random_seq(rng, run) + core + random_seq(rng, run), core, [D] * run + [M] * 30 + [D] * run, 2, True)
+    # ---- gaps that open and close on a piece boundary of the band (band column 63 | 64 and 127 | 128): y has no T, a T in x is
+    # deleted; x is a few bases of y around the boundary, behind an Ins run that row 0 pays for; the radius is beyond the matrix,
+    # so that the band column is the column.  Which event each provides: the census of tests/test_guided_reference.py
+    y = random_seq(rng, 140, alphabet=3)
+    for col in (63, 127):
+        c["ins_opens_behind_column_%d" % col] = case(y[col - 4:col] + y[col + 7:col + 12], y, [], 300)              # an Ins run opens behind a match in column col
+        c["match_behind_del_in_column_%d" % col] = case(y[col - 4:col] + b"T" + y[col:col + 6], y, [], 300)       # a match in column col + 1 behind a Del in column col
+        c["del_in_column_%d" % (col + 1)] = case(y[col - 4:col + 1] + b"T" + y[col + 1:col + 6], y, [], 300)       # a Del in column col + 1 under a match
+        c["match_behind_del_in_column_%d" % (col - 1)] = case(y[col - 5:col - 1] + b"T" + y[col - 1:col + 6], y, [], 300)   # a match in column col behind a Del
+    # a Del run down a column and an Ins run on from it along the last row, where a mismatch costs more than both: the band (the
+    # guide's own path, and a radius shorter than the Ins run) keeps the other corner, Ins first and Del then, out
+    for col, radius, run in ((63, 63, 70), (126, 126, 130)):
+        y = random_seq(rng, col - 3, alphabet=2) + b"GGG" + random_seq(rng, run, alphabet=2)      # GGG can match in one place only
+        c["ins_run_behind_del_in_column_%d" % col] = case(b"GGGTT", y, [I] * (col - 3) + [M] * 3 + [D] * 2 + [I] * run, radius,
+                                                          scores=(1, -20, -3, -1))
+    # ---- ties at the largest scores the call takes: every unit is 1,024, with a gap's extension at that price and free
+    for scores, tag in (((1024, -1024, -1024, -1024), "s1024"), ((1024, -1024, -1024, 0), "s1024_ext0")):
+        for name in ("all_tie", "all_tie_longer_y", "all_tie_infix", "mismatch_or_two_opens", "one_long_gap", "two_short_gaps", "low_complexity0",
+                     "low_complexity1", "low_complexity2", "low_complexity3", "hand_two_placements"):
+            c[name + "_" + tag] = dict(c[name], scores=scores)
     return c
 
 
@@ -151,6 +212,65 @@ def over_wide_pair():
     return case(x, y, [M] * 25 + [I] * 5000 + [M] * 25, 4)
 
 
+def over_cap_pair(infix=False):
+    """rows_of_4096 with one base more: four rows of 4,097 cells, one more than JTK_GUIDED_MAX_WIDTH"""
+    rng = np.random.default_rng(7307)
+    return case(random_seq(rng, 3), random_seq(rng, 4096, alphabet=2), [M] * 3, 5000, infix)
+
+
+LARGE_BATCH_WIDE = 520
+
+
+def large_batch(seed=7308):
+    """520 pairs of one to three rows by 513 ..= 700 cells (a radius beyond the matrix), more than the 512 waves of the
+    global-rows launch, so that waves take a second pair on rows their first one left; every fifth pair in between is one for
+    the LDS launch.  No two wide pairs have the same width and content."""
+    rng = np.random.default_rng(seed)
+    out, wide = [], 0
+    while wide < LARGE_BATCH_WIDE:
+        if len(out) % 5 == 4:
+            x = random_seq(rng, int(rng.integers(1, 40)))
+            y, guide = mutate_with_guide(rng, x, 0.2)
+            out.append(case(x, y, guide, int(rng.integers(0, 9))))
+            continue
+        n, m = int(rng.integers(0, 3)), int(rng.integers(512, 700))
+        x = random_seq(rng, n)
+        y = random_seq(rng, m, alphabet=(4, 2)[wide % 2])
+        out.append(case(x, y, [int(v) for v in rng.integers(0, 4, int(rng.integers(0, 6)))], m + 1 + wide % 3))
+        wide += 1
+    return out
+
+
+MAX_LEN = 32000      # GD_MAX_LEN of guided.hip
+MAX_SCORES = ((1024, -1024, -1024, -1024), (1024, -1024, -1024, 0))      # +- JTK_GUIDED_MAX_SCORE
+
+
+def limit_pair(scores=SCORES, radius=2):
+    """32,000 against 32,000 bases, the longest the call takes, mostly mismatching: x is a run of A with a C every 997 bases, y a
+    run of C with an A every 991 bases, so fewer than a hundred columns of any diagonal match.  With every unit at 1,024 the
+    score is below -3e7 (asserted in tests/test_guided_reference.py)."""
+    x = bytearray(b"A" * MAX_LEN)
+    y = bytearray(b"C" * MAX_LEN)
+    x[::997] = b"C" * len(x[::997])
+    y[::991] = b"A" * len(y[::991])
+    return case(x, y, [M] * MAX_LEN, radius, scores=scores)
+
+
+# (scores, radius) the 32,000-base pair runs at.  The first three are what the limit and the score range ask for; with a free
+# extension a radius of 2 lets runs of four gaps undercut four mismatches, so the -3e7 case is at radius 1 and radius 2 is a
+# fourth run, whose path is runs of Dels and Ins throughout.
+LIMIT_RUNS = ((SCORES, 2), (MAX_SCORES[0], 2), (MAX_SCORES[1], 1), (MAX_SCORES[1], 2))
+
+
+def over_length_batch(seed=7309):
+    """five pairs: pair 1 has 32,001 x bases, pair 3 has 32,001 y bases, the others are small"""
+    rng = np.random.default_rng(seed)
+    out = mixed_batch(seed, count=5)
+    out[1] = case(random_seq(rng, MAX_LEN + 1), random_seq(rng, 20), [M] * 20, 2)
+    out[3] = case(random_seq(rng, 20), random_seq(rng, MAX_LEN + 1), [M] * 20, 2)
+    return out
+
+
 def big_pair(radius, infix=False):
     """2,000 against about 2,100 bases at 10 % error, guided by the alignment that made them"""
     rng = np.random.default_rng(7304)
@@ -173,6 +293,46 @@ def _expected(key):
 def expected(cs):
     """the reference's answer for a case, computed once and shared (callers must not change it)"""
     return _expected(_key(cs))
+
+
+EVENT_STATES = "MDI"
+
+
+def events(cs):
+    """the events on the optimal path of a case that the kernel's structure tells apart (the census of
+    tests/test_guided_reference.py): a set of strings"""
+    trace = {}
+    out = G.align_guided(cs["x"], cs["y"], cs["guide"], cs["radius"], infix=cs["infix"], scores=cs["scores"], trace=trace)
+    assert out == expected(cs)
+    band, found = trace["band"], set()
+    run_end = None
+    for state, i, j, pred in trace["steps"]:
+        name = "%s from %s" % (EVENT_STATES[state], EVENT_STATES[pred])
+        found.add(name)
+        col = j - band[i][0]
+        if col >= 64 and col % 64 in (0, 63):
+            found.add("%s at band column %d mod 64" % (name, col % 64))
+        if state == 0 and j - 1 in band[i - 1]:
+            found.add("M from the %s cell of the row above" % ("first", "last")[band[i - 1].index(j - 1)])
+        if state == 1 and j in band[i - 1]:
+            found.add("D from the %s cell of the row above" % ("first", "last")[band[i - 1].index(j)])
+        if state == 2:      # (the walk goes back: the run's last cell comes first)
+            run_end = col if run_end is None else run_end
+            if pred != 2:
+                if run_end // 64 - (col - 1) // 64 >= 2:
+                    found.add("an I gap over two piece boundaries")
+                run_end = None
+    if trace["tied_end_rows"] > 1:
+        found.add("the end row chosen among tied rows")
+    if trace["tied_states"] > 1:
+        found.add("the end state chosen among tied states")
+    return found
+
+
+ALL_EVENTS = (["%s from %s" % (a, b) for a in EVENT_STATES for b in EVENT_STATES]
+              + ["%s from %s at band column %d mod 64" % (a, b, c) for a in EVENT_STATES for b in EVENT_STATES for c in (0, 63)]
+              + ["%s from the %s cell of the row above" % (a, b) for a in "MD" for b in ("first", "last")]
+              + ["an I gap over two piece boundaries", "the end row chosen among tied rows", "the end state chosen among tied states"])
 
 
 def row_widths(cs):

@@ -62,8 +62,10 @@ def check_scores(scores):
         raise ValueError("scores need open <= ext <= 0 and mismatch <= 0 <= match")
 
 
-def align_guided(x, y, guide, radius, infix=False, scores=ALN_PARAMETER):
-    """-> dict(score, start, end, ops); x and y are sequences of comparable items (bytes, str, lists)"""
+def align_guided(x, y, guide, radius, infix=False, scores=ALN_PARAMETER, trace=None):
+    """-> dict(score, start, end, ops); x and y are sequences of comparable items (bytes, str, lists).
+    trace: a dict that gets the band, the steps of the walk back as (state, i, j, state of the predecessor) with 0 = M, 1 = D,
+    2 = I, the number of end rows that hold the best score and the number of states that hold it in the end cell"""
     check_scores(scores)
     match, mismatch, gap_open, gap_ext = scores
     n, m = len(x), len(y)
@@ -99,7 +101,12 @@ def align_guided(x, y, guide, radius, infix=False, scores=ALN_PARAMETER):
     state = [get(t, end, m) for t in tables].index(score)
     i, j = end, m
     ops = []
+    steps = []
+    if trace is not None:
+        trace.update(band=band, steps=steps, tied_states=[get(t, end, m) for t in tables].count(score),
+                     tied_end_rows=sum(best_of(r, m) == score for r in range(n + 1) if band[r][1] == m) if infix else 1)
     while True:
+        at = (state, i, j)
         if state == 0:
             if j == 0 and (infix or i == 0):
                 break
@@ -118,6 +125,7 @@ def align_guided(x, y, guide, radius, infix=False, scores=ALN_PARAMETER):
             j -= 1
             cand = [get(M, i, j) + gap_open, get(D, i, j) + gap_open, get(I, i, j) + gap_ext]
         state = cand.index(value)
+        steps.append(at + (state,))
     start = i
     ops = [DEL] * start + ops[::-1] + [DEL] * (n - end)
     return dict(score=int(score), start=start, end=end, ops=ops)

@@ -5,7 +5,8 @@ import pytest
 
 import gpolish_cases as K
 import gpolish_reference as gp
-from phmm_reference import edited
+from guided_reference import band_cells
+from phmm_reference import edited, inactive
 
 
 def test_wide_table_is_the_unbanded_distance_to_the_edited_template():
@@ -107,3 +108,105 @@ def test_first_best_row_on_a_homopolymer():
     gain, dead, _, _ = gp.gains(tmpl, reads[:1], guides[:1], radius, 0)       # the read with one A more
     assert gain[2, 4] == gain[2, 8] == 1
     assert gp.select(gain, dead, 0, 0, len(tmpl))[0] == (0, 4)
+
+
+def band_widths(tmpl, read, guide, radius):
+    band = band_cells(len(tmpl), len(read), np.asarray(guide).tolist(), radius)
+    return [hi - lo + 1 for lo, hi in band.values()]
+
+
+SIZE_LIMIT = 777541      # the band cells of guided_cases.big_pair(200): no case here costs the reference more for one read
+
+
+def test_ring_cases_have_the_widths_they_are_named_for():
+    """the storage path of every read of the cases made for the global ring: m + 1 <= 512 reserves no ring, a widest row of at
+    most 512 cells is kept in LDS, a wider one in the ring, up to 4,096"""
+    def widest(name):
+        tmpl, reads, guides, radius = K.TABLE[name]()
+        return len(tmpl), [(len(r), max(band_widths(tmpl, r, g, radius)), sum(band_widths(tmpl, r, g, radius))) for r, g in zip(reads, guides)]
+    for n in (1, 5, 12):
+        got_n, reads = widest("ring_n%d_wide" % n)
+        assert got_n == n and [m for m, _, _ in reads] == [513, 600, 700] and all(w == m + 1 for m, w, _ in reads)
+        got_n, reads = widest("ring_n%d_ins_run" % n)
+        assert got_n == n and all(m == n + 520 and 521 <= w <= 525 and cells <= 525 + 5 * n for m, w, cells in reads)
+    _, reads = widest("ring_mixed_block")
+    kinds = ["none" if m + 1 <= 512 else "lds" if w <= 512 else "ring" for m, w, _ in reads]
+    assert kinds == ["none", "lds", "ring", "ring", "ring", "none", "lds", "ring"]      # two blocks of four waves, each with all three
+    _, reads = widest("ring_width4096")
+    assert reads[0][:2] == (4095, 4096) and reads[1][1] <= 512
+    for name in K.TABLE:
+        assert all(cells <= SIZE_LIMIT for _, _, cells in widest(name)[1]), name
+    # the polish case stays in the ring over its rounds: the radius is beyond every read, and every read is longer than 512
+    c = K.case("ring_rounds")
+    log = K.rounds_log("ring_rounds")
+    assert len(log) == 2 and log[0][1] != log[1][1] and len(K.expected("ring_rounds")[0]) != log[1][1]      # n differs from round to round
+    assert all(len(r) + 1 > 512 and c["radius"] > len(r) for r in c["reads"])
+
+
+def test_sixteen_bit_cells_above_32767():
+    """the distance and the largest stored F of the two f16 cases lie above 32,767 and below 65,535, the stored infinity; the
+    band admits so little that the banded distance is far above the edit distance (n substitutions)"""
+    for name, (tmpl, reads, guides, radius) in (("table", K.TABLE["f16_table"]()), ("polish", K.f16_case(K.MAX_LEN, 1))):
+        dist, _ops, F, _band = gp.fill(tmpl, reads[0], guides[0], radius)
+        top = max(F.values())
+        print(name, "n", len(tmpl), "dist", dist, "largest F", top, "cells", len(F))
+        assert 32767 < dist <= top < 65535 and len(tmpl) < dist and len(F) <= SIZE_LIMIT
+    assert len(K.case("f16_polish")["tmpl"]) == len(K.case("f16_polish")["reads"][0]) == 32000
+    assert K.table_expected("f16_table")[1][0][0] > 32767 and K.expected("f16_polish")[2][0] > 32767
+
+
+def test_refused_pileups_and_what_the_reference_does_with_them():
+    assert len(K.case("too_long_template")["tmpl"]) == 32001 and len(K.case("too_long_read")["reads"][1]) == 32001
+    # the reference has no buffers to outgrow: it goes on to a consensus far longer than the device's tmpl_cap = n + 64 + n / 8
+    c = K.case("outgrows")
+    cons = K.expected("outgrows")[0]
+    assert len(c["tmpl"]) == 40 and K.OUTGROWS_CAP == 109 and len(cons) > 2 * K.OUTGROWS_CAP
+    assert any(n > K.OUTGROWS_CAP for _t, n, _g, _d, _e in K.rounds_log("outgrows"))
+
+
+def census():
+    """event -> the polish case that provides it, from the rounds of every named polish case"""
+    found = {}
+    for name in sorted(K.POLISH):
+        e = K.case(name)["ignore_edge"]
+        for t, n, gain, dead, edits in K.rounds_log(name):
+            grow = 0
+            for pos, row in edits:
+                found.setdefault("row %d applied" % row, name)
+                grow += 1 if 4 <= row < 8 else row - 7 if 8 <= row < 11 else 10 - row if row >= 11 else 0
+                if 4 <= row <= 10 and pos == 0:
+                    found.setdefault("an insertion edit at position 0", name)
+                if row >= 11 and pos + (row - 10) == n - 1:
+                    found.setdefault("a delete edit that ends at n - 2, the last that exists", name)
+            for (a, row), (b, _) in zip(edits, edits[1:]):
+                if b - a == (row - 10 if row >= 11 else 1) + inactive(t):
+                    found.setdefault("two edits as close as inactive lets them be", name)
+                if row < 11 and b - a == 1 + inactive(t):
+                    found.setdefault("two edits 1 + inactive apart", name)
+            if grow >= 3:
+                found.setdefault("a round that adds three bases or more", name)
+            if grow <= -3:
+                found.setdefault("a round that removes three bases or more", name)
+            for pos in [p for p in range(n) if p < e or p + e >= n]:
+                alive = [int(gain[pos, q]) for q in range(gp.NUM_ROW) if not dead[pos, q]]
+                if alive and max(alive) >= 1:
+                    found.setdefault("ignore_edge cuts off an edit that would apply", name)
+    return found
+
+
+# Copying one base (row 8) makes the template that inserting that base (rows 4-7) makes, and the first best row wins: where the
+# band holds both entries row 8 is never applied.  It is compared entry by entry in the tables, not as an edit.
+CENSUS = ["row %d applied" % row for row in range(gp.NUM_ROW) if row != 8] + [
+    "an insertion edit at position 0", "a delete edit that ends at n - 2, the last that exists", "two edits 1 + inactive apart",
+    "two edits as close as inactive lets them be", "a round that adds three bases or more", "a round that removes three bases or more",
+    "ignore_edge cuts off an edit that would apply"]
+
+
+def test_census_of_the_polish_cases():
+    """which case makes the scan and the surgery take which turn: every row but 8 as the applied edit, and the edits at the edges.
+    A delete edit never reaches n - 1 (edited() has none with p + d >= n), so the last one that exists stands for it"""
+    found = census()
+    for event in CENSUS:
+        print(event, "<-", found.get(event))
+    assert [event for event in CENSUS if event not in found] == []
+    assert all(edited(np.zeros(9, dtype=np.uint8) + 65, 9 - d, 10 + d) is None for d in (1, 2, 3))

@@ -1,6 +1,18 @@
 """jtk_lc_polish_guided on the device against tests/gpolish_reference.py, no tolerance: consensus bytes, every op, every
 distance, rounds and status of the cases of tests/gpolish_cases.py, and through jtk_lc_debug_guided_table every entry of the
-14-row table, dead ones included.  The CPU side (the reference against its own properties) is tests/test_gpolish_reference.py."""
+14-row table, dead ones included.  The CPU side (the reference against its own properties, the storage path of every read of the
+ring cases, the 16-bit condition and the census of the applied edits) is tests/test_gpolish_reference.py.
+
+Duration of `pytest tests -m gpu` on one MI355X: GPU_SUITE_SECONDS of tests/test_gpu_guided.py.  TEST_SECONDS is the call time
+of each new test in a run of this module on its own; the new cases that are not listed take 0.01 to 0.04 s.
+
+Seeded faults, each in an uncommitted copy of gpolish.hip, one build and one run of this module and tests/test_gpolish_abi.py
+each: KERNEL_SEEDED_FAULTS below.  Neither fault fails any test of the two modules as they were before the ring and 16-bit cases
+(20 passed, run once against the same libraries).
+
+Not reached: gp_rethread_kernel's `overflow` arm.  Re-threaded ops consume the new template and the read, so they are at most
+new_n + m <= tmpl_cap + m <= ops_cap long whenever gp_select_kernel let the round through; the arm is a second guard behind
+`n + grow > tmpl_cap`, which test_pileups_beyond_the_limits_beside_pileups_that_are_answered takes."""
 import numpy as np
 import pytest
 
@@ -11,6 +23,21 @@ from jtk_amd import api, batch as jb, ffi
 pytestmark = pytest.mark.gpu
 
 UNSUPPORTED, CHUNK_FAILED = -3, -6
+
+TEST_SECONDS = {
+    "test_table[f16_table]": 0.91, "test_table[ring_width4096]": 0.09, "test_table[ring_n12_wide]": 0.08, "test_polish_case[ring_rounds]": 0.28,
+    "test_polish_case[f16_polish]": 0.18, "test_rounds_in_the_global_ring_in_three_slices_or_more": 0.29,
+    "test_pileups_beyond_the_limits_beside_pileups_that_are_answered": 0.05,
+}
+KERNEL_SEEDED_FAULTS = {
+    "gpolish.hip, gp_read: where the ring is in global memory, the backward fill reads the row below from ring row (i + 2) & 3":
+        "test_table[ring_n1_wide, ring_n5_wide, ring_n12_wide, ring_n1_ins_run, ring_n5_ins_run, ring_n12_ins_run, ring_mixed_block, "
+        "ring_width4096], test_polish_case[ring_rounds], test_rounds_in_the_global_ring_in_three_slices_or_more: table entries, then "
+        "the consensus; the 26 other tests pass",
+    "gpolish.hip, gp_sat: a cell saturates to the stored infinity from 32,767 on":
+        "test_table[f16_table], test_polish_case[f16_polish]: the distance is lost and the call returns JTK_ERR_INTERNAL (a walk "
+        "left the band); the 34 other tests pass",
+}
 
 
 @pytest.fixture(scope="module")
@@ -110,6 +137,51 @@ def test_mixed_batch_in_three_slices_or_more(lib):
     print("work bytes", need, "slices", slices)
     assert slices >= 3
     check_mixed(out, cases, b, bad)
+
+
+def test_rounds_in_the_global_ring_in_three_slices_or_more(lib):
+    """ring_rounds (every row of every read is wider than 512 cells, and the template changes between the rounds) beside two
+    LDS-sized pile-ups, with the work-area budget at a quarter of what the reads take: the rings are carved per slice"""
+    names = ["planted70", "ring_rounds", "many_reads"]
+    cases, b = pack(names)
+    radii = np.array([c["radius"] for c in cases], dtype=np.uint32)
+    whole = api.polish_guided(b, radii, max_rounds=K.MIXED_ROUNDS)
+    assert api.gpolish_timing()["slices"] == 1
+    need = api.gpolish_timing()["work_bytes"]
+    try:
+        api.guided_scratch_cap(max(need // 4, 1))
+        out = api.polish_guided(b, radii, max_rounds=K.MIXED_ROUNDS)
+        slices = api.gpolish_timing()["slices"]
+    finally:
+        api.guided_scratch_cap(0)
+    print("work bytes", need, "slices", slices)
+    assert slices >= 3 and K.case("ring_rounds")["max_rounds"] == K.MIXED_ROUNDS
+    for c, name in enumerate(names):
+        check(out, c, b, K.mixed_expected(name), name)
+    for key in ("cons", "cons_off", "ops_out", "ops_out_off", "dist"):
+        assert bytes(out[key]) == bytes(whole[key]), key
+
+
+def test_pileups_beyond_the_limits_beside_pileups_that_are_answered(lib):
+    """a template of 32,001 bases and a read of 32,001 bases are refused on the host (JTK_ERR_UNSUPPORTED); a template of 40
+    bases under reads of 300 outgrows tmpl_cap = 109 in some round and is refused there (JTK_ERR_CHUNK_FAILED).  The reference has
+    no cap and polishes that pile-up on to more than 218 bases (tests/test_gpolish_reference.py): this is a refusal, not parity.
+    The pile-ups between them are answered"""
+    cases, b = pack(K.LIMITS)
+    radii = np.array([c["radius"] for c in cases], dtype=np.uint32)
+    with pytest.raises(ffi.JtkError):
+        api.polish_guided(b, radii)
+    out = api.polish_guided(b, radii, raise_on_chunk_failure=False)
+    assert out["rc"] == CHUNK_FAILED
+    for c, name in enumerate(K.LIMITS):
+        if name in K.LIMITS_STATUS:
+            print(name, "status", int(out["result"][c]["status"]), "rounds", int(out["result"][c]["polish_rounds"]))
+            assert int(out["result"][c]["status"]) == K.LIMITS_STATUS[name], name
+            assert int(out["cons_off"][c + 1]) == int(out["cons_off"][c]), name
+            for r in b.chunk_reads(c):
+                assert int(out["ops_out_off"][r + 1]) == int(out["ops_out_off"][r]) and int(out["dist"][r]) == 0xFFFFFFFF, name
+        else:
+            check(out, c, b, K.expected(name), name)
 
 
 def test_take_consensus_of_two_chunks_with_two_clusters(lib):

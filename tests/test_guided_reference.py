@@ -91,6 +91,83 @@ def test_named_cases_spell_their_scores_and_have_the_widths_they_are_named_for()
     assert narrow["start"] <= 2 and 9 <= wide["start"] <= 11 and wide["score"] > narrow["score"]
 
 
+SIZE_LIMIT = sum(K.row_widths(K.big_pair(200)))      # no newer case costs the reference more band cells than this one
+
+
+def test_cases_at_the_limits_are_what_they_are_named_for():
+    """the widths, lengths, row counts, op counts and scores that the cases at the kernel's limits are built for, and the size
+    condition: none of them costs the reference more band cells than big_pair(200)"""
+    assert SIZE_LIMIT == 777541
+    for name, cs in K.CASES.items():
+        assert sum(K.row_widths(cs)) <= SIZE_LIMIT, name
+    # ---- global rows up to the cap, and one cell over it
+    for width in (1024, 1025, 2047, 2048, 2049, 4096):
+        for tag in ("global", "infix"):
+            assert set(K.row_widths(K.CASES["rows_of_%d_%s" % (width, tag)])) == {width}
+    assert api.ffi.GUIDED_MAX_WIDTH == 4096
+    for infix in (False, True):
+        assert set(K.row_widths(K.over_cap_pair(infix))) == {4097} and K.over_cap_pair(infix)["infix"] == infix
+    # ---- more global-row pairs than the 512 waves that run them, no two alike, LDS-sized pairs in between
+    batch = K.large_batch()
+    wide = [cs for cs in batch if max(K.row_widths(cs)) > 512]
+    assert len(wide) == K.LARGE_BATCH_WIDE >= 520 and len(batch) - len(wide) >= 100
+    assert all(513 <= w <= 700 for cs in wide for w in K.row_widths(cs)) and all(1 <= len(K.row_widths(cs)) <= 3 for cs in wide)
+    assert all(max(K.row_widths(cs)) <= 512 for cs in batch if cs not in wide)
+    assert len({(cs["x"], cs["y"]) for cs in wide}) == len(wide)
+    assert {len(K.row_widths(cs)) for cs in wide} == {1, 2, 3}
+    # the pairs a wave takes second, on the rows that a wide pair of other content left
+    second = [(batch[at - 512], batch[at]) for at in range(512, len(batch)) if batch[at] in wide and batch[at - 512] in wide]
+    assert len(second) >= 64 and all(len(a["y"]) != len(b["y"]) or a["y"] != b["y"] for a, b in second)
+    assert sum(sum(K.row_widths(cs)) for cs in batch) <= SIZE_LIMIT
+    # ---- the length limit and the score range
+    for scores, radius in K.LIMIT_RUNS:
+        cs = K.limit_pair(scores, radius)
+        assert len(cs["x"]) == len(cs["y"]) == K.MAX_LEN == 32000 and sum(K.row_widths(cs)) <= SIZE_LIMIT
+        out = K.expected(cs)
+        assert G.score_of_ops(cs["x"], cs["y"], out["ops"], out["start"], out["end"], scores) == out["score"]
+        if (scores, radius) in ((K.MAX_SCORES[0], 2), (K.MAX_SCORES[1], 1)):
+            assert out["score"] < -3e7, (scores, radius, out["score"])
+    assert max(abs(s) for scores in K.MAX_SCORES for s in scores) == 1024      # JTK_GUIDED_MAX_SCORE (include/jtk_lc.h)
+    over = K.over_length_batch()
+    assert (len(over[1]["x"]), len(over[3]["y"])) == (32001, 32001) and all(len(over[p]["x"]) <= 120 for p in (0, 2, 4))
+    # ---- the 64-op loads of the walk, the 64-row steps of the prefix sum, the 64-op stores of the walk back
+    for length in (63, 64, 65, 128):
+        for last in "MDI":
+            cs = K.CASES["guide_of_%d_ends_in_skipped_%s" % (length, last)]
+            assert len(cs["guide"]) == length
+            path = G.guide_path(len(cs["x"]), len(cs["y"]), cs["guide"][:40])
+            assert path[-1] == (len(cs["x"]), len(cs["y"]))      # the table's corner after 40 ops: every later op is skipped
+            assert cs["guide"][length - 1] == dict(M=M, D=D, I=I)[last] and (length <= 64 or cs["guide"][63] == cs["guide"][length - 1])
+    cs = K.CASES["skipped_match_then_dels"]
+    path = G.guide_path(50, 20, cs["guide"])      # 63 ops that fit, the M that does not, seven Dels that do
+    assert cs["guide"][63] == M and path[63] == (43, 20) and path[64] == (44, 20) and path[-1] == (50, 20) and len(path) == 71
+    for rows in (63, 64, 65, 128, 129):
+        assert len(K.row_widths(K.CASES["rows%d" % rows])) == rows
+    for name, nops in (("nops64", 64), ("nops128", 128), ("nops128_infix", 128)):
+        assert len(K.expected(K.CASES[name])["ops"]) == nops, name
+    for run in (63, 64, 65):
+        out = K.expected(K.CASES["free_runs_of_%d" % run])
+        assert (out["start"], out["end"]) == (run, run + 30) and out["ops"] == [D] * run + [M] * 30 + [D] * run
+
+
+def test_census_of_the_named_cases():
+    """every event on the optimal path that the kernel's structure tells apart is provided by a named case: the nine (state,
+    predecessor) steps, each of them in the first and in the last column of a 64-column piece behind the first (an I step in the
+    first column takes the carried left neighbour), an I gap over two piece boundaries (the carried running maximum, twice), M
+    and D steps from the first and the last cell of the row above, and ties between end rows and between end states"""
+    found = {}
+    for name, cs in K.CASES.items():
+        for event in K.events(cs):
+            found.setdefault(event, name)
+    for event in K.ALL_EVENTS:
+        print(event, "<-", found.get(event))
+    assert len(K.ALL_EVENTS) == 9 + 18 + 4 + 3
+    assert [event for event in K.ALL_EVENTS if event not in found] == []
+    # the carried left neighbour of both kinds, by the cases made for it
+    assert "I from M at band column 0 mod 64" in K.events(K.CASES["ins_opens_behind_column_127"])
+    assert "I from D at band column 0 mod 64" in K.events(K.CASES["ins_run_behind_del_in_column_63"])
+
+
 def test_encode_reference_hand_worked_trials():
     cons = b"ACGTTGCAAGCT"
     # lower bound: (12 - 4) / 12 > 0.5
@@ -135,6 +212,40 @@ def test_named_trials_have_the_verdicts_they_are_named_for():
     t = EC.CASES["band_is_wider"]
     assert EC.expected(EC.CASES["band_is_10"])["band"] == 10 and EC.expected(t)["band"] == E.band_of(t["end"] - t["start"], 0.5) > 30
     assert EC.expected(EC.CASES["cons_shorter_than_edge"])["head_len"] < 100
+
+
+def test_trials_at_the_edges_of_the_counts_are_what_they_are_named_for():
+    out = EC.expected(EC.CASES["cons_len1"])      # 0 / 0 in the head: the verdict is min(NaN, tail) = the tail's
+    assert (out["head_len"], out["head_match"], out["tail_len"], out["ops_len"], out["verdict"]) == (0, 0, 1, 1, E.ACCEPTED)
+    for n in (99, 100, 101):
+        t = EC.CASES["cons_len%d" % n]
+        assert len(t["cons"]) == n and EC.expected(t)["verdict"] == E.ACCEPTED
+    for lead, trail in ((63, 65), (64, 64), (65, 63)):
+        for tag, forward in (("", True), ("_reverse", False)):
+            t = EC.CASES["trims_%d_%d%s" % (lead, trail, tag)]
+            out = EC.expected(t)
+            assert (out["trim_head"], out["trim_tail"]) == (lead, trail) and t["is_forward"] == forward
+            assert out["position_from_start"] == t["start"] + (lead if forward else trail)
+    assert EC.expected(EC.CASES["ops_len64"])["ops_len"] == 64 and EC.expected(EC.CASES["ops_len128"])["ops_len"] == 128
+    assert len(EC.expected(EC.CASES["ops_len64"])["ops"]) == 64
+    # the trial with a band of more than 256, under the size condition in each of its passes
+    t = EC.wide_band_trial()
+    wl = t["end"] - t["start"]
+    assert E.band_of(wl, t["sim_thr"]) > 256 and len(t["cons"]) + 1 > 512 and (wl + 1) * (2 * E.band_of(wl, t["sim_thr"]) + 1) <= SIZE_LIMIT
+    # the refused trials pass the filter, and the one for the guided pass gets a guide with one Ins run of 4,200
+    for t in (EC.refused_by_infix(), EC.refused_by_guided_pass(), EC.refused_by_guided_pass(False), EC.refused_by_length()):
+        assert not t["sim_thr"] < max(len(t["cons"]) - (t["end"] - t["start"]), 0) / len(t["cons"])
+    assert len(EC.refused_by_infix()["cons"]) == 32001 and len(EC.refused_by_length()["chunk_seq"]) == 32001
+    for forward in (True, False):
+        t = EC.refused_by_guided_pass(forward)
+        window = E.window_of(t["read"], t["start"], t["end"], forward)
+        guide = E.first_guide(t["cons"], window)
+        assert guide == [M] * 100 + [I] * 4200 + [M] * 100 and len(window) <= 32000 and len(t["cons"]) <= 32000
+        assert max(K.row_widths(K.case(window, t["cons"], guide, E.band_of(len(window), t["sim_thr"]), True))) > api.ffi.GUIDED_MAX_WIDTH
+    trials, refused = EC.refusal_batch()
+    assert sorted(refused) == [0, 4, 6, len(trials) - 1] and [t["sim_thr"] for k, t in enumerate(trials) if k in refused] == [0.97, 0.25, 0.999, 0.97]
+    verdicts = [EC.expected(t)["verdict"] for t in EC.shared_trials()]
+    assert set(verdicts) == {E.ACCEPTED, E.LOWER_BOUND, E.REJECTED}
 
 
 def test_fill_trials_is_try_encoding_heads_arithmetic():
