@@ -1,6 +1,7 @@
-// chain_layout.h -- included by mcmc_kernels.hip alone: the ring's geometry, the control block and ONE list of the arrays of a
-// chunk's work area, from which the device's carve (lds_carve, chain_lds.h) and the host's sizes below both follow.
-// Plain C++ (tests/test_chain_layout.py compiles it without HIP); wants JTK_MAX_COPY (device_common.h).
+// chain_layout.h -- the ring's geometry, the control block and ONE list of the arrays of a chunk's work area, from which the
+// device's carve (lds_carve, chain_lds.h; mcmc_kernels.hip alone) and the host's sizes below both follow (mcmc_kernels.hip for
+// its launches, session_plan.h for the launch classes).  Plain C++ (tests/test_chain_layout.py compiles it without HIP); wants
+// JTK_MAX_COPY (batch_types.h).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -102,11 +103,11 @@ static size_t mcmc_lds_fixed() {
     const uint32_t seg_log = JTK_SEG_LOG_LIGHT;
     return 0 JTK_CHAIN_FIXED_ARRAYS(JTK_CHAIN_ADD_BYTES);
 }
-size_t mcmc_ws_bytes(uint32_t n, uint32_t d, uint32_t k) {
+inline size_t mcmc_ws_bytes(uint32_t n, uint32_t d, uint32_t k) {
     k = clamp_k(k);
     return ((mcmc_lds_core(n, d, k) - mcmc_lds_fixed()) + 255) & ~(size_t)255;
 }
 // (the session sorts chunks into launch classes by this number, which assumes the light kernel's 24 KiB ring; the general kernel
 // is launched with 12 KiB less (launch_mcmc), so the classing is conservative by that much and jtk_lc_timing_t.chain_lds_bytes
 // reports an upper bound -- ADVICE round 5; left as it is: tests pin the class boundaries at these sizes)
-size_t mcmc_lds_bytes(uint32_t lds_n, uint32_t lds_d, uint32_t lds_k) { return mcmc_lds_core(lds_n, lds_d, clamp_k(lds_k)); }
+inline size_t mcmc_lds_bytes(uint32_t lds_n, uint32_t lds_d, uint32_t lds_k) { return mcmc_lds_core(lds_n, lds_d, clamp_k(lds_k)); }

@@ -2,6 +2,7 @@
 #include <cstring>
 
 #include "session_internal.h"
+#include "session_plan.h"
 
 int jtk_lc_cluster_features(const jtk_lc_params_t *params, size_t n_chunks, const jtk_lc_feature_chunk_t *chunks,
                             const double *variants, const uint32_t *variant_type, uint32_t *label, double *log_post,
@@ -22,7 +23,7 @@ int jtk_lc_cluster_features(const jtk_lc_params_t *params, size_t n_chunks, cons
     std::vector<ChunkState> sts(n_chunks);
     std::vector<uint64_t> vt_off(n_chunks), lg_off(n_chunks);
     uint64_t n_reads = 0, n_var = 0, n_vt = 0, lgo = 0;
-    uint32_t max_n = 1, max_d = 1, max_k = 2;
+    uint32_t max_k = 2;
     if ((rc = check_contiguous(chunks, n_chunks, &n_reads))) return rc;
     for (size_t c = 0; c < n_chunks; c++) {
         const jtk_lc_feature_chunk_t &fc = chunks[c];
@@ -46,29 +47,11 @@ int jtk_lc_cluster_features(const jtk_lc_params_t *params, size_t n_chunks, cons
         if (fc.var_off + (uint64_t)fc.n_reads * fc.dim > n_var) n_var = fc.var_off + (uint64_t)fc.n_reads * fc.dim;
         if (fc.vt_off + fc.dim > n_vt) n_vt = fc.vt_off + fc.dim;
     }
-    // chunks whose work area fits a CU's LDS run in the table-driven kernels (one launch sized for their maxima); the others --
-    // more than JTK_MAX_PILEUP reads, or too large a feature matrix -- in mcmc_kernel_huge with a global-memory work area
-    std::vector<uint32_t> in_lds, in_ws;
-    for (size_t c = 0; c < n_chunks; c++) {
-        if (sts[c].status != 0) continue;
-        const jtk_lc_feature_chunk_t &fc = chunks[c];
-        const uint32_t d = std::max<uint32_t>(1, fc.dim), k = std::max<uint32_t>(2, fc.copy_num);
-        (fc.n_reads > JTK_MAX_PILEUP || mcmc_lds_bytes(std::max<uint32_t>(1, fc.n_reads), d, k) > 160 * 1024 ? in_ws : in_lds).push_back((uint32_t)c);
-    }
-    for (;;) {
-        max_n = max_d = 1;
-        for (uint32_t c : in_lds) {
-            max_n = std::max(max_n, chunks[c].n_reads);
-            max_d = std::max(max_d, chunks[c].dim);
-        }
-        if (in_lds.empty() || mcmc_lds_bytes(max_n, max_d, max_k) <= 160 * 1024) break;
-        auto worst = std::max_element(in_lds.begin(), in_lds.end(), [&](uint32_t a, uint32_t b) {
-            return (uint64_t)chunks[a].n_reads * std::max<uint32_t>(1, chunks[a].dim) < (uint64_t)chunks[b].n_reads * std::max<uint32_t>(1, chunks[b].dim);
-        });
-        in_ws.push_back(*worst);  // the maxima of the launch combine beyond a CU's LDS: its largest member leaves
-        in_lds.erase(worst);
-    }
-    std::sort(in_ws.begin(), in_ws.end());
+    // the two launches: the table-driven kernels on what fits a CU's LDS, mcmc_kernel_huge on the rest (session_plan.h)
+    std::vector<uint8_t> failed(n_chunks);
+    for (size_t c = 0; c < n_chunks; c++) failed[c] = sts[c].status != 0;
+    FeatureChainPlan fp;
+    plan_feature_chain(n_chunks, chunks, failed, max_k, JTK_CU_LDS_BYTES, fp);
     std::vector<jtk_lc_params_t> pv(1, *params);
     std::vector<double> varv(variants, variants + n_var);
     std::vector<uint32_t> vtv(variant_type, variant_type + 2 * n_vt);
@@ -83,37 +66,23 @@ int jtk_lc_cluster_features(const jtk_lc_params_t *params, size_t n_chunks, cons
     if ((rc = dev_alloc<double>(d_post, n_reads * post_stride))) return rc;
     if ((rc = dev_alloc<double>(d_lg, lgo))) return rc;
     DevPtr d_split, d_order, d_ws, d_wsoff;  // light / general chunk lists of the chain launch; the two launches' chunk lists
-    std::vector<uint32_t> order(in_lds);
-    order.insert(order.end(), in_ws.begin(), in_ws.end());
-    for (size_t c = 0; c < n_chunks; c++)  // (chunks that failed validation: listed too, they return at once)
-        if (sts[c].status != 0) order.insert(order.begin() + (ptrdiff_t)in_lds.size(), (uint32_t)c);
-    const uint32_t n_lds = (uint32_t)(order.size() - in_ws.size());
-    if ((rc = dev_upload(s, d_order, order))) return rc;
-    std::vector<uint64_t> ws_off;
-    uint64_t ws = 0;
-    uint32_t hn = 1, hd = 1;
-    for (uint32_t c : in_ws) {
-        ws_off.push_back(ws);
-        ws += mcmc_ws_bytes(std::max<uint32_t>(1, chunks[c].n_reads), std::max<uint32_t>(1, chunks[c].dim), std::max<uint32_t>(2, chunks[c].copy_num));
-        hn = std::max(hn, chunks[c].n_reads);
-        hd = std::max(hd, chunks[c].dim);
-    }
-    if (!in_ws.empty()) {
-        if ((rc = dev_alloc<uint8_t>(d_ws, ws))) return rc;
-        if ((rc = dev_upload(s, d_wsoff, ws_off))) return rc;
+    if ((rc = dev_upload(s, d_order, fp.order))) return rc;
+    if (fp.n_ws) {
+        if ((rc = dev_alloc<uint8_t>(d_ws, fp.ws_bytes))) return rc;
+        if ((rc = dev_upload(s, d_wsoff, fp.ws_off))) return rc;
     }
     tstart(s, JTK_K_MCMC);  // (the session owns the events: no return below leaks one)
     if ((rc = dev_alloc<uint32_t>(d_split, 2 * n_chunks + 8))) return rc;
-    if (n_lds && launch_mcmc(s->stream, n_lds, d_chunks.as<ChunkMeta>(), d_state.as<ChunkState>(),
+    if (fp.n_lds && launch_mcmc(s->stream, fp.n_lds, d_chunks.as<ChunkMeta>(), d_state.as<ChunkState>(),
                     d_params.as<jtk_lc_params_t>(), d_var.as<double>(), d_vt.as<uint32_t>(), d_vtoff.as<uint64_t>(), 1,
                     d_label.as<uint32_t>(), d_post.as<double>(), post_stride, d_lg.as<double>(), d_lgoff.as<uint64_t>(),
-                    max_n, max_d, max_k, nullptr, d_order.as<uint32_t>(), d_split.as<uint32_t>(), nullptr, nullptr, nullptr) != 0)
+                    fp.lds.n, fp.lds.d, max_k, nullptr, d_order.as<uint32_t>(), d_split.as<uint32_t>(), nullptr, nullptr, nullptr) != 0)
         return jtk_fail(JTK_ERR_INTERNAL, "the chain kernel could not be launched (jump table upload failed)");
-    if (!in_ws.empty() &&
-        launch_mcmc_huge(s->stream, (uint32_t)in_ws.size(), d_chunks.as<ChunkMeta>(), d_state.as<ChunkState>(),
+    if (fp.n_ws &&
+        launch_mcmc_huge(s->stream, fp.n_ws, d_chunks.as<ChunkMeta>(), d_state.as<ChunkState>(),
                          d_params.as<jtk_lc_params_t>(), d_var.as<double>(), d_vt.as<uint32_t>(), d_vtoff.as<uint64_t>(), 1,
-                         d_label.as<uint32_t>(), d_post.as<double>(), post_stride, d_lg.as<double>(), d_lgoff.as<uint64_t>(), hn, hd,
-                         max_k, nullptr, d_order.as<uint32_t>() + n_lds, d_ws.as<uint8_t>(), d_wsoff.as<uint64_t>()) != 0)
+                         d_label.as<uint32_t>(), d_post.as<double>(), post_stride, d_lg.as<double>(), d_lgoff.as<uint64_t>(), fp.ws.n, fp.ws.d,
+                         max_k, nullptr, d_order.as<uint32_t>() + fp.n_lds, d_ws.as<uint8_t>(), d_wsoff.as<uint64_t>()) != 0)
         return jtk_fail(JTK_ERR_INTERNAL, "the chain kernel could not be launched (jump table upload failed)");
     tstop(s);
     JTK_HIP_TRY(hipMemcpyAsync(sts.data(), d_state.p, sts.size() * sizeof(ChunkState), hipMemcpyDeviceToHost, s->stream));

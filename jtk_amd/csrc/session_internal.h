@@ -1,11 +1,14 @@
 // session_internal.h -- what the host translation units that drive a resident batch share: the session object, its pooled
 // device blocks and the steps of a stage call (session.hip defines them; session_split.hip, session_stages.hip,
-// session_refit.hip and session_features.hip build the other entry points of include/jtk_lc.h on them).
+// session_refit.hip and session_features.hip build the other entry points of include/jtk_lc.h on them; session_trace.hip
+// reads a finished session).  The plain records are batch_types.h's; every offset, launch class and wave count of a batch
+// is worked out by session_plan.h, which has no HIP in it.
 #pragma once
 #include <memory>
 #include <string>
 #include <vector>
 
+#include "batch_types.h"
 #include "device_common.h"
 #include "host_common.h"
 #include "jtk_lc_debug.h"
@@ -49,18 +52,6 @@ struct SplitResult {
     uint32_t k = 0;
     double score = 0.0;
     int status = 0;
-};
-
-// what a sub-problem inherits from its chunk instead of deriving it from its own template / read count
-struct ChunkExtra {
-    uint32_t radius;        // config.band_width (mod.rs:112,142,153)
-    double local_coverage;  // config.local_coverage (mod.rs:108-112)
-    uint64_t rng[4];        // the chunk's generator, as the previous call left it (mod.rs:158)
-    uint32_t take_num;      // HMMPolishConfig take_num (0 = every read votes)
-};
-
-struct ChainClass {
-    uint32_t first = 0, count = 0, lds_n = 0, lds_d = 0, lds_k = 0, lds_bytes = 0;
 };
 
 struct jtk_lc_session {

@@ -3,7 +3,6 @@ carve and the host's sizes both expand.  The sizes the header computes -- mcmc_l
 launch classes by), mcmc_ws_bytes (a chunk's slice of the global workspace) and the fixed head in front of the sized arrays --
 against a restatement, written here, of the hand-written sum the host carried before the list existed."""
 import os
-import re
 import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -15,6 +14,7 @@ KS = (0, 1, 2, 4, 7, 9)
 
 PROGRAM = r'''
 #include <stdio.h>
+#include "batch_types.h"
 #include "chain_layout.h"
 #define PRINT_FIXED(member, type, bytes) printf("F %s\n", #member);
 #define PRINT_SIZED(member, type, bytes) printf("S %s\n", #member);
@@ -47,11 +47,10 @@ def expected(n, d, k):
 
 
 def test_chain_layout_sizes_follow_from_one_list_of_arrays(tmp_path):
-    max_copy = int(re.search(r"^#define JTK_MAX_COPY (\d+)", open(os.path.join(CSRC, "device_common.h")).read(), re.M).group(1))
     src = tmp_path / "layout.cpp"
     src.write_text(PROGRAM)
     exe = tmp_path / "layout"
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-DJTK_MAX_COPY=%d" % max_copy, "-I", CSRC, str(src), "-o", str(exe)])
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-I", CSRC, str(src), "-o", str(exe)])  # JTK_MAX_COPY: batch_types.h
     rows = [line.split() for line in subprocess.check_output([str(exe)]).decode().splitlines()]
     fixed_names = [r[1] for r in rows if r[0] == "F"]
     sized_names = [r[1] for r in rows if r[0] == "S"]
