@@ -516,7 +516,8 @@ JTK_LC_API int jtk_lc_fill_candidates(size_t n_reads, const uint64_t *node_off, 
  * What the reference gets from kiley::bialignment::guided (`global_guided`, `infix_guided`): an alignment that already
  * exists (an edlib alignment of jtk_lc_align_reads*, an earlier pass of this call) is refined under affine gap scores inside
  * a band of `radius` cells around its path.  Call sites: encode/deletion_fill.rs:526,553-554 (infix, radius = band, scores
- * (2, -6, -5, -1)), dense_encoding.rs:757, determine_chunks.rs:538, consensus/mod.rs:560,1231-1233,1259-1261 (global).
+ * (2, -6, -5, -1)), determine_chunks.rs:538, consensus/mod.rs:560,1231-1233,1259-1261 (global); dense_encoding.rs:757 (global)
+ * is jtk_lc_encode_edges below.
  * kiley is not part of the reference tree: the aligner follows THIS build's specification, DESIGN.md section 4 ("Guided
  * alignment"), and parity with kiley's band shape and its choice among equally good alignments is NOT pinned.  In short:
  * the guide is walked from (0, 0) (ops that do not fit are skipped, a short guide goes on diagonally, then by Del, then by
@@ -599,6 +600,73 @@ typedef struct jtk_encode_result {
 JTK_LC_API int jtk_lc_encode_nodes(size_t n_trials, const jtk_encode_trial_t *trials, const uint8_t *read_bases,
                         const uint8_t *cons_bases, const uint8_t *chunk_bases, jtk_encode_result_t *result, uint8_t *ops_out,
                         uint64_t *ops_out_off, uint64_t ops_cap, int device);
+
+/* ---- dense_encoding's trial of an edge or a tip: encode_edge, batched ---------------------------------------------------
+ * `encode_edge` with `tune_position` (dense_encoding.rs:627-759), which `fill_edges_by_new_chunks` (:202-293) calls for every
+ * read and every gap or tip on a polyploid edge, for a batch of trials, as it stands.  Trial t lays the contig
+ * contig_bases[contig_off .. + contig_len) -- merge_chunks' concatenation of the edge's new chunks (:595-609), whose chunk k
+ * ends at break_points[break_first + k] -- onto the window read_bases[read_off + start .. read_off + end) of a raw read
+ * (reverse-complemented when is_forward == 0, upper-cased) and cuts the alignment at the break points into one node per chunk:
+ *   1. the infix alignment of the contig into the window, the window free (jtk_lc_align_reads_mode; :731): [seq_start, seq_end)
+ *      of the oriented window, to which the window is truncated.  In the read's coordinates that is (start + seq_start,
+ *      start + seq_end) forward and (end - seq_end, end - seq_start) reverse (:741-744);
+ *   2. the infix alignment of the truncated window into the contig, the contig free (:746-755): [ctg_start, ctg_end) and the guide;
+ *   3. one global pass of jtk_lc_align_guided's aligner, x = contig[ctg_start .. ctg_end), y = the truncated window, `radius`
+ *      (read_type.band_width(contig_len)), scores (2, -6, -5, -1) (:756-757): `score`;
+ *   4. the cut (:640-692).  The op stream is (ctg_start - the break point below it) Dels, the pass's ops without their leading Ins
+ *      run (head_ins, where ypos starts), (contig_len - ctg_end) Dels.  first_chunk = the first k with ctg_start < break point k
+ *      (n_chunks when there is none); the chunks below it are not reached.  The op that brings xpos to break point k closes chunk
+ *      k; the Ins behind it belong to chunk k + 1, and what follows the last chunk's closing op is dropped.  Per closed chunk:
+ *      ops_len, mat_num = the Matches among them, query_len = the ops that are no Del, query_off = seq_start + ypos - query_len
+ *      (the node's seq inside the ORIENTED window), position_from_start = start + query_off forward, (end - seq_start) - ypos
+ *      reverse (:674-677), and the ops themselves, virtual Dels included;
+ *   5. verdict 0 when 1 - sim_thr < mat_num / ops_len in f64 (:671), else 2; 3 for a chunk that is not reached (all else 0).
+ * Trial t's chunk k is nodes[node_off[t] + k] and its ops ops_out[ops_out_off[node_off[t] + k] .. ops_out_off[node_off[t] + k + 1])
+ * (ops_out_off holds node_off[n_trials] + 1 entries), in chunk order.  The caller takes `seq` from the oriented window, runs
+ * kiley_op_to_ops on the ops, and reverses a reverse trial's accepted nodes (:693-695).
+ * This build's own decisions: both infix alignments and the guided pass follow DESIGN.md section 4 -- parity with edlib's choice
+ * among equal placements and with kiley is NOT pinned.  A truncated window of length 0 (the reference would hand edlib an empty
+ * sequence) or ctg_start == contig_len gives status 0 and every chunk not reached; with the empty window no pass runs and
+ * ctg_start = ctg_end = score = 0.  There is no limit on n_chunks other than memory.
+ * Limits, per trial (status = JTK_ERR_UNSUPPORTED where an infix alignment or the guided pass refuses it: every chunk not
+ * reached, no ops, the rest of the batch is answered and the call returns JTK_ERR_CHUNK_FAILED): 32,000 bases per sequence,
+ * contig_len + window length < 32,768 (the infix alignments run without a distance bound), JTK_GUIDED_MAX_WIDTH cells in a row
+ * of the band.
+ * JTK_ERR_INVALID_ARG, before a device is looked for: start >= end (the reference asserts), n_chunks == 0, an empty contig,
+ * break points that do not ascend strictly from above 0 or do not end at contig_len, node_off that is not the prefix sum of
+ * n_chunks, a base that is not ACGT (the window's after upper-casing), ops_cap below sum(contig_len + end - start) -- which
+ * always holds the batch's ops, and is asked for whatever they come to, so that the answer does not depend on the data. */
+typedef struct jtk_edge_trial {
+    uint64_t read_off;              /* the read's first base in read_bases */
+    uint32_t start, end;            /* the window, in bases of the read */
+    uint32_t is_forward;
+    uint32_t radius;                /* read_type.band_width(contig_len) (:637) */
+    uint64_t contig_off;            /* into contig_bases */
+    uint32_t contig_len;
+    uint32_t n_chunks;
+    uint64_t break_first;           /* into break_points: n_chunks strictly ascending ends, the last == contig_len */
+    double sim_thr;                 /* read_type.sim_thr() (:658) */
+} jtk_edge_trial_t;
+enum jtk_edge_verdict { JTK_EDGE_ACCEPTED = 0, JTK_EDGE_REJECTED = 2, JTK_EDGE_NOT_REACHED = 3 };
+typedef struct jtk_edge_result {
+    int32_t status;
+    int32_t score;                  /* of the guided pass */
+    uint32_t seq_start, seq_end;    /* inside the oriented window, end exclusive */
+    uint32_t ctg_start, ctg_end;    /* end exclusive */
+    uint32_t first_chunk;           /* n_chunks when no chunk is reached */
+    uint32_t head_ins;              /* remove_leading_insertions (:655) */
+} jtk_edge_result_t;
+typedef struct jtk_edge_node {
+    uint32_t verdict;               /* enum jtk_edge_verdict */
+    uint32_t mat_num, ops_len;      /* alignment_identity's two integers (:622-625) */
+    uint32_t query_off, query_len;  /* the node's seq inside the oriented window */
+    uint32_t reserved;
+    uint64_t position_from_start;
+} jtk_edge_node_t;
+JTK_LC_API int jtk_lc_encode_edges(size_t n_trials, const jtk_edge_trial_t *trials, const uint8_t *read_bases,
+                        const uint8_t *contig_bases, const uint32_t *break_points, const uint64_t *node_off,
+                        jtk_edge_result_t *result, jtk_edge_node_t *nodes, uint8_t *ops_out, uint64_t *ops_out_off,
+                        uint64_t ops_cap, int device);
 
 /* ---- consensus polishing that votes with banded edit distances -----------------------------------------------------------
  * What the reference gets from kiley::bialignment::guided::polish_until_converge / polish_until_converge_with:

@@ -55,6 +55,10 @@ JTK_LC_API void jtk_lc_debug_guided_timing(double *out);
 /* Of this thread's last jtk_lc_encode_nodes call, 8 doubles: the trials that passed the lower-bound filter, the HIP-event time
  * in ms of the three guided passes [1..3] and the cells they filled [4..6], and the host clock of the infix alignment in ms. */
 JTK_LC_API void jtk_lc_debug_encode_timing(double *out);
+/* Of this thread's last jtk_lc_encode_edges call, 8 doubles: the trials, the HIP-event time in ms of the guided pass [1], the
+ * cells it filled [2] and its slices [3], the host clock in ms of the two infix alignments [4], [5], and the HIP-event time in ms
+ * of the cut and pack kernels [6]. */
+JTK_LC_API void jtk_lc_debug_edges_timing(double *out);
 
 /* One round's fill of jtk_lc_polish_guided for a single pile-up, nothing applied: dist_out[r] = the banded edit distance of
  * read r along its ops, and table_out[r * table_stride + p * 14 + row] = T[p][row] of DESIGN.md section 4 ("Guided polishing")

@@ -636,6 +636,182 @@ def fill_trials(side, candidates, seq_len, next_node, cons_len_of):
     return out
 
 
+_REVCMP = bytes.maketrans(b"ACGTacgt", b"TGCAtgca")
+
+
+def _as_bytes(s):
+    return bytes(s) if isinstance(s, (bytes, bytearray)) else bytes(np.asarray(s, dtype=np.uint8))
+
+
+def _oriented_window(read_bases, read_off, start, end, is_forward):
+    """the window as tune_position takes it (dense_encoding.rs:722-727)"""
+    w = bytes(np.asarray(read_bases[read_off + start:read_off + end], dtype=np.uint8)).upper()
+    return w if is_forward else w.translate(_REVCMP)[::-1]
+
+
+def encode_edges(trials, read_bases, contig_bases, break_points, device=0, raise_on_trial_failure=True):
+    """jtk_lc_encode_edges: `encode_edge` with `tune_position` (dense_encoding.rs:627-759) for every trial (ffi.EDGE_TRIAL_DT).
+    -> dict(result (ffi.EDGE_RESULT_DT, per trial), nodes (ffi.EDGE_NODE_DT, per slot: trial t's chunk k at node_off[t] + k),
+    node_off, ops, ops_off (per slot), accepted, rc).  accepted[t] is what encode_edge returns for trial t: its accepted nodes as
+    dict(chunk (index in the trial), position_from_start, seq, ops, mat_num, ops_len), reversed for a reverse trial (:693-695);
+    the caller runs kiley_op_to_ops on the ops.  Both infix alignments and the guided pass are this build's own specification
+    (DESIGN.md section 4): parity with edlib's choice among equal placements and with kiley is not pinned."""
+    trials = np.ascontiguousarray(trials, dtype=ffi.EDGE_TRIAL_DT)
+    n = len(trials)
+    rb, cb = (np.ascontiguousarray(np.append(np.asarray(a, dtype=np.uint8), np.uint8(0))) for a in (read_bases, contig_bases))
+    bp = np.ascontiguousarray(np.append(np.asarray(break_points, dtype=np.uint32), np.uint32(0)))
+    node_off = np.zeros(n + 1, dtype=np.uint64)
+    node_off[1:] = np.cumsum(trials["n_chunks"].astype(np.uint64))
+    n_nodes = int(node_off[n])
+    cap = int(trials["contig_len"].astype(np.int64).sum() + (trials["end"].astype(np.int64) - trials["start"].astype(np.int64)).clip(0).sum())
+    result = np.zeros(n + 1, dtype=ffi.EDGE_RESULT_DT)
+    nodes = np.zeros(n_nodes + 1, dtype=ffi.EDGE_NODE_DT)
+    ops, ops_off = np.zeros(cap + 1, dtype=np.uint8), np.zeros(n_nodes + 1, dtype=np.uint64)
+    rc = ffi.lib().jtk_lc_encode_edges(n, trials.ctypes.data, u8p(rb), u8p(cb), u32p(bp), u64p(node_off), result.ctypes.data, nodes.ctypes.data,
+                                       u8p(ops), u64p(ops_off), cap, device)
+    if rc != 0 and (raise_on_trial_failure or rc != -6):
+        check(rc)
+    accepted = []
+    for t in range(n):
+        tr, got = trials[t], []
+        window = None
+        for k in range(int(tr["n_chunks"])):
+            e = int(node_off[t]) + k
+            nd = nodes[e]
+            if int(result[t]["status"]) != 0 or int(nd["verdict"]) != ffi.EDGE_ACCEPTED:
+                continue
+            if window is None:
+                window = _oriented_window(rb, int(tr["read_off"]), int(tr["start"]), int(tr["end"]), bool(tr["is_forward"]))
+            q = int(nd["query_off"])
+            got.append(dict(chunk=k, position_from_start=int(nd["position_from_start"]), seq=window[q:q + int(nd["query_len"])],
+                            ops=ops[int(ops_off[e]):int(ops_off[e + 1])].copy(), mat_num=int(nd["mat_num"]), ops_len=int(nd["ops_len"])))
+        accepted.append(got if tr["is_forward"] else got[::-1])
+    return dict(result=result[:n], nodes=nodes[:n_nodes], node_off=node_off, ops=ops[:int(ops_off[n_nodes])], ops_off=ops_off, accepted=accepted, rc=rc)
+
+
+def edges_timing():
+    """jtk_lc_debug_edges_timing: of the last encode_edges call, the trials, kernel ms, cells and slices of the guided pass, host ms
+    of the two infix alignments, kernel ms of the cut and the pack"""
+    out = (C.c_double * 8)()
+    ffi.lib().jtk_lc_debug_edges_timing(out)
+    return dict(n_trials=int(out[0]), pass_ms=out[1], pass_cells=int(out[2]), slices=int(out[3]), infix_host_ms=[out[4], out[5]], cut_ms=out[6])
+
+
+def pack_edge_trials(items):
+    """items: dict(read, start, end, is_forward, chunks (the edge's chunk sequences, in order), radius, sim_thr) each; sequences
+    are bytes or uint8 arrays.  Every item gets buffers of its own.  -> (trials (ffi.EDGE_TRIAL_DT), read_bases, contig_bases,
+    break_points): the arguments of encode_edges; the contig and its break points are merge_chunks' (dense_encoding.rs:595-609)."""
+    reads = _flat([it["read"] for it in items])
+    contigs = _flat([b"".join(_as_bytes(c) for c in it["chunks"])
+                     for it in items])
+    arr = np.zeros(len(items), dtype=ffi.EDGE_TRIAL_DT)
+    breaks = []
+    for k, it in enumerate(items):
+        ends = np.cumsum([len(c) for c in it["chunks"]], dtype=np.int64)
+        arr[k] = (reads[1][k], it["start"], it["end"], int(bool(it["is_forward"])), it["radius"], contigs[1][k], int(ends[-1]) if len(ends) else 0,
+                  len(ends), len(breaks), it["sim_thr"])
+        breaks.extend(int(e) for e in ends)
+    return arr, reads[0], contigs[0], np.asarray(breaks, dtype=np.uint32)
+
+
+EDGE_MARGIN = 25     # dense_encoding.rs:209
+
+
+def edge_trials(nodes, seq_len, edges, tips, band_width_of, sim_thr):
+    """`fill_edges_by_new_chunks` (dense_encoding.rs:202-293) up to its calls of encode_edge; pure host arithmetic, no GPU.
+    nodes: the read's nodes in order, (chunk, cluster, is_forward, position_from_start, seq length) each; seq_len: the raw read's
+    length; edges: {((chunk, cluster, is_forward), (chunk, cluster, is_forward)): [chunk sequence, ...]}; tips: {(chunk, cluster,
+    is_forward, is_tail): [[chunk sequence, ...], ...]}, both keyed as the reference's EdgeAndUnit and TipAndUnit;
+    band_width_of(contig_len) -> the radius (read_type.band_width); sim_thr: read_type.sim_thr().
+    Covered: the head tip with both keys (the second one, which the reference marks "Here is a bug", as it stands), every
+    windows(2) gap with MARGIN = 25, the forward key before the reverse key, and the `end <= start` skip, the tail tip with both
+    keys.  -> list of dict(insert_at, start, end, is_forward, chunks, radius, sim_thr) in the reference's order (pack_edge_trials
+    takes them once `read` is added); insert_at is the index the trial's nodes get in `inserts`: 0, idx + 1, len + 1."""
+    out = []
+
+    def trial(insert_at, start, end, direction, chunks):
+        contig_len = sum(len(c) for c in chunks)
+        out.append(dict(insert_at=insert_at, start=start, end=end, is_forward=direction, chunks=chunks, radius=int(band_width_of(contig_len)),
+                        sim_thr=sim_thr))
+
+    if len(nodes):
+        chunk, cluster, forward, position, _ = nodes[0]
+        start, end = 0, min(position + EDGE_MARGIN, seq_len)
+        for chunks in tips.get((chunk, cluster, bool(forward), False), ()):
+            trial(0, start, end, True, chunks)
+        for chunks in tips.get((chunk, cluster, not forward, True), ()):
+            trial(0, start, end, False, chunks)
+    for idx in range(len(nodes) - 1):
+        a, b = nodes[idx], nodes[idx + 1]
+        start = min(max(a[3] + a[4], EDGE_MARGIN) - EDGE_MARGIN, seq_len)
+        end = min(b[3] + EDGE_MARGIN, seq_len)
+        forward_key = ((a[0], a[1], bool(a[2])), (b[0], b[1], bool(b[2])))
+        reverse_key = ((b[0], b[1], not b[2]), (a[0], a[1], not a[2]))
+        if forward_key in edges:
+            chunks, direction = edges[forward_key], True
+        elif reverse_key in edges:
+            chunks, direction = edges[reverse_key], False
+        else:
+            continue
+        if end <= start:     # "TooNear"
+            continue
+        trial(idx + 1, start, end, direction, chunks)
+    if len(nodes):
+        chunk, cluster, forward, position, length = nodes[-1]
+        start = max(min(position + length, seq_len) - EDGE_MARGIN, 0)
+        end = min(seq_len + EDGE_MARGIN, seq_len)
+        for chunks in tips.get((chunk, cluster, bool(forward), True), ()):
+            trial(len(nodes) + 1, start, end, True, chunks)
+        for chunks in tips.get((chunk, cluster, not forward, False), ()):
+            trial(len(nodes) + 1, start, end, False, chunks)
+    return out
+
+
+CONS_MIN_LENGTH, CONS_MAX_LENGTH = 400, 10_000     # dense_encoding.rs:7-8
+
+
+def edge_consensus_plan(seqs, cov_thr):
+    """the host part of `consensus` (dense_encoding.rs:548-561, :572-573) -> None or (the kept sequences, the draft first, and the
+    band).  Own decision where select_nth_unstable leaves the order open: the sequences keep their input order, the median is the
+    element at index len / 2 of the ascending lengths, and the draft is the first sequence in input order of that length."""
+    seqs = [_as_bytes(s) for s in seqs]
+    median = sorted(len(s) for s in seqs)[len(seqs) // 2]
+    upper, lower = 2 * median, max(median, CONS_MIN_LENGTH) // 2
+    if upper <= lower or CONS_MAX_LENGTH < median:
+        return None
+    idx = next(k for k, s in enumerate(seqs) if len(s) == median)
+    seqs[0], seqs[idx] = seqs[idx], seqs[0]
+    seqs = [s for s in seqs if lower <= len(s) < upper]
+    if len(seqs) <= cov_thr:
+        return None
+    mean_len = sum(len(s) for s in seqs) // len(seqs)
+    return seqs, min(max(mean_len // 20, 10), 50)
+
+
+def edge_consensus(seqs, cov_thr, device=0):
+    """`consensus` (dense_encoding.rs:548-579): the edge's sequences of median-like length, aligned to the draft with align_reads
+    (global), then two polish_guided calls that share the ops.  -> the consensus (uint8 array), or None where the reference
+    returns None: 2 median <= max(median, 400) / 2, a median above 10,000, at most cov_thr sequences inside the length window
+    [max(median, 400) / 2, 2 median), a result that is not longer than 400.  The polish is this build's own specification."""
+    from .batch import pack
+    plan = edge_consensus_plan(seqs, cov_thr)
+    if plan is None:
+        return None
+    seqs, band = plan
+    reads = [np.frombuffer(s, dtype=np.uint8) for s in seqs]
+    none = np.zeros(0, dtype=np.uint8)
+    batch = pack([(0, 1, reads[0], reads, [none] * len(reads), [1] * len(reads), None)])
+    aligned = align_reads(batch, device=device)
+    ops, ops_off = aligned["ops"], aligned["ops_off"]
+    cons = reads[0]
+    for _ in range(2):      # :574-577
+        batch = pack([(0, 1, cons, reads, [ops[int(ops_off[r]):int(ops_off[r + 1])] for r in range(len(reads))], [1] * len(reads), None)])
+        out = polish_guided(batch, band, device=device)
+        cons = out["cons"][int(out["cons_off"][0]):int(out["cons_off"][1])].copy()
+        ops, ops_off = out["ops_out"], out["ops_out_off"]
+    return cons if CONS_MIN_LENGTH < len(cons) else None
+
+
 def correct_clustering_with_sims(*args, **kw):
     """correct_clustering with the diagnostic switch of include/jtk_lc_debug.h on: returns (cluster, touched, sims), sims = the
     raw similarity matrix (before filter_similarity) of every corrected chunk, in selected_chunks order.  A test hook: the

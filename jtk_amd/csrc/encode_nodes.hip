@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "device_common.h"
+#include "encode_window.h"
 #include "guided_internal.h"
 #include "jtk_lc_debug.h"
 #include "wave_util.h"
@@ -26,10 +27,6 @@ constexpr uint32_t EN_EDGE_LEN = 100;   // deletion_fill.rs:9
 constexpr double EN_EDGE_BOUND = 0.5;   // :7
 constexpr int EN_MATCH = 2, EN_MISMATCH = -6, EN_OPEN = -5, EN_EXT = -1;  // ALN_PARAMETER (haplotyper/src/lib.rs)
 
-struct EnWindow {
-    uint64_t off;   // into the raw slices and into the windows alike
-    uint32_t len, is_forward;
-};
 struct EnFit {
     uint32_t trim_head, trim_tail, mat_num, ops_len, head_match, head_len, tail_match, tail_len;
 };
@@ -37,22 +34,6 @@ struct EnTrial {   // what encode_fit_kernel needs besides the second pass's res
     uint64_t win_off, chunk_off;
     uint32_t win_len, cons_len, chunk_len, band;
 };
-
-// one workgroup per window; flags |= 1 where a base is not ACGT after upper-casing
-__global__ void __launch_bounds__(256) encode_window_kernel(uint32_t n, const EnWindow *wins, const uint8_t *raw, uint8_t *out, uint32_t *flags) {
-    const uint32_t t = blockIdx.x;
-    if (t >= n) return;
-    const EnWindow w = wins[t];
-    bool bad = false;
-    for (uint32_t q = threadIdx.x; q < w.len; q += blockDim.x) {
-        uint8_t c = raw[w.off + (w.is_forward ? q : w.len - 1 - q)];
-        if (c >= 'a' && c <= 'z') c -= 32;
-        if (!w.is_forward) c = c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : c;
-        bad |= c != 'A' && c != 'C' && c != 'G' && c != 'T';
-        out[w.off + q] = c;
-    }
-    if (bad) atomicOr(flags, 1u);
-}
 
 // the second pass: the same sequences, guided by the first pass's ops
 __global__ void __launch_bounds__(256) encode_next_kernel(uint32_t n, const jtk_guided_pair_t *in, const uint64_t *slot_end, const uint32_t *nops,

@@ -96,13 +96,21 @@ ENCODE_TRIAL_DT = np.dtype([("read_off", "<u8"), ("start", "<u4"), ("end", "<u4"
 ENCODE_RESULT_DT = np.dtype([("status", "<i4"), ("verdict", "<u4"), ("trim_head", "<u4"), ("trim_tail", "<u4"), ("position_from_start", "<u8"),
                              ("query_len", "<u4"), ("band", "<u4"), ("score", "<i4"), ("mat_num", "<u4"), ("ops_len", "<u4"), ("head_match", "<u4"),
                              ("head_len", "<u4"), ("tail_match", "<u4"), ("tail_len", "<u4"), ("reserved", "<u4")])
+# jtk_edge_trial_t / jtk_edge_result_t / jtk_edge_node_t (jtk_lc_encode_edges)
+EDGE_TRIAL_DT = np.dtype([("read_off", "<u8"), ("start", "<u4"), ("end", "<u4"), ("is_forward", "<u4"), ("radius", "<u4"), ("contig_off", "<u8"),
+                          ("contig_len", "<u4"), ("n_chunks", "<u4"), ("break_first", "<u8"), ("sim_thr", "<f8")])
+EDGE_RESULT_DT = np.dtype([("status", "<i4"), ("score", "<i4"), ("seq_start", "<u4"), ("seq_end", "<u4"), ("ctg_start", "<u4"), ("ctg_end", "<u4"),
+                           ("first_chunk", "<u4"), ("head_ins", "<u4")])
+EDGE_NODE_DT = np.dtype([("verdict", "<u4"), ("mat_num", "<u4"), ("ops_len", "<u4"), ("query_off", "<u4"), ("query_len", "<u4"), ("reserved", "<u4"),
+                         ("position_from_start", "<u8")])
+EDGE_ACCEPTED, EDGE_REJECTED, EDGE_NOT_REACHED = 0, 2, 3   # enum jtk_edge_verdict
 GUIDED_MAX_WIDTH = 4096    # JTK_GUIDED_MAX_WIDTH
 ENCODE_ACCEPTED, ENCODE_LOWER_BOUND, ENCODE_REJECTED = 0, 1, 2   # enum jtk_encode_verdict
 
 # every symbol declared in include/jtk_lc.h (tests check the library exports them)
 EXPORTED_SYMBOLS = (
     "jtk_lc_cluster_chunks", "jtk_lc_cluster_chunks_multi", "jtk_lc_cluster_polished", "jtk_lc_polish_chunks", "jtk_lc_align_reads", "jtk_lc_align_reads_mode", "jtk_lc_modification_table",
-    "jtk_lc_cluster_features", "jtk_lc_estimate_gains", "jtk_lc_estimate_minimum_gain", "jtk_lc_fit_model", "jtk_lc_correct_clustering", "jtk_lc_squish_clusters", "jtk_lc_squish_classify", "jtk_lc_node_errors", "jtk_lc_error_quantile", "jtk_lc_estimate_error_rate", "jtk_lc_purge_diverged", "jtk_lc_fill_candidates", "jtk_lc_align_guided", "jtk_lc_polish_guided", "jtk_lc_encode_nodes", "jtk_lc_trim_cache", "jtk_lc_pileup_sort_key", "jtk_lc_normalize_pileup", "jtk_lc_strerror",
+    "jtk_lc_cluster_features", "jtk_lc_estimate_gains", "jtk_lc_estimate_minimum_gain", "jtk_lc_fit_model", "jtk_lc_correct_clustering", "jtk_lc_squish_clusters", "jtk_lc_squish_classify", "jtk_lc_node_errors", "jtk_lc_error_quantile", "jtk_lc_estimate_error_rate", "jtk_lc_purge_diverged", "jtk_lc_fill_candidates", "jtk_lc_align_guided", "jtk_lc_polish_guided", "jtk_lc_encode_nodes", "jtk_lc_encode_edges", "jtk_lc_trim_cache", "jtk_lc_pileup_sort_key", "jtk_lc_normalize_pileup", "jtk_lc_strerror",
     "jtk_lc_last_error", "jtk_lc_version", "jtk_lc_device_ok", "jtk_lc_last_timing",
     "jtk_lc_session_create", "jtk_lc_session_run", "jtk_lc_session_fetch", "jtk_lc_session_destroy", "jtk_lc_session_trace",
 )
@@ -112,7 +120,7 @@ DEBUG_SYMBOLS = (
     "jtk_lc_debug_chain_profile", "jtk_lc_debug_purge_timing", "jtk_lc_debug_fill_pairs", "jtk_lc_debug_fill_timing",
     "jtk_lc_debug_gains_keep", "jtk_lc_debug_gains_batches", "jtk_lc_debug_gains_batch_sizes", "jtk_lc_debug_gains_batch",
     "jtk_lc_debug_guided_scratch_cap", "jtk_lc_debug_guided_timing", "jtk_lc_debug_encode_timing",
-    "jtk_lc_debug_guided_table", "jtk_lc_debug_gpolish_timing",
+    "jtk_lc_debug_guided_table", "jtk_lc_debug_gpolish_timing", "jtk_lc_debug_edges_timing",
 )
 DEBUG_GAINS_OPS_STRIDE = 512   # JTK_LC_DEBUG_GAINS_OPS_STRIDE
 SYNTH_SYMBOLS = ("jtk_synth_pileup",)
@@ -186,6 +194,8 @@ def lib():
     sig("jtk_lc_debug_fill_timing", None, PD)
     sig("jtk_lc_align_guided", i32, sz, vp, PU8, PU8, PU8, i32, i32, i32, i32, i32, PU8, PU64, u64, PI32, PU32, PU32, PI32, i32)
     sig("jtk_lc_encode_nodes", i32, sz, vp, PU8, PU8, PU8, vp, PU8, PU64, u64, i32)
+    sig("jtk_lc_encode_edges", i32, sz, vp, PU8, PU8, PU32, PU64, vp, vp, PU8, PU64, u64, i32)
+    sig("jtk_lc_debug_edges_timing", None, PD)
     sig("jtk_lc_debug_guided_scratch_cap", None, u64)
     sig("jtk_lc_debug_guided_timing", None, PD)
     sig("jtk_lc_debug_encode_timing", None, PD)

@@ -76,6 +76,22 @@ pub struct JtkEncodeResult {
     pub query_len: u32, pub band: u32, pub score: i32, pub mat_num: u32, pub ops_len: u32, pub head_match: u32,
     pub head_len: u32, pub tail_match: u32, pub tail_len: u32, pub reserved: u32,
 }
+// one call of encode_edge (dense_encoding.rs:627-697), what tune_position found for it, and one record per chunk of its contig
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct JtkEdgeTrial {
+    pub read_off: u64, pub start: u32, pub end: u32, pub is_forward: u32, pub radius: u32, pub contig_off: u64,
+    pub contig_len: u32, pub n_chunks: u32, pub break_first: u64, pub sim_thr: f64,
+}
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct JtkEdgeResult {
+    pub status: i32, pub score: i32, pub seq_start: u32, pub seq_end: u32, pub ctg_start: u32, pub ctg_end: u32,
+    pub first_chunk: u32, pub head_ins: u32,
+}
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct JtkEdgeNode {
+    pub verdict: u32, pub mat_num: u32, pub ops_len: u32, pub query_off: u32, pub query_len: u32, pub reserved: u32,
+    pub position_from_start: u64,
+}
 
 extern "C" {
     pub fn jtk_lc_cluster_chunks(
@@ -188,6 +204,12 @@ extern "C" {
     pub fn jtk_lc_encode_nodes(
         n_trials: usize, trials: *const JtkEncodeTrial, read_bases: *const u8, cons_bases: *const u8, chunk_bases: *const u8,
         result: *mut JtkEncodeResult, ops_out: *mut u8, ops_out_off: *mut u64, ops_cap: u64, device: c_int) -> c_int;
+    // encode_edge with tune_position (dense_encoding.rs:627-759) for a batch of trials: one node record per chunk of the trial's
+    // contig, in chunk order; verdict 0 accepted, 2 rejected (:671), 3 not reached
+    pub fn jtk_lc_encode_edges(
+        n_trials: usize, trials: *const JtkEdgeTrial, read_bases: *const u8, contig_bases: *const u8, break_points: *const u32,
+        node_off: *const u64, result: *mut JtkEdgeResult, nodes: *mut JtkEdgeNode, ops_out: *mut u8, ops_out_off: *mut u64,
+        ops_cap: u64, device: c_int) -> c_int;
     // the resident-batch form (jtk_lc.h: session_create + run + fetch == jtk_lc_cluster_chunks) and, on it, the reference's
     // trace! rows of one chunk (TOTAL / CAND / PICK / DUMP / RANGE / LK / COUNTS; pseudo_mcmc.rs:122-127,236,250-262,467-472,539)
     pub fn jtk_lc_session_create(

@@ -310,6 +310,98 @@ pub(crate) fn encode_nodes_gpu(trials: &[(&[u8], (usize, usize, bool), (&definit
     }).collect()
 }
 
+/// The windows `fill_edges_by_new_chunks` (dense_encoding.rs:202-293) hands to encode_edge, with its arithmetic as it stands:
+/// the head tip with both keys (the second one is the one the reference marks "Here is a bug"), every windows(2) gap with
+/// MARGIN = 25, the forward key before the reverse key and the `end <= start` skip, the tail tip with both keys.
+/// -> (insert index, start, end, is_forward, the edge's chunks) in the reference's order.
+pub(crate) fn edge_trials<'a>(read: &definitions::EncodedRead, seq_len: usize, edges: &'a HashMap<DEdge, Vec<definitions::Chunk>>,
+                              tips: &'a HashMap<(u64, u64, bool, bool), Vec<Vec<definitions::Chunk>>>)
+    -> Vec<(usize, usize, usize, bool, &'a [definitions::Chunk])> {
+    const MARGIN: usize = 25;
+    let mut out = vec![];
+    if let Some(head) = read.nodes.first() {
+        let (start, end) = (0, (head.position_from_start + MARGIN).min(seq_len));
+        for (key, direction) in [((head.chunk, head.cluster, head.is_forward, false), true), ((head.chunk, head.cluster, !head.is_forward, true), false)] {
+            for chunks in tips.get(&key).into_iter().flatten() { out.push((0, start, end, direction, chunks.as_slice())); }
+        }
+    }
+    for (idx, w) in read.nodes.windows(2).enumerate() {
+        let start = ((w[0].position_from_start + w[0].seq().len()).max(MARGIN) - MARGIN).min(seq_len);
+        let end = (w[1].position_from_start + MARGIN).min(seq_len);
+        let forward = ((w[0].chunk, w[0].cluster, w[0].is_forward), (w[1].chunk, w[1].cluster, w[1].is_forward));
+        let reverse = ((w[1].chunk, w[1].cluster, !w[1].is_forward), (w[0].chunk, w[0].cluster, !w[0].is_forward));
+        let (chunks, direction) = match (edges.get(&forward), edges.get(&reverse)) {
+            (Some(c), _) => (c, true),
+            (None, Some(c)) => (c, false),
+            _ => continue,
+        };
+        if end <= start { continue; }                                                                       // "TooNear", :249-261
+        out.push((idx + 1, start, end, direction, chunks.as_slice()));
+    }
+    if let Some(tail) = read.nodes.last() {
+        let idx = read.nodes.len();
+        let start = (tail.position_from_start + tail.seq().len()).min(seq_len).saturating_sub(MARGIN);
+        let end = (seq_len + MARGIN).min(seq_len);
+        for (key, direction) in [((tail.chunk, tail.cluster, tail.is_forward, true), true), ((tail.chunk, tail.cluster, !tail.is_forward, false), false)] {
+            for chunks in tips.get(&key).into_iter().flatten() { out.push((idx + 1, start, end, direction, chunks.as_slice())); }
+        }
+    }
+    out
+}
+type DEdge = ((u64, u64, bool), (u64, u64, bool));
+
+/// `encode_edge` (dense_encoding.rs:627-697) for all the trials of a batch of reads at once, in place of the calls inside
+/// fill_edges_by_new_chunks: trial t lays the contig of its chunks (merge_chunks, :595-609) onto seq[start..end] of its raw
+/// read.  Returns per trial what encode_edge returns: the accepted nodes, reversed for a reverse trial (:693-695).  Both infix
+/// alignments and the guided pass are the library's own specification (parity with edlib's choice among equal placements and
+/// with kiley is not pinned).
+pub(crate) fn encode_edges_gpu(trials: &[(&[u8], (usize, usize, bool), &[definitions::Chunk])], read_type: &definitions::ReadType)
+    -> Vec<Vec<definitions::Node>> {
+    let (mut reads, mut contigs, mut breaks, mut node_off, mut ts) = (vec![], vec![], vec![], vec![0u64], vec![]);
+    let mut read_at = HashMap::new();
+    for &(seq, (start, end, is_forward), chunks) in trials.iter() {
+        let read_off = *read_at.entry((seq.as_ptr(), seq.len())).or_insert_with(|| {
+            reads.extend_from_slice(seq);
+            (reads.len() - seq.len()) as u64
+        });
+        let (contig_off, break_first) = (contigs.len() as u64, breaks.len() as u64);
+        let mut at = 0u32;
+        for c in chunks.iter() {
+            contigs.extend_from_slice(c.seq());
+            at += c.seq().len() as u32;
+            breaks.push(at);
+        }
+        node_off.push(node_off.last().unwrap() + chunks.len() as u64);
+        ts.push(JtkEdgeTrial { read_off, start: start as u32, end: end as u32, is_forward: is_forward as u32,
+            radius: read_type.band_width(at as usize) as u32, contig_off, contig_len: at, n_chunks: chunks.len() as u32, break_first,
+            sim_thr: read_type.sim_thr() });
+    }
+    let cap: usize = ts.iter().map(|t| (t.contig_len + t.end - t.start) as usize).sum();
+    let n_nodes = *node_off.last().unwrap() as usize;
+    let (mut result, mut nodes) = (vec![JtkEdgeResult::default(); ts.len()], vec![JtkEdgeNode::default(); n_nodes + 1]);
+    let (mut ops, mut ops_off) = (vec![0u8; cap + 1], vec![0u64; n_nodes + 1]);
+    let rc = unsafe { jtk_lc_encode_edges(ts.len(), ts.as_ptr(), reads.as_ptr(), contigs.as_ptr(), breaks.as_ptr(), node_off.as_ptr(),
+        result.as_mut_ptr(), nodes.as_mut_ptr(), ops.as_mut_ptr(), ops_off.as_mut_ptr(), cap as u64, /*device*/ 0) };
+    assert!(rc == 0 || rc == -6, "{}", unsafe { std::ffi::CStr::from_ptr(jtk_lc_last_error()) }.to_string_lossy());
+    let kop = [kiley::Op::Match, kiley::Op::Mismatch, kiley::Op::Ins, kiley::Op::Del];
+    trials.iter().enumerate().map(|(t, &(seq, (start, end, is_forward), chunks))| {
+        if result[t].status != 0 { return vec![]; }
+        let mut window = if is_forward { seq[start..end].to_vec() } else { bio_utils::revcmp(&seq[start..end]) };   // :722-727
+        window.iter_mut().for_each(u8::make_ascii_uppercase);
+        let mut out: Vec<_> = chunks.iter().enumerate().filter_map(|(k, chunk)| {
+            let e = node_off[t] as usize + k;
+            let nd = &nodes[e];
+            if nd.verdict != 0 { return None; }
+            let kops: Vec<_> = ops[ops_off[e] as usize..ops_off[e + 1] as usize].iter().map(|&o| kop[o as usize]).collect();
+            let query = window[nd.query_off as usize..(nd.query_off + nd.query_len) as usize].to_vec();
+            Some(definitions::Node::new(chunk.id, is_forward, query, crate::misc::kiley_op_to_ops(&kops).0,
+                                        nd.position_from_start as usize, chunk.cluster_num))                       // :672-682
+        }).collect();
+        if !is_forward { out.reverse(); }
+        out
+    }).collect()
+}
+
 fn to_ffi(h: &kiley::hmm::PairHiddenMarkovModel) -> JtkHmm {
     let d = crate::model_tune::kiley_into_def(h);                  // model_tune.rs:65-92
     JtkHmm { mat_mat: d.mat_mat, mat_ins: d.mat_ins, mat_del: d.mat_del, ins_mat: d.ins_mat, ins_ins: d.ins_ins,
