@@ -722,7 +722,11 @@ JTK_LC_API int jtk_lc_device_ok(int device);
 
 /* Timing of the last jtk_lc_cluster_* call on this thread, measured with HIP events on the library's
  * own stream: total device milliseconds and the milliseconds + launch count of each kernel family
- * (index = enum jtk_kernel_id).  Used by bench.py for the live roofline number. */
+ * (index = enum jtk_kernel_id).  Used by bench.py for the live roofline number.
+ * The figures come from event pairs on the session's stream.  Sessions that share a lane (more sessions on a device than
+ * its hardware queues pay for streams: INTEGRATION.md section 4) share that stream, and a family's figure then includes
+ * whatever kernels of the lane's other sessions ran in between; kernel_ms[JTK_K_MCMC] is the merged chain launch that
+ * carried the session's chunks, plus the wait for the sessions it was gathered with. */
 enum jtk_kernel_id { JTK_K_PHMM = 0, JTK_K_POLISH = 1, JTK_K_FILTER = 2, JTK_K_MCMC = 3, JTK_K_COUNT = 4 };
 typedef struct jtk_lc_timing {
     double total_ms;

@@ -133,3 +133,27 @@ int launch_mcmc(hipStream_t s, uint32_t n_chunks, const ChunkMeta *chunks, Chunk
                 uint32_t vt_stride_mode, uint32_t *label, double *post, uint32_t post_stride, double *lg,
                 const uint64_t *lg_off, uint32_t lds_n, uint32_t lds_d, uint32_t lds_k, const uint64_t *rng_resume,
                 const uint32_t *order, uint32_t *split, hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join);
+// One chain launch for several sessions (the sessions of a lane, session_lanes.h): a segment is what launch_mcmc takes for one
+// session; the kernels get the segments as a by-value table and a workgroup finds its own by its index.  n_seg = 1 is
+// launch_mcmc.  Every segment has a split scratch and no rng_resume (anything else launches alone, through launch_mcmc).
+#define JTK_MCMC_MAX_SEGMENTS 8
+struct McmcSegment {
+    uint32_t n_chunks;
+    const ChunkMeta *chunks;
+    ChunkState *state;
+    const jtk_lc_params_t *params;
+    const double *feat;
+    const uint32_t *vtype;
+    const uint64_t *vt_off;
+    uint32_t vt_stride_mode;
+    uint32_t *label;
+    double *post;
+    uint32_t post_stride;
+    double *lg;
+    const uint64_t *lg_off;
+    uint32_t lds_n, lds_d, lds_k;
+    const uint64_t *rng_resume;
+    const uint32_t *order;
+    uint32_t *split;
+};
+int launch_mcmc_merged(hipStream_t s, int n_seg, const McmcSegment *seg, hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join);

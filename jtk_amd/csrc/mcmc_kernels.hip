@@ -30,6 +30,7 @@
 // consumer's draws, chain_lds.h the carve, chain_common.h k-means and the chains' shared helpers, chain_producer.h the producer
 // wave, chain_generic.h / chain_tab.h / chain_k2.h the three chains, chain_jump_table.h the producer's table on the host.
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 #include "device_common.h"
@@ -293,7 +294,7 @@ __device__ __forceinline__ double gains_expected(const jtk_gains_t *g, uint32_t 
 #define JTK_TRACE_REC_LEN 16
 #define JTK_TRACE_OLD (JTK_TRACE_REC + 8 * JTK_TRACE_REC_LEN)
 template <bool LIGHT, bool HUGE = false, bool TRACE = false>
-__device__ __forceinline__ void mcmc_body(const ChunkMeta *chunks, ChunkState *state,
+__device__ __forceinline__ void mcmc_body(uint32_t blk, const ChunkMeta *chunks, ChunkState *state,
                                                   const jtk_lc_params_t *params, const double *feat_all,
                                                   const uint32_t *vtype_all, const uint64_t *vt_off_all,
                                                   uint32_t vt_stride_mode, uint32_t *label_all, double *post_all,
@@ -302,13 +303,15 @@ __device__ __forceinline__ void mcmc_body(const ChunkMeta *chunks, ChunkState *s
                                                   uint32_t flags, const uint64_t *rng_resume, const uint32_t *order,
                                                   const uint32_t *order_count, unsigned char *ws_base = nullptr,
                                                   const uint64_t *ws_off = nullptr, double *trace = nullptr) {
+    // `blk`: the workgroup's index among those of its session (blockIdx.x, less the segment's first workgroup in a merged launch;
+    // the global-workspace kernels are never merged and read blockIdx.x itself: their code stays what it was).
     // workgroups are dispatched in blockIdx order: `order` lists the chunks with the longest chains first (their
     // length is 20 x 2000 x n proposals per candidate k), so that on ragged batches the kernel does not end on a
     // long chain that started late.  `order_count`, if given, is the device-side length of the list (the grid is the
     // upper bound the host knows).
-    if (order_count && blockIdx.x >= uni(*order_count)) return;
+    if (order_count && (HUGE ? blockIdx.x : blk) >= uni(*order_count)) return;
     const uint32_t seg_log = uni(seg_log_in);  // the ring's geometry: JTK_SEG_LOG_LIGHT / _GENERAL
-    const uint32_t ci = order ? order[blockIdx.x] : blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t ci = order ? order[HUGE ? blockIdx.x : blk] : (HUGE ? blockIdx.x : blk), lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     ChunkState *st = &state[ci];
     if (st->status != 0) return;
     const ChunkMeta cm = chunks[ci];
@@ -561,17 +564,51 @@ __device__ __forceinline__ void mcmc_body(const ChunkMeta *chunks, ChunkState *s
 #define MCMC_KERNEL_ARGS                                                                                                    \
     chunks, state, params, feat_all, vtype_all, vt_off_all, vt_stride_mode, label_all, post_all, post_stride, lg_all,       \
         lg_off, lds_n, lds_d, lds_k, seg_log, flags, rng_resume, order, order_count
-__global__ __launch_bounds__(128, JTK_MCMC_WAVES) void mcmc_kernel(MCMC_KERNEL_PARAMS) { mcmc_body<false>(MCMC_KERNEL_ARGS); }
+// The LDS chain kernels take their arguments as a table of segments, by value: one segment per session of a merged launch
+// (launch_mcmc_merged), each MCMC_KERNEL_PARAMS of that session plus the launch's first workgroup that belongs to it.  A
+// workgroup finds its segment by a scan of the (at most JTK_MCMC_MAX_SEGMENTS) first workgroups -- scalar loads from the
+// kernel-argument segment -- and runs mcmc_body on that segment's pointers, with its index inside the segment as `blk`.
+// lds_n / lds_d / lds_k describe the LAYOUT of the work area and stay per segment; the launch's dynamic LDS is the largest need.
+struct ChainSeg {
+    const ChunkMeta *chunks;
+    ChunkState *state;
+    const jtk_lc_params_t *params;
+    const double *feat_all;
+    const uint32_t *vtype_all;
+    const uint64_t *vt_off_all;
+    uint32_t *label_all;
+    double *post_all;
+    double *lg_all;
+    const uint64_t *lg_off;
+    const uint64_t *rng_resume;
+    const uint32_t *order, *order_count;
+    uint32_t vt_stride_mode, post_stride, lds_n, lds_d, lds_k, wg0;
+};
+struct ChainSegTable {
+    ChainSeg seg[JTK_MCMC_MAX_SEGMENTS];
+    uint32_t n, seg_log, flags;
+};
+template <bool LIGHT>
+__device__ __forceinline__ void mcmc_segment_body(const ChainSegTable &t) {
+    uint32_t i = 0;
+    for (uint32_t j = 1; j < JTK_MCMC_MAX_SEGMENTS; j++)
+        if (j < t.n && blockIdx.x >= t.seg[j].wg0) i = j;
+    const ChainSeg &g = t.seg[i];
+    mcmc_body<LIGHT>(blockIdx.x - g.wg0, g.chunks, g.state, g.params, g.feat_all, g.vtype_all, g.vt_off_all, g.vt_stride_mode,
+                     g.label_all, g.post_all, g.post_stride, g.lg_all, g.lg_off, g.lds_n, g.lds_d, g.lds_k, t.seg_log, t.flags,
+                     g.rng_resume, g.order, g.order_count);
+}
+__global__ __launch_bounds__(128, JTK_MCMC_WAVES) void mcmc_kernel(const ChainSegTable t) { mcmc_segment_body<false>(t); }
 // Pile-ups whose work area does not fit a CU's LDS, or of more than JTK_MAX_PILEUP reads: the per-read arrays live in a
 // global-memory workspace (ws_base + ws_off[block]), the chain is the one-proposal-per-iteration one.  One wave per SIMD: the
 // seven inlined instantiations of that chain need ~360 registers, and nothing here is built for speed.
 __global__ __launch_bounds__(128, 1) void mcmc_kernel_huge(MCMC_KERNEL_PARAMS, unsigned char *ws_base, const uint64_t *ws_off) {
-    mcmc_body<false, true>(MCMC_KERNEL_ARGS, ws_base, ws_off);
+    mcmc_body<false, true>(blockIdx.x, MCMC_KERNEL_ARGS, ws_base, ws_off);
 }
 // jtk_lc_session_trace: ONE chunk through the global-workspace body (any pile-up size), with the trace records
 __global__ __launch_bounds__(128, 1) void mcmc_kernel_trace(MCMC_KERNEL_PARAMS, unsigned char *ws_base, const uint64_t *ws_off,
                                                             double *trace) {
-    mcmc_body<false, true, true>(MCMC_KERNEL_ARGS, ws_base, ws_off, trace);
+    mcmc_body<false, true, true>(blockIdx.x, MCMC_KERNEL_ARGS, ws_base, ws_off, trace);
 }
 #ifndef JTK_MCMC_LIGHT_WAVES
 #ifdef JTK_MCMC_STATS
@@ -580,13 +617,29 @@ __global__ __launch_bounds__(128, 1) void mcmc_kernel_trace(MCMC_KERNEL_PARAMS, 
 #define JTK_MCMC_LIGHT_WAVES 3
 #endif
 #endif
-__global__ __launch_bounds__(128, JTK_MCMC_LIGHT_WAVES) void mcmc_kernel_light(MCMC_KERNEL_PARAMS) { mcmc_body<true>(MCMC_KERNEL_ARGS); }
+__global__ __launch_bounds__(128, JTK_MCMC_LIGHT_WAVES) void mcmc_kernel_light(const ChainSegTable t) { mcmc_segment_body<true>(t); }
 
 // One wave splits a launch's chunk list (order[] or 0 .. count-1) into the chunks the light kernel can run and the rest,
 // keeping the order (longest chain first) in both: out = counts[2] | light[count] | heavy[count].  Chunks with a trivial
 // outcome (no variant column, failed earlier, copy number < 2) go to the light list: they return at once in either kernel.
-__global__ __launch_bounds__(64) void chain_split_kernel(uint32_t count, const uint32_t *order, const ChunkMeta *chunks,
-                                                         const ChunkState *state, uint32_t *out) {
+// One workgroup per segment of a merged launch.
+struct SplitSeg {
+    uint32_t count;
+    const uint32_t *order;
+    const ChunkMeta *chunks;
+    const ChunkState *state;
+    uint32_t *out;
+};
+struct SplitSegTable {
+    SplitSeg seg[JTK_MCMC_MAX_SEGMENTS];
+};
+__global__ __launch_bounds__(64) void chain_split_kernel(const SplitSegTable t) {
+    const SplitSeg &g = t.seg[blockIdx.x];
+    const uint32_t count = g.count;
+    const uint32_t *order = g.order;
+    const ChunkMeta *chunks = g.chunks;
+    const ChunkState *state = g.state;
+    uint32_t *out = g.out;
     const uint32_t lane = threadIdx.x;
     uint32_t *light = out + 2, *heavy = out + 2 + count;
     uint32_t nl = 0, nh = 0;
@@ -618,42 +671,76 @@ __global__ __launch_bounds__(64) void chain_split_kernel(uint32_t count, const u
 
 }  // namespace
 
-// `split`: 2 + 2 * n_chunks words of device scratch, or null.  With it the launch is two kernels: the light one (168
-// registers, the diploid chunks of <= 127 reads (JTK_LIGHT_MAX_READS) with <= 2 variant columns) and the general one for the rest; without it (or
-// with rng_resume) the general kernel runs everything.  `side` (with its two events), if given, is a second stream the
-// general kernel runs on, beside the light one instead of before it.
+// One chain launch for the segments of `seg` (device_common.h: McmcSegment): per segment `split` is 2 + 2 * n_chunks words of
+// device scratch, or null.  With it the launch is two kernels: the light one (168 registers, the diploid chunks of <= 127
+// reads (JTK_LIGHT_MAX_READS) with <= 2 variant columns) and the general one for the rest; without it (or with rng_resume,
+// either only in a launch of ONE segment) the general kernel runs everything.  `side` (with its two events), if given, is a
+// second stream the general kernel runs on, beside the light one instead of before it.
+int launch_mcmc_merged(hipStream_t s, int n_seg, const McmcSegment *seg, hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join) {
+    if (n_seg < 1 || n_seg > JTK_MCMC_MAX_SEGMENTS) return -1;
+    bool plain = false;
+    for (int i = 0; i < n_seg; i++) plain = plain || !seg[i].split || seg[i].rng_resume;
+    if (plain && n_seg != 1) return -1;
+    ChainSegTable general, light;
+    SplitSegTable sp;
+    memset(&general, 0, sizeof general);
+    memset(&sp, 0, sizeof sp);
+    uint32_t grid = 0;
+    size_t lds = 0, lds_light = 0;
+    for (int i = 0; i < n_seg; i++) {
+        const McmcSegment &x = seg[i];
+        const uint32_t lds_k = clamp_k(x.lds_k);
+        ChainSeg &g = general.seg[i];
+        g = ChainSeg{x.chunks, x.state, x.params, x.feat, x.vtype, x.vt_off, x.label, x.post, x.lg, x.lg_off, x.rng_resume, x.order,
+                     nullptr, x.vt_stride_mode, x.post_stride, x.lds_n, x.lds_d, lds_k, grid};
+        lds = std::max(lds, mcmc_lds_core(x.lds_n, x.lds_d, lds_k, JTK_SEG_LOG_GENERAL));  // the general kernel: a 12 KiB ring
+        grid += x.n_chunks;
+    }
+    general.n = (uint32_t)n_seg;
+    general.seg_log = JTK_SEG_LOG_GENERAL;
+    if (grid == 0) return 0;
+    if (mcmc_upload_jump_table() != 0) return -1;  // the caller fails the call: nothing was launched
+    if (plain) {
+        mcmc_kernel<<<grid, 128, lds, s>>>(general);
+        return 0;
+    }
+    light = general;
+    light.seg_log = JTK_SEG_LOG_LIGHT;
+    for (int i = 0; i < n_seg; i++) {
+        const McmcSegment &x = seg[i];
+        sp.seg[i] = SplitSeg{x.n_chunks, x.order, x.chunks, x.state, x.split};
+        ChainSeg &g = general.seg[i], &l = light.seg[i];
+        g.rng_resume = l.rng_resume = nullptr;
+        g.order = x.split + 2 + x.n_chunks;
+        g.order_count = x.split + 1;
+        l.order = x.split + 2;
+        l.order_count = x.split;
+        l.lds_n = std::min<uint32_t>(x.lds_n, JTK_LIGHT_MAX_READS);
+        l.lds_d = std::min<uint32_t>(x.lds_d, JTK_LIGHT_MAX_DIM);
+        l.lds_k = 2u;
+        lds_light = std::max(lds_light, mcmc_lds_bytes(l.lds_n, l.lds_d, 2));
+    }
+    chain_split_kernel<<<n_seg, 64, 0, s>>>(sp);
+    hipStream_t hs = s;
+    if (side && ev_fork && ev_join && hipEventRecord(ev_fork, s) == hipSuccess &&
+        hipStreamWaitEvent(side, ev_fork, 0) == hipSuccess)
+        hs = side;
+    mcmc_kernel<<<grid, 128, lds, hs>>>(general);
+    mcmc_kernel_light<<<grid, 128, lds_light, s>>>(light);
+    if (hs != s) {
+        if (hipEventRecord(ev_join, hs) != hipSuccess || hipStreamWaitEvent(s, ev_join, 0) != hipSuccess) return -1;
+    }
+    return 0;
+}
+
 int launch_mcmc(hipStream_t s, uint32_t n_chunks, const ChunkMeta *chunks, ChunkState *state,
                 const jtk_lc_params_t *params, const double *feat, const uint32_t *vtype, const uint64_t *vt_off,
                 uint32_t vt_stride_mode, uint32_t *label, double *post, uint32_t post_stride, double *lg,
                 const uint64_t *lg_off, uint32_t lds_n, uint32_t lds_d, uint32_t lds_k, const uint64_t *rng_resume,
                 const uint32_t *order, uint32_t *split, hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join) {
-    if (n_chunks == 0) return 0;
-    lds_k = clamp_k(lds_k);
-    const size_t lds = mcmc_lds_core(lds_n, lds_d, lds_k, JTK_SEG_LOG_GENERAL);  // the general kernel: a 12 KiB ring
-    if (mcmc_upload_jump_table() != 0) return -1;  // the caller fails the call: nothing was launched
-    if (!split || rng_resume) {
-        mcmc_kernel<<<n_chunks, 128, lds, s>>>(chunks, state, params, feat, vtype, vt_off, vt_stride_mode, label, post,
-                                              post_stride, lg, lg_off, lds_n, lds_d, lds_k,
-                                              JTK_SEG_LOG_GENERAL, 0u, rng_resume, order, nullptr);
-        return 0;
-    }
-    chain_split_kernel<<<1, 64, 0, s>>>(n_chunks, order, chunks, state, split);
-    hipStream_t hs = s;
-    if (side && ev_fork && ev_join && hipEventRecord(ev_fork, s) == hipSuccess &&
-        hipStreamWaitEvent(side, ev_fork, 0) == hipSuccess)
-        hs = side;
-    mcmc_kernel<<<n_chunks, 128, lds, hs>>>(chunks, state, params, feat, vtype, vt_off, vt_stride_mode, label, post, post_stride,
-                                           lg, lg_off, lds_n, lds_d, lds_k, JTK_SEG_LOG_GENERAL, 0u,
-                                           nullptr, split + 2 + n_chunks, split + 1);
-    const uint32_t ln = std::min<uint32_t>(lds_n, JTK_LIGHT_MAX_READS), ld = std::min<uint32_t>(lds_d, JTK_LIGHT_MAX_DIM);
-    mcmc_kernel_light<<<n_chunks, 128, mcmc_lds_bytes(ln, ld, 2), s>>>(chunks, state, params, feat, vtype, vt_off, vt_stride_mode,
-                                                                       label, post, post_stride, lg, lg_off, ln, ld, 2u,
-                                                                       JTK_SEG_LOG_LIGHT, 0u, nullptr,
-                                                                       split + 2, split);
-    if (hs != s) {
-        if (hipEventRecord(ev_join, hs) != hipSuccess || hipStreamWaitEvent(s, ev_join, 0) != hipSuccess) return -1;
-    }
-    return 0;
+    const McmcSegment seg = {n_chunks, chunks, state, params, feat, vtype, vt_off, vt_stride_mode, label, post, post_stride, lg,
+                             lg_off, lds_n, lds_d, lds_k, rng_resume, order, split};
+    return launch_mcmc_merged(s, 1, &seg, side, ev_fork, ev_join);
 }
 
 // The chunks listed in `order` (one workgroup each) through mcmc_kernel_huge; ws_off[i] = offset of order[i]'s slice of `ws`

@@ -4,7 +4,7 @@
 // One process drives one GPU.  A session validates and encodes the flat host batch (its layout is session_plan.h's: this file
 // computes no offset, launch class or wave count of its own), uploads it once, allocates
 // every workspace up front (sized for 288 GB of HBM: the full N x 14(L+1) tables of all chunks stay
-// resident), and then runs the stage as a short sequence of kernel launches on its own stream:
+// resident), and then runs the stage as a short sequence of kernel launches on its lane's stream (session_lanes.h):
 //
 //   band_prep -> [ phmm -> finalize -> polish_round ]* until no chunk is active -> filter -> mcmc
 //
@@ -113,12 +113,13 @@ struct BlockPool {
 };
 BlockPool g_pool;
 
-// A batch in flight uses up to four slices x two streams (the chain's general kernel runs beside its light one).  ROCm maps
-// streams onto GPU_MAX_HW_QUEUES hardware queues (4 by default) and streams that share a queue run in order: a slice's 300 ms
-// chain kernel would then hold up another slice's pair-HMM launches.  Eight streams need eight queues, and the host's own
-// streams (the null stream as soon as anything uses it) take theirs: 12.  The variable is read when the HIP runtime
-// initialises, so it is set -- unless the host has set it -- when this library is loaded; a host that has initialised HIP
-// earlier sets it itself.
+// ROCm maps streams onto GPU_MAX_HW_QUEUES hardware queues (4 by default) and streams that share a queue run in order: a
+// slice's 300 ms chain kernel would then hold up another slice's pair-HMM launches.  So sessions do not own streams: they take
+// them from the device's lanes (session_lanes.h), as many as the queues pay for, and the sessions of a lane launch their
+// chains as one kernel.  Where nobody has chosen a queue count the library asks for 12 when it is loaded (the variable is read
+// when the HIP runtime initialises): four lanes of two streams -- the chain's general kernel runs beside its light one -- and
+// the host's own streams (the null stream as soon as anything uses it).  A host's own value is never overwritten: the lanes
+// are fitted to it.
 static bool g_queues_by_library = false;  // the variable was absent when the library was loaded
 static int g_host_queues = 0;             // the host's own setting, if any
 __attribute__((constructor)) void jtk_lc_default_hw_queues() {
@@ -133,6 +134,53 @@ __attribute__((constructor)) void jtk_lc_default_hw_queues() {
 
 std::mutex g_stripe_mutex;
 std::shared_ptr<StripePool> g_stripes[JTK_POOL_DEVICES];
+
+// The lanes, per device: made on demand, never destroyed (a stream that outlives its sessions costs nothing, and no session
+// of a later call has to wait for hipStreamDestroy).
+struct LaneStreams {
+    hipStream_t stream = nullptr, side = nullptr;
+    hipEvent_t ev_chain[2] = {nullptr, nullptr};
+};
+typedef LaneTable<LaneStreams, jtk_lc_session> DeviceLanes;
+std::mutex g_lanes_mutex;  // the map, and the late creation of a lane's side stream
+std::map<int, DeviceLanes *> g_lanes;
+DeviceLanes &device_lanes(int device) {
+    std::lock_guard<std::mutex> lock(g_lanes_mutex);
+    DeviceLanes *&t = g_lanes[device];
+    if (!t) t = new DeviceLanes();
+    return *t;
+}
+
+// The session's streams: the least loaded lane of its device.  The lane count follows the hardware queues the process runs on
+// -- the host's GPU_MAX_HW_QUEUES, or the 12 this library asked for -- unless JTK_LC_LANES gives it; JTK_LC_SIDE_STREAM says
+// whether the session uses the lane's second stream.  Both are read here, when a session is created.
+int take_lane(jtk_lc_session *s, bool want_side) {
+    const char *fl = getenv("JTK_LC_LANES"), *fs = getenv("JTK_LC_SIDE_STREAM");
+    const int queues = g_queues_by_library ? 12 : (g_host_queues > 0 ? g_host_queues : 4);
+    const LanePlan lp = lane_plan(queues, fl ? atoi(fl) : 0, fs ? atoi(fs) : -1);
+    DeviceLanes &t = device_lanes(s->device);
+    const int lane = t.acquire(lp.max_lanes, [](LaneStreams &ls) { return hipStreamCreate(&ls.stream) == hipSuccess; });
+    if (lane < 0) return jtk_fail(JTK_ERR_INTERNAL, "hipStreamCreate failed");
+    DeviceLanes::Lane &L = t.lane(lane);
+    s->lane = lane;
+    s->gather = &L.gather;
+    s->stream = L.streams.stream;
+    JTK_HIP_TRY(hipEventCreateWithFlags(&s->ev_done, hipEventDisableTiming));
+    if (want_side && lp.side) {
+        std::lock_guard<std::mutex> lock(g_lanes_mutex);
+        if (!L.streams.side) {
+            hipStream_t side = nullptr;
+            JTK_HIP_TRY(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
+            JTK_HIP_TRY(hipEventCreateWithFlags(&L.streams.ev_chain[0], hipEventDisableTiming));
+            JTK_HIP_TRY(hipEventCreateWithFlags(&L.streams.ev_chain[1], hipEventDisableTiming));
+            L.streams.side = side;
+        }
+        s->side = L.streams.side;
+        s->ev_chain[0] = L.streams.ev_chain[0];
+        s->ev_chain[1] = L.streams.ev_chain[1];
+    }
+    return 0;
+}
 
 }  // namespace
 
@@ -165,19 +213,29 @@ static void pinned_page_give(uint32_t *p) {
     g_pinned_free.push_back(p);
 }
 
-jtk_lc_session::~jtk_lc_session() {
-    if (stream) (void)hipStreamSynchronize(stream);  // blocks go back to the pool, not through hipFree's implicit sync
-    if (side) {
-        (void)hipStreamSynchronize(side);
-        (void)hipStreamDestroy(side);
+// The session's own work, not the stream: the lane's other sessions go on putting kernels behind it.  (Whatever the session
+// ran on the side stream has been joined into `stream` by the launch that put it there.)
+int session_wait(jtk_lc_session *s) {
+    if (!s->ev_done) {
+        JTK_HIP_TRY(hipStreamSynchronize(s->stream));
+        return 0;
     }
-    for (auto &e : ev_chain)
-        if (e) (void)hipEventDestroy(e);
+    JTK_HIP_TRY(hipEventRecord(s->ev_done, s->stream));
+    JTK_HIP_TRY(hipEventSynchronize(s->ev_done));
+    return 0;
+}
+
+jtk_lc_session::~jtk_lc_session() {
+    if (stream) (void)session_wait(this);  // blocks go back to the pool, not through hipFree's implicit sync
     for (auto &t : timers) {
         if (t.a) (void)hipEventDestroy(t.a);
         if (t.b) (void)hipEventDestroy(t.b);
     }
-    if (stream) (void)hipStreamDestroy(stream);
+    if (ev_done) (void)hipEventDestroy(ev_done);
+    if (lane >= 0)   // the streams and the chain events stay with the lane
+        device_lanes(device).release(lane);
+    else if (stream)
+        (void)hipStreamDestroy(stream);
     if (h_nactive) pinned_page_give(h_nactive);  // (hipHostFree synchronises the whole device: never on the one-shot path)
     for (auto &e : ev_round)
         if (e) (void)hipEventDestroy(e);
@@ -285,7 +343,7 @@ static int stage_reads(jtk_lc_session *s, uint64_t n_reads, const uint8_t *read_
                         reinterpret_cast<uint32_t *>(stage + o_flag));
     uint32_t flags = 0;
     JTK_HIP_TRY(hipMemcpyAsync(&flags, stage + o_flag, 4, hipMemcpyDeviceToHost, s->stream));
-    JTK_HIP_TRY(hipStreamSynchronize(s->stream));   // (also: `tmp` may go back to the pool)
+    if ((rc = session_wait(s))) return rc;   // (also: `tmp` may go back to the pool)
     JTK_HIP_TRY(hipGetLastError());
     if (flags & 2u) return jtk_fail(JTK_ERR_INVALID_ARG, "non-ACGT base in a read");
     if (flags & 4u) return jtk_fail(JTK_ERR_INVALID_ARG, "bad op code");
@@ -304,21 +362,6 @@ static int alloc_polish_workspaces(jtk_lc_session *s, const BatchPlan &bp) {
     JTK_HIP_TRY(hipMemsetAsync(s->d_counter.p, 0, 4 * sizeof(uint32_t), s->stream));  // once: the ticket counters are never reset
     if ((rc = dev_alloc<uint32_t>(s->d_nactive, JTK_NACTIVE_SLOTS))) return rc;
     if ((rc = dev_alloc<uint32_t>(s->d_chain_split, 2 * (size_t)s->n_chunks + 8))) return rc;
-    return 0;
-}
-
-// The second stream (the chain's general kernel beside its light one) only where the hardware queues are there for it: the
-// host asked for >= 8 queues, or the variable was absent when this library was loaded and jtk_lc_default_hw_queues set it (a
-// host that initialised HIP BEFORE loading the library and never set the variable runs on 4 queues: it says so with
-// JTK_LC_SIDE_STREAM=0)
-static int setup_side_stream(jtk_lc_session *s) {
-    const char *force = getenv("JTK_LC_SIDE_STREAM");
-    const bool on = force ? atoi(force) != 0 : (g_queues_by_library || g_host_queues >= 8);
-    if (on) {
-        JTK_HIP_TRY(hipStreamCreateWithFlags(&s->side, hipStreamNonBlocking));
-        JTK_HIP_TRY(hipEventCreateWithFlags(&s->ev_chain[0], hipEventDisableTiming));
-        JTK_HIP_TRY(hipEventCreateWithFlags(&s->ev_chain[1], hipEventDisableTiming));
-    }
     return 0;
 }
 
@@ -367,7 +410,7 @@ static int acquire_stripes(jtk_lc_session *s, uint64_t stride, uint32_t n_stripe
         // streams on eight queues one slice's second stream then shared a queue with its first, and that slice's two chain
         // kernels ran one after the other (serial chain time 1,340 -> 1,490 ms per pass until this was found)
         JTK_HIP_TRY(hipMemsetAsync(p->owner.p, 0, (size_t)p->n * sizeof(uint32_t), s->stream));
-        JTK_HIP_TRY(hipStreamSynchronize(s->stream));
+        if ((rc = session_wait(s))) return rc;
         cur = p;
     }
     s->stripes = cur;
@@ -457,7 +500,7 @@ int session_create_ex(const jtk_lc_params_t *params, size_t n_chunks, const jtk_
     }
 
     // ---- device allocation + upload
-    JTK_HIP_TRY(hipStreamCreate(&s->stream));
+    if ((rc = take_lane(s, !polish_only))) return rc;
     tstart(s, -1);
     const std::vector<jtk_lc_params_t> pv(1, *params);
     const std::vector<HmmDev> hv = {to_dev(params->forward), to_dev(params->reverse)};
@@ -466,7 +509,6 @@ int session_create_ex(const jtk_lc_params_t *params, size_t n_chunks, const jtk_
     if ((rc = stage_reads(s, bp.n_reads, read_bases, read_off, ops, ops_off, bp.raw))) return rc;
     if ((rc = alloc_polish_workspaces(s, bp))) return rc;
     if (!polish_only) {
-        if ((rc = setup_side_stream(s))) return rc;
         if ((rc = alloc_cluster_workspaces(s, bp))) return rc;
     }
     if (extra) {
@@ -489,7 +531,7 @@ int session_create_ex(const jtk_lc_params_t *params, size_t n_chunks, const jtk_
     s->bufs.ops_len[2] = s->d_opslen1.as<uint32_t>();
     if ((rc = dev_upload(s, s->d_state0, s->h_state0))) return rc;
     tstop(s);
-    JTK_HIP_TRY(hipStreamSynchronize(s->stream));
+    if ((rc = session_wait(s))) return rc;
     float ms = 0;
     (void)hipEventElapsedTime(&ms, s->timers.back().a, s->timers.back().b);
     memset(&g_timing, 0, sizeof g_timing);
@@ -506,9 +548,41 @@ int jtk_lc_session_create(const jtk_lc_params_t *params, size_t n_chunks, const 
                              post_stride, device, nullptr, 3 /* mod.rs:105 */, out);
 }
 
+// The chain launch of `n` sessions of one lane (LaneGather::arrive calls it, under the lane's mutex, from the thread of the
+// member that found the lane gathered): per chain class one merged launch with a segment for every member that has chunks of
+// the class.  The second stream only if every member uses it.
+static int launch_lane_chains(jtk_lc_session *const *members, int n) {
+    hipStream_t side = members[0]->side;
+    for (int i = 1; i < n; i++)
+        if (!members[i]->side) side = nullptr;
+    for (int j = 0; j < 2; j++) {
+        McmcSegment seg[JTK_LANE_MAX_SEGMENTS];
+        int n_seg = 0;
+        for (int i = 0; i < n; i++) {
+            jtk_lc_session *s = members[i];
+            const ChainClass &cc = s->chain_class[j];
+            if (cc.count == 0) continue;
+            // the class's own stretch of the split scratch: 2 + 2 * count words from 2 * first + 4 * j
+            seg[n_seg++] = McmcSegment{cc.count, s->d_chunks.as<ChunkMeta>(), s->d_state.as<ChunkState>(), s->d_params.as<jtk_lc_params_t>(),
+                                       s->d_feat.as<double>(), s->d_vtype.as<uint32_t>(), nullptr, 0, s->d_label.as<uint32_t>(),
+                                       s->d_post.as<double>(), s->post_stride, s->d_lg.as<double>(), s->d_lg_off.as<uint64_t>(),
+                                       cc.lds_n, cc.lds_d, cc.lds_k, nullptr, s->d_order.as<uint32_t>() + cc.first,
+                                       s->d_chain_split.as<uint32_t>() + 2 * cc.first + 4 * j};
+        }
+        if (n_seg && launch_mcmc_merged(members[0]->stream, n_seg, seg, side, members[0]->ev_chain[0], members[0]->ev_chain[1]) != 0)
+            return -1;
+    }
+    return 0;
+}
+static_assert(JTK_LANE_MAX_SEGMENTS <= JTK_MCMC_MAX_SEGMENTS, "a lane's launch must fit the kernels' segment table");
+
 // one pass of the kernel sequence over the resident batch
 int run_batch(jtk_lc_session_t *s, int skip_polish) {
     JTK_HIP_TRY(hipSetDevice(s->device));
+    // From here to its chain launch the session is "in its pass" for the sessions it shares a lane with: they hold their
+    // chains back until it arrives or leaves (any return below).  A session that resumes RNG streams (a sub-problem of the
+    // split branch) launches alone, as does one that has no chain at all.
+    LanePass<jtk_lc_session> pass(!s->polish_only && !s->resume_rng ? s->gather : nullptr);
     const double h2d = g_timing.h2d_ms;
     memset(&g_timing, 0, sizeof g_timing);
     g_timing.h2d_ms = h2d;
@@ -610,7 +684,8 @@ int run_batch(jtk_lc_session_t *s, int skip_polish) {
         tstop(s);
         tstart(s, JTK_K_MCMC);
         int mcmc_rc = 0;
-        for (int j = 0; j < 2; j++) {
+        if (pass.g) mcmc_rc = pass.arrive(s, launch_lane_chains);  // with the lane's other sessions, or at once if none is in a pass
+        for (int j = 0; j < 2 && !pass.g; j++) {
             const ChainClass &cc = s->chain_class[j];
             if (cc.count == 0 || mcmc_rc != 0) continue;
             // the class's own stretch of the split scratch: 2 + 2 * count words from 2 * first + 4 * j
@@ -630,14 +705,14 @@ int run_batch(jtk_lc_session_t *s, int skip_polish) {
         }
         tstop(s);
         if (mcmc_rc != 0) {
-            (void)hipStreamSynchronize(st);
+            (void)session_wait(s);
             return jtk_fail(JTK_ERR_INTERNAL, "the chain kernel could not be launched (jump table upload failed)");
         }
         s->ran = true;
         s->ran_fused = !need_tables;
     }  // !polish_only
     JTK_HIP_TRY(hipEventRecord(ev1, st));
-    JTK_HIP_TRY(hipStreamSynchronize(st));
+    JTK_HIP_TRY(hipEventSynchronize(ev1));   // the session's last kernel, not the stream: lane-mates may be queueing behind it
     JTK_HIP_TRY(hipGetLastError());
     float ms = 0;
     (void)hipEventElapsedTime(&ms, ev0, ev1);
@@ -694,7 +769,7 @@ int fetch_begin(jtk_lc_session_t *s, FetchPlan &pl, uint32_t *label, double *log
     if (label) JTK_HIP_TRY(hipMemcpyAsync(label, s->d_label.p, (size_t)s->n_reads * 4, hipMemcpyDeviceToHost, st));
     if (log_post)
         JTK_HIP_TRY(hipMemcpyAsync(log_post, s->d_post.p, (size_t)s->n_reads * s->post_stride * 8, hipMemcpyDeviceToHost, st));
-    JTK_HIP_TRY(hipStreamSynchronize(st));
+    if (int rc = session_wait(s)) return rc;
     for (uint32_t c = 0; c < s->n_chunks; c++) {
         const ChunkState &cs = pl.state[c];
         if (cs.status != 0) {
@@ -764,7 +839,7 @@ int fetch_finish(jtk_lc_session_t *s, FetchPlan &pl, uint8_t *cons_out, uint64_t
     hipEvent_t ev1;
     JTK_HIP_TRY(hipEventCreate(&ev1));
     JTK_HIP_TRY(hipEventRecord(ev1, st));
-    JTK_HIP_TRY(hipStreamSynchronize(st));
+    JTK_HIP_TRY(hipEventSynchronize(ev1));
     JTK_HIP_TRY(hipGetLastError());
     float ms = 0;
     (void)hipEventElapsedTime(&ms, pl.ev0, ev1);

@@ -12,6 +12,7 @@
 #include "device_common.h"
 #include "host_common.h"
 #include "jtk_lc_debug.h"
+#include "session_lanes.h"
 
 #define JTK_POOL_DEVICES 16
 
@@ -56,7 +57,14 @@ struct SplitResult {
 
 struct jtk_lc_session {
     int device = 0;
+    // The streams are the session's lane's (session_lanes.h; session.hip: take_lane), shared with the lane's other sessions:
+    // `lane` is its index in the device's table, `gather` the lane's chain launches, ev_done what the session records behind
+    // its own work to wait for THAT and not for the stream (session_wait).  lane < 0 (session_features.hip): the session made
+    // `stream` itself and destroys it.
     hipStream_t stream = nullptr;
+    int lane = -1;
+    LaneGather<jtk_lc_session> *gather = nullptr;
+    hipEvent_t ev_done = nullptr;
     jtk_lc_params_t params;
     uint32_t n_chunks = 0, n_reads = 0, post_stride = 1;
     uint32_t max_tmpl = 0, max_read = 0, max_n = 0, max_copy = 0, n_waves = 0;
@@ -105,11 +113,12 @@ struct jtk_lc_session {
     uint32_t *h_nactive = nullptr;       // pinned + mapped: the per-round "chunks still active" counters, written by commit_kernel
     uint32_t *h_nactive_dev = nullptr;   // the same memory as the device addresses it
     hipEvent_t ev_round[2] = {nullptr, nullptr};
-    // the chain launch: light / general chunk lists made on the device (mcmc_kernels.hip), the general kernel on its own stream
+    // the chain launch: light / general chunk lists made on the device (mcmc_kernels.hip), the general kernel on the lane's
+    // second stream (null: the session does not use one)
     DevPtr d_chain_split;
     hipStream_t side = nullptr;
     hipEvent_t ev_chain[2] = {nullptr, nullptr};
-    ~jtk_lc_session();  // session.hip: waits for its streams, frees its events, returns its pinned page
+    ~jtk_lc_session();  // session.hip: waits for its own work, frees its events, returns its lane and its pinned page
 };
 
 // a fetch in two halves (session.hip: fetch_begin / fetch_finish)
@@ -135,6 +144,7 @@ int dev_upload(jtk_lc_session *s, DevPtr &d, const std::vector<T> &v) {
     if (!v.empty()) JTK_HIP_TRY(hipMemcpyAsync(d.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s->stream));
     return 0;
 }
+int session_wait(jtk_lc_session *s);        // until everything the session has put on its stream so far is done
 void tstart(jtk_lc_session *s, int kind);  // a timed stretch of the session's stream; ~jtk_lc_session frees the events
 void tstop(jtk_lc_session *s);
 int session_create_ex(const jtk_lc_params_t *params, size_t n_chunks, const jtk_lc_chunk_t *chunks,
