@@ -90,6 +90,39 @@ JTK_LC_API int jtk_lc_debug_gains_batch_sizes(size_t batch, uint64_t *sizes);
 JTK_LC_API int jtk_lc_debug_gains_batch(size_t batch, uint8_t *tmpl, uint64_t *tmpl_off, uint8_t *reads, uint64_t *read_off,
                                         uint8_t *ops, uint32_t *ops_len, double *lk);
 
+/* The lane of a session ("Lanes and the merged chain launch"): sessions of one lane share a stream and
+ * gather their chain kernels into one launch.  Whether two sessions meet in a launch is otherwise a race between their host
+ * threads; these three make it a test's choice and let the test read back what was launched.
+ *
+ * jtk_lc_debug_session_lane: the index of the session's lane in its device's table (JTK_ERR_INVALID_ARG for a null session).
+ *
+ * jtk_lc_debug_lane_hold(device, lane, 1) holds the lane: until the matching (device, lane, 0) every session that reaches its
+ * chain point pends, none launches.  On release a pending session launches everything pending in arrival order, at most 8
+ * sessions per launch.  Holds count; a lane that does not exist and a release without a hold are JTK_ERR_INVALID_ARG.  Sessions
+ * that enter no gather (polish-only ones, the sub-sessions of the split branch) do not wait for a hold.
+ *
+ * jtk_lc_debug_lane_state: in_pass = sessions between the start of a pass and their chain point (holds not counted), holds,
+ * pending = sessions at their chain point waiting for the launch, launch_calls = launches the lane has made so far (one call
+ * carries up to 8 sessions), and the n_records = min(launch_calls, JTK_LC_DEBUG_LANE_RECORDS) most recent of them, oldest first.
+ * Per chain class (0: work areas up to 80 KiB, 1: above) a call makes one merged launch with a segment for every carried
+ * session that has chunks of the class: segments[j] of them (0 = no launch), chunks[j] workgroups in all, seg_chunks[j][i] in
+ * segment i.  Read it while the lane is held or idle. */
+#define JTK_LC_DEBUG_LANE_RECORDS 8
+typedef struct jtk_lc_debug_lane_launch {
+    uint32_t members;
+    uint32_t segments[2];
+    uint32_t chunks[2];
+    uint32_t seg_chunks[2][8];
+} jtk_lc_debug_lane_launch_t;
+typedef struct jtk_lc_debug_lane_state {
+    uint32_t in_pass, holds, pending, n_records;
+    uint64_t launch_calls;
+    jtk_lc_debug_lane_launch_t records[JTK_LC_DEBUG_LANE_RECORDS];
+} jtk_lc_debug_lane_state_t;
+JTK_LC_API int jtk_lc_debug_session_lane(jtk_lc_session_t *s);
+JTK_LC_API int jtk_lc_debug_lane_hold(int device, int lane, int hold);
+JTK_LC_API int jtk_lc_debug_lane_state(int device, int lane, jtk_lc_debug_lane_state_t *out);
+
 #ifdef __cplusplus
 }
 #endif

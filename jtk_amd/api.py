@@ -931,6 +931,13 @@ class Session:
         check(f(self._h, u64p(cyc), u32p(ev)))
         return cyc, ev
 
+    def lane(self):
+        """jtk_lc_debug_session_lane (include/jtk_lc_debug.h): the index of the session's lane on its device"""
+        lane = self._lib.jtk_lc_debug_session_lane(self._h)
+        if lane < 0:
+            check(lane)
+        return lane
+
     def close(self):
         if self._h:
             self._lib.jtk_lc_session_destroy(self._h)
@@ -947,6 +954,26 @@ class Session:
             self.close()
         except Exception:
             pass
+
+
+def lane_hold(lane, hold, device=0):
+    """jtk_lc_debug_lane_hold (include/jtk_lc_debug.h): hold (True) or release (False) the chain launches of a lane; a lane
+    that does not exist and a release without a hold raise JtkError"""
+    check(ffi.lib().jtk_lc_debug_lane_hold(int(device), int(lane), int(bool(hold))))
+
+
+def lane_state(lane, device=0):
+    """jtk_lc_debug_lane_state: dict(in_pass, holds, pending, launch_calls, records); records = the most recent launch calls,
+    oldest first, each dict(members, segments=[class 0, class 1], chunks=[...], seg_chunks=[[per segment], [...]])"""
+    st = ffi.LaneState()
+    check(ffi.lib().jtk_lc_debug_lane_state(int(device), int(lane), C.byref(st)))
+    records = []
+    for r in st.records[:st.n_records]:
+        seg = [int(r.segments[0]), int(r.segments[1])]
+        records.append(dict(members=int(r.members), segments=seg, chunks=[int(r.chunks[0]), int(r.chunks[1])],
+                            seg_chunks=[[int(r.seg_chunks[j][i]) for i in range(seg[j])] for j in range(2)]))
+    return dict(in_pass=int(st.in_pass), holds=int(st.holds), pending=int(st.pending), launch_calls=int(st.launch_calls),
+                records=records)
 
 
 def normalize_pileup(label, log_post, cluster_num):

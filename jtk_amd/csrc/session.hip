@@ -137,9 +137,19 @@ std::shared_ptr<StripePool> g_stripes[JTK_POOL_DEVICES];
 
 // The lanes, per device: made on demand, never destroyed (a stream that outlives its sessions costs nothing, and no session
 // of a later call has to wait for hipStreamDestroy).
+// Beside the streams, the lane's ledger (include/jtk_lc_debug.h): what each of the last calls of launch_lane_chains put into
+// its two class launches, and the holds a test has taken on the lane's gather.
+struct LaneLedger {
+    std::mutex m;
+    unsigned long long calls = 0;
+    jtk_lc_debug_lane_launch_t ring[JTK_LANE_LEDGER] = {};  // call c at c % JTK_LANE_LEDGER, as LaneGather keeps its member counts
+    int holds = 0;
+};
+static_assert(JTK_LANE_LEDGER == JTK_LC_DEBUG_LANE_RECORDS && JTK_LANE_MAX_SEGMENTS == 8, "jtk_lc_debug_lane_launch_t");
 struct LaneStreams {
     hipStream_t stream = nullptr, side = nullptr;
     hipEvent_t ev_chain[2] = {nullptr, nullptr};
+    LaneLedger ledger;
 };
 typedef LaneTable<LaneStreams, jtk_lc_session> DeviceLanes;
 std::mutex g_lanes_mutex;  // the map, and the late creation of a lane's side stream
@@ -550,11 +560,24 @@ int jtk_lc_session_create(const jtk_lc_params_t *params, size_t n_chunks, const 
 
 // The chain launch of `n` sessions of one lane (LaneGather::arrive calls it, under the lane's mutex, from the thread of the
 // member that found the lane gathered): per chain class one merged launch with a segment for every member that has chunks of
-// the class.  The second stream only if every member uses it.
+// the class.  The second stream only if every member uses it.  What the two launches were given -- read from the segment
+// tables themselves, not from the members -- goes into the lane's ledger when the call returns.
 static int launch_lane_chains(jtk_lc_session *const *members, int n) {
     hipStream_t side = members[0]->side;
     for (int i = 1; i < n; i++)
         if (!members[i]->side) side = nullptr;
+    jtk_lc_debug_lane_launch_t rec;
+    memset(&rec, 0, sizeof rec);
+    rec.members = (uint32_t)n;
+    struct Keep {  // (a launch that fails is recorded with what it was given, too)
+        jtk_lc_session *s;
+        const jtk_lc_debug_lane_launch_t &rec;
+        ~Keep() {
+            LaneLedger &lg = device_lanes(s->device).lane(s->lane).streams.ledger;
+            std::lock_guard<std::mutex> lock(lg.m);
+            lg.ring[lg.calls++ % JTK_LANE_LEDGER] = rec;
+        }
+    } keep{members[0], rec};
     for (int j = 0; j < 2; j++) {
         McmcSegment seg[JTK_LANE_MAX_SEGMENTS];
         int n_seg = 0;
@@ -569,12 +592,76 @@ static int launch_lane_chains(jtk_lc_session *const *members, int n) {
                                        cc.lds_n, cc.lds_d, cc.lds_k, nullptr, s->d_order.as<uint32_t>() + cc.first,
                                        s->d_chain_split.as<uint32_t>() + 2 * cc.first + 4 * j};
         }
+        rec.segments[j] = (uint32_t)n_seg;
+        for (int i = 0; i < n_seg; i++) {
+            rec.seg_chunks[j][i] = seg[i].n_chunks;
+            rec.chunks[j] += seg[i].n_chunks;
+        }
         if (n_seg && launch_mcmc_merged(members[0]->stream, n_seg, seg, side, members[0]->ev_chain[0], members[0]->ev_chain[1]) != 0)
             return -1;
     }
     return 0;
 }
 static_assert(JTK_LANE_MAX_SEGMENTS <= JTK_MCMC_MAX_SEGMENTS, "a lane's launch must fit the kernels' segment table");
+
+// include/jtk_lc_debug.h: the lane of a session, a hold on a lane's gather, and what the lane has launched
+static DeviceLanes::Lane *existing_lane(int device, int lane) {
+    DeviceLanes *t = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(g_lanes_mutex);
+        auto it = g_lanes.find(device);
+        if (it != g_lanes.end()) t = it->second;
+    }
+    if (!t || lane < 0 || lane >= t->size()) return nullptr;
+    return &t->lane(lane);
+}
+int jtk_lc_debug_session_lane(jtk_lc_session_t *s) {
+    g_last_error.clear();
+    if (!s) return jtk_fail(JTK_ERR_INVALID_ARG, "null session");
+    if (s->lane < 0) return jtk_fail(JTK_ERR_INVALID_ARG, "the session has no lane");
+    return s->lane;
+}
+int jtk_lc_debug_lane_hold(int device, int lane, int hold) {
+    g_last_error.clear();
+    DeviceLanes::Lane *L = existing_lane(device, lane);
+    if (!L) return jtk_fail(JTK_ERR_INVALID_ARG, "jtk_lc_debug_lane_hold: device " + std::to_string(device) + " has no lane " + std::to_string(lane));
+    LaneLedger &lg = L->streams.ledger;
+    {
+        std::lock_guard<std::mutex> lock(lg.m);
+        if (!hold && lg.holds == 0) return jtk_fail(JTK_ERR_INVALID_ARG, "jtk_lc_debug_lane_hold: release of a lane that is not held");
+        lg.holds += hold ? 1 : -1;
+    }
+    if (hold) L->gather.enter();
+    else L->gather.withdraw();
+    return JTK_OK;
+}
+int jtk_lc_debug_lane_state(int device, int lane, jtk_lc_debug_lane_state_t *out) {
+    g_last_error.clear();
+    DeviceLanes::Lane *L = existing_lane(device, lane);
+    if (!L || !out) return jtk_fail(JTK_ERR_INVALID_ARG, "jtk_lc_debug_lane_state: no such lane, or a null pointer");
+    LaneLedger &lg = L->streams.ledger;
+    // The member counts are the gather's, the class records the ledger's; both advance inside one call of the launch, under
+    // the gather's mutex.  A launch between the two reads shows as different call counts: read again.
+    for (int attempt = 0; attempt < 16; attempt++) {
+        memset(out, 0, sizeof *out);
+        int members[JTK_LANE_LEDGER], in_pass = 0, pending = 0;
+        unsigned long long calls = 0;
+        const int have = L->gather.recent(members, &in_pass, &pending, &calls);
+        std::lock_guard<std::mutex> lock(lg.m);
+        if (lg.calls != calls) continue;
+        out->holds = (uint32_t)lg.holds;
+        out->in_pass = (uint32_t)std::max(0, in_pass - lg.holds);
+        out->pending = (uint32_t)pending;
+        out->launch_calls = calls;
+        out->n_records = (uint32_t)have;
+        for (int i = 0; i < have; i++) {
+            out->records[i] = lg.ring[(calls - have + i) % JTK_LANE_LEDGER];
+            if (out->records[i].members != (uint32_t)members[i]) return jtk_fail(JTK_ERR_INTERNAL, "the lane's ledger and its gather disagree");
+        }
+        return JTK_OK;
+    }
+    return jtk_fail(JTK_ERR_INTERNAL, "jtk_lc_debug_lane_state: the lane kept launching; read it while it is held or idle");
+}
 
 // one pass of the kernel sequence over the resident batch
 int run_batch(jtk_lc_session_t *s, int skip_polish) {

@@ -55,9 +55,39 @@ inline LanePlan lane_plan(int queues, int forced_lanes, int forced_side) {
 // launch runs under the lane's mutex: launches of one lane never interleave.  A waiting member waits for lane-mates that are
 // in a pass NOW or enter one while it waits; a mate that has arrived cannot enter another pass before its launch, so a member
 // waits for at most (members of the lane - 1) passes, and a mate that leaves its pass early (withdraw) is not waited for.
+//
+// A hold is a plain enter() / withdraw() pair from a caller that is no member (a test, through include/jtk_lc_debug.h): while
+// it is held nobody finds the lane empty, so every arriving member pends; on release a waiting member launches everything
+// pending in arrival order, at most JTK_LANE_MAX_SEGMENTS per launch.  A member that withdraws under a hold is neither
+// launched nor waited for.  in_pass() / pending() / launch_calls() / recent() say what the lane is doing and what it
+// launched: the member counts of the last JTK_LANE_LEDGER calls of `launch`, oldest first.
+#define JTK_LANE_LEDGER 8
 template <class Member>
 class LaneGather {
 public:
+    int in_pass() {
+        std::lock_guard<std::mutex> lock(m_);
+        return in_pass_;
+    }
+    int pending() {
+        std::lock_guard<std::mutex> lock(m_);
+        return (int)pending_.size();
+    }
+    unsigned long long launch_calls() {
+        std::lock_guard<std::mutex> lock(m_);
+        return calls_;
+    }
+    // members[i] of the i-th oldest of the last min(launch_calls(), JTK_LANE_LEDGER) calls; returns their number.  in_pass,
+    // pending and calls (any may be null) are read under the same lock.
+    int recent(int *members, int *in_pass = nullptr, int *pending = nullptr, unsigned long long *calls = nullptr) {
+        std::lock_guard<std::mutex> lock(m_);
+        const int have = (int)std::min<unsigned long long>(calls_, JTK_LANE_LEDGER);
+        for (int i = 0; i < have; i++) members[i] = ring_[(calls_ - have + i) % JTK_LANE_LEDGER];
+        if (in_pass) *in_pass = in_pass_;
+        if (pending) *pending = (int)pending_.size();
+        if (calls) *calls = calls_;
+        return have;
+    }
     void enter() {
         std::lock_guard<std::mutex> lock(m_);
         in_pass_++;
@@ -84,6 +114,7 @@ public:
                     const size_t n = std::min<size_t>(pending_.size(), JTK_LANE_MAX_SEGMENTS);
                     Member *group[JTK_LANE_MAX_SEGMENTS];
                     for (size_t i = 0; i < n; i++) group[i] = pending_[i]->member;
+                    ring_[calls_++ % JTK_LANE_LEDGER] = (int)n;
                     const int rc = launch(static_cast<Member *const *>(group), (int)n);
                     for (size_t i = 0; i < n; i++) {
                         pending_[i]->rc = rc;
@@ -108,6 +139,8 @@ private:
     std::condition_variable cv_;
     int in_pass_ = 0;
     std::vector<Ticket *> pending_;  // tickets live on their members' stacks until launched
+    unsigned long long calls_ = 0;   // calls of `launch` so far
+    int ring_[JTK_LANE_LEDGER] = {}; // their member counts, call c at c % JTK_LANE_LEDGER
 };
 
 // a session's pass through its lane's gather: leaves it on every path out of the scope

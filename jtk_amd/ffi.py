@@ -63,6 +63,21 @@ class Timing(C.Structure):
                 ("chain_lds_bytes", C.c_uint32 * 2)]
 
 
+DEBUG_LANE_RECORDS = 8   # JTK_LC_DEBUG_LANE_RECORDS
+
+
+class LaneLaunch(C.Structure):
+    """jtk_lc_debug_lane_launch_t: one call of a lane's chain launch"""
+    _fields_ = [("members", C.c_uint32), ("segments", C.c_uint32 * 2), ("chunks", C.c_uint32 * 2),
+                ("seg_chunks", (C.c_uint32 * 8) * 2)]
+
+
+class LaneState(C.Structure):
+    """jtk_lc_debug_lane_state_t"""
+    _fields_ = [("in_pass", C.c_uint32), ("holds", C.c_uint32), ("pending", C.c_uint32), ("n_records", C.c_uint32),
+                ("launch_calls", C.c_uint64), ("records", LaneLaunch * DEBUG_LANE_RECORDS)]
+
+
 class SquishConfig(C.Structure):
     """jtk_squish_config_t; the defaults are SquishConfig::default() (squish_erroneous_clusters.rs:29-38)."""
     _fields_ = [("ari_thr", C.c_double), ("match_score", C.c_double), ("mismatch_score", C.c_double), ("count_thr", C.c_uint64)]
@@ -121,6 +136,7 @@ DEBUG_SYMBOLS = (
     "jtk_lc_debug_gains_keep", "jtk_lc_debug_gains_batches", "jtk_lc_debug_gains_batch_sizes", "jtk_lc_debug_gains_batch",
     "jtk_lc_debug_guided_scratch_cap", "jtk_lc_debug_guided_timing", "jtk_lc_debug_encode_timing",
     "jtk_lc_debug_guided_table", "jtk_lc_debug_gpolish_timing", "jtk_lc_debug_edges_timing",
+    "jtk_lc_debug_session_lane", "jtk_lc_debug_lane_hold", "jtk_lc_debug_lane_state",
 )
 DEBUG_GAINS_OPS_STRIDE = 512   # JTK_LC_DEBUG_GAINS_OPS_STRIDE
 SYNTH_SYMBOLS = ("jtk_synth_pileup",)
@@ -221,6 +237,9 @@ def lib():
     sig("jtk_lc_debug_gains_batches", sz)
     sig("jtk_lc_debug_gains_batch_sizes", i32, sz, PU64)
     sig("jtk_lc_debug_gains_batch", i32, sz, PU8, PU64, PU8, PU64, PU8, PU32, PD)
+    sig("jtk_lc_debug_session_lane", i32, vp)
+    sig("jtk_lc_debug_lane_hold", i32, i32, i32, i32)
+    sig("jtk_lc_debug_lane_state", i32, i32, i32, C.POINTER(LaneState))
     _lib = L
     return L
 

@@ -203,6 +203,164 @@ static void lone() {
     printf("LONE %d\n", calls);
 }
 
+// ---- holds: an outsider's enter() / withdraw() around the members' arrivals (what jtk_lc_debug_lane_hold does to a lane)
+
+// poll `done` every 50 us for at most 30 s (a sanitizer build on a loaded machine is slow; nothing here waits that long)
+template <class Done>
+static bool wait_for(Done &&done) {
+    const auto until = std::chrono::steady_clock::now() + std::chrono::seconds(30);
+    while (!done()) {
+        if (std::chrono::steady_clock::now() > until) return false;
+        std::this_thread::sleep_for(std::chrono::microseconds(50));
+    }
+    return true;
+}
+
+struct OrderRecorder {  // the members of every launch, by id, in the order the launch was given them
+    std::mutex m;
+    std::vector<std::vector<int>> launches;
+    int operator()(Member *const *g, int n) {
+        EXPECT(n >= 1 && n <= JTK_LANE_MAX_SEGMENTS, "a launch of %d members", n);
+        std::vector<int> ids;
+        for (int i = 0; i < n; i++) {
+            EXPECT(g[i]->state.load() == ARRIVED, "member %d launched in state %d", g[i]->id, g[i]->state.load());
+            g[i]->launched++;
+            ids.push_back(g[i]->id);
+        }
+        std::lock_guard<std::mutex> lock(m);
+        launches.push_back(ids);
+        return 0;
+    }
+    size_t count() {
+        std::lock_guard<std::mutex> lock(m);
+        return launches.size();
+    }
+};
+
+// one member's pass on a thread of its own, started once `pending_before` members pend: the arrival order is the caller's
+static std::thread arrive_after(LaneGather<Member> &g, OrderRecorder &rec, Member &me, int pending_before) {
+    EXPECT(wait_for([&]() { return g.pending() == pending_before; }), "member %d: pending never reached %d", me.id, pending_before);
+    return std::thread([&g, &rec, &me]() {
+        LanePass<Member> p(&g);
+        me.state = ARRIVED;
+        EXPECT(p.arrive(&me, rec) == 0, "rc");
+        EXPECT(me.launched.load() == 1, "member %d launched %d times", me.id, me.launched.load());
+    });
+}
+
+static void expect_launches(OrderRecorder &rec, LaneGather<Member> &g, const std::vector<std::vector<int>> &want, const char *what) {
+    EXPECT(rec.launches == want, "%s: %zu launches, %zu wanted, or other members", what, rec.launches.size(), want.size());
+    int ring[JTK_LANE_LEDGER], in_pass = -1, pending = -1;
+    unsigned long long calls = 0;
+    const int have = g.recent(ring, &in_pass, &pending, &calls);
+    EXPECT(calls == want.size() && g.launch_calls() == want.size(), "%s: %llu calls counted", what, calls);
+    EXPECT(in_pass == 0 && pending == 0 && g.in_pass() == 0 && g.pending() == 0, "%s: in pass %d, pending %d afterwards", what, in_pass, pending);
+    EXPECT(have == (int)std::min<size_t>(want.size(), JTK_LANE_LEDGER), "%s: %d records", what, have);
+    for (int i = 0; i < have; i++) {
+        const size_t call = want.size() - have + i;
+        EXPECT(ring[i] == (int)want[call].size(), "%s: call %zu recorded with %d members", what, call, ring[i]);
+    }
+}
+
+// an outsider holds, n members arrive one after the other from n threads: all pend, nothing is launched; the release gives the
+// first min(n, 8) in arrival order, then the rest, 8 at a time
+static void held(int n) {
+    LaneGather<Member> g;
+    std::vector<Member> mem(n);
+    OrderRecorder rec;
+    g.enter();
+    EXPECT(g.in_pass() == 1 && g.pending() == 0 && g.launch_calls() == 0, "a fresh hold");
+    std::vector<std::thread> th;
+    for (int i = 0; i < n; i++) {
+        mem[i].id = i;
+        th.push_back(arrive_after(g, rec, mem[i], i));
+    }
+    EXPECT(wait_for([&]() { return g.pending() == n; }), "held %d: pending stays at %d", n, g.pending());
+    EXPECT(g.in_pass() == 1, "held %d: %d in a pass beside the hold", n, g.in_pass() - 1);
+    EXPECT(g.launch_calls() == 0 && rec.count() == 0, "held %d: launched under the hold", n);
+    g.withdraw();
+    for (auto &t : th) t.join();
+    std::vector<std::vector<int>> want;
+    for (int i = 0; i < n; i++) {
+        if (i % JTK_LANE_MAX_SEGMENTS == 0) want.emplace_back();
+        want.back().push_back(i);
+    }
+    expect_launches(rec, g, want, "held");
+    printf("HELD %d", n);
+    for (auto &l : rec.launches) printf(" %zu", l.size());
+    printf("\n");
+}
+
+// a member that leaves its pass while the lane is held is neither launched nor waited for: once between two arrivals, once
+// after the hold itself has gone
+static void held_withdraw() {
+    LaneGather<Member> g;
+    Member a, b, c;
+    a.id = 0, b.id = 1, c.id = 2;
+    OrderRecorder rec;
+    g.enter();
+    std::thread ta = arrive_after(g, rec, a, 0);
+    EXPECT(wait_for([&]() { return g.pending() == 1; }), "a pends");
+    {
+        LanePass<Member> pb(&g);
+        b.state = BEFORE;
+        EXPECT(g.in_pass() == 2, "b in its pass under the hold");
+        b.state = IDLE;
+    }  // b fails: no arrive()
+    EXPECT(g.in_pass() == 1 && g.pending() == 1 && g.launch_calls() == 0, "b's withdrawal under the hold launched or unpended");
+    std::thread tc = arrive_after(g, rec, c, 1);
+    EXPECT(wait_for([&]() { return g.pending() == 2; }), "c pends");
+    g.withdraw();
+    ta.join();
+    tc.join();
+    expect_launches(rec, g, {{0, 2}}, "withdraw under a hold");
+    EXPECT(b.launched.load() == 0, "the withdrawn member was launched");
+
+    // the hold goes while b is still in a pass: a goes on waiting for b, and launches alone when b leaves
+    LaneGather<Member> g2;
+    Member a2, b2;
+    a2.id = 0, b2.id = 1;
+    OrderRecorder rec2;
+    g2.enter();
+    std::thread ta2 = arrive_after(g2, rec2, a2, 0);
+    EXPECT(wait_for([&]() { return g2.pending() == 1; }), "a2 pends");
+    {
+        LanePass<Member> pb(&g2);
+        b2.state = ARRIVED;  // (never arrives; ARRIVED so that no launch check trips over it)
+        g2.withdraw();       // the hold
+        std::this_thread::sleep_for(std::chrono::milliseconds(2));
+        EXPECT(g2.launch_calls() == 0 && g2.pending() == 1 && g2.in_pass() == 1, "released with a mate in its pass: launched at once");
+    }
+    ta2.join();
+    expect_launches(rec2, g2, {{0}}, "a mate that leaves after the release");
+    EXPECT(b2.launched.load() == 0, "the withdrawn member was launched");
+    printf("HELD_WITHDRAW ok\n");
+}
+
+// a second hold taken while members pend: the release of the first launches nothing, later arrivals join the same gather
+static void second_hold() {
+    LaneGather<Member> g;
+    Member mem[3];
+    OrderRecorder rec;
+    for (int i = 0; i < 3; i++) mem[i].id = i;
+    g.enter();
+    std::vector<std::thread> th;
+    th.push_back(arrive_after(g, rec, mem[0], 0));
+    th.push_back(arrive_after(g, rec, mem[1], 1));
+    EXPECT(wait_for([&]() { return g.pending() == 2; }), "two pend");
+    g.enter();     // the second hold
+    g.withdraw();  // the first one's release
+    std::this_thread::sleep_for(std::chrono::milliseconds(2));
+    EXPECT(g.launch_calls() == 0 && g.pending() == 2 && g.in_pass() == 1, "the first release launched under the second hold");
+    th.push_back(arrive_after(g, rec, mem[2], 2));
+    EXPECT(wait_for([&]() { return g.pending() == 3; }), "three pend");
+    EXPECT(g.launch_calls() == 0, "launched under the second hold");
+    g.withdraw();
+    for (auto &t : th) t.join();
+    expect_launches(rec, g, {{0, 1, 2}}, "second hold");
+    printf("SECOND_HOLD ok\n");
+}
+
 int main() {
     plans();
     const int qs[] = {1, 4, 8, 12};
@@ -211,6 +369,10 @@ int main() {
     nine();
     withdraw_and_status();
     lone();
+    const int held_sizes[] = {1, 3, 8, 9, 17};
+    for (int n : held_sizes) held(n);
+    held_withdraw();
+    second_hold();
     printf("FAILURES %d\n", g_failures.load());
     return g_failures.load() ? 1 : 0;
 }

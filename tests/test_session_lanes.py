@@ -5,7 +5,8 @@ its runtime refuse to start in the machine's address-space layout), the fallback
 says which one ran.  The program checks the threaded scenarios itself
 (three sessions x four passes from three threads with seeded delays: every arrival launched exactly once, no launch while a
 lane-mate is before its chain point, at most 8 members per launch; nine sessions: launches of 8 and 1; a session that leaves
-through a failure path; a lone session launches from its own thread) and prints the lane plans and assignments, which are
+through a failure path; a lone session launches from its own thread; a lane held by an outsider while 1, 3, 8, 9 and 17 members
+arrive, a member that withdraws under the hold, a second hold taken while members pend) and prints the lane plans and assignments, which are
 compared here with a restatement of the rules."""
 import os
 import subprocess
@@ -66,6 +67,15 @@ def test_the_program_runs_clean_under_the_sanitizer(program):
     assert "NINE 8 1" in out and "WITHDRAW ok" in out and "LONE 3" in out
     line = next(l for l in out.splitlines() if l.startswith("THREE_BY_FOUR")).split()
     assert int(line[4]) == 12 and 4 <= int(line[2]) <= 12   # 12 arrivals; between one launch per pass and one per arrival
+
+
+def test_a_held_lane_gathers_every_arrival(program):
+    """an outsider's enter() / withdraw() around N arrivals from N threads (the program asserts pending == N with no launch made,
+    the members of each launch in arrival order, and the ring of member counts): one launch of the first min(N, 8), then the rest"""
+    out = program[0].stdout.decode().splitlines()
+    held = {int(l.split()[1]): [int(x) for x in l.split()[2:]] for l in out if l.startswith("HELD ")}
+    assert held == {1: [1], 3: [3], 8: [8], 9: [8, 1], 17: [8, 8, 1]}
+    assert "HELD_WITHDRAW ok" in out and "SECOND_HOLD ok" in out
 
 
 def test_lane_plans(program):
