@@ -123,6 +123,31 @@ JTK_LC_API int jtk_lc_debug_session_lane(jtk_lc_session_t *s);
 JTK_LC_API int jtk_lc_debug_lane_hold(int device, int lane, int hold);
 JTK_LC_API int jtk_lc_debug_lane_state(int device, int lane, jtk_lc_debug_lane_state_t *out);
 
+/* The variant filter of a clustering pass by itself ("The filter seam"): homop_kernel, chunk_tables_kernel,
+ * the column filter and the pick, through the launch functions and on the batch layout of a session, from planted input
+ * instead of a pair-HMM pass.  `chunks` / `tmpl_bases` / `strand` as for jtk_lc_session_create (copy_num <= 7); the reads have
+ * no bases.  Read g of a chunk with template length L brings, back to back in read order,
+ *   mode JTK_LC_DEBUG_FILTER_TABLE:      values: 14 (L + 1) doubles, its table minus its likelihood; exps and lk are not read.
+ *                                        Runs the table filter (column_filter_kernel, pick_kernel<true>).
+ *   mode JTK_LC_DEBUG_FILTER_ROWS_FUSED: values: 16 (L + 1) doubles of row sums, exps: L + 1 exponents, lk[g].  Runs the fused
+ *                                        filter (column_filter_fused_kernel, pick_kernel<false>); JTK_ERR_INVALID_ARG for a
+ *                                        chunk of more than 65,535 reads, as a session never takes it for one.
+ *   mode JTK_LC_DEBUG_FILTER_ROWS_TABLE: the same input; finalize_kernel as a session's last pass calls it, then the table filter.
+ * Out, per chunk c: cand[14 * tmpl_off_c + 14 * c ..] = the 14 (L + 1) scores of its columns, -1 for a column that is no
+ * candidate (tmpl_off_c = the sum of the earlier chunks' L); dim[c]; pos[21 c ..] the picked columns in column order and
+ * vtype[42 c ..] their (homopolymer length, difference type) pairs; feat[21 * read_first_c ..] = n_reads x dim[c] features, row
+ * major; trace[66 c ..] = the pick again by pick_trace_kernel: candidates, picks, then the picked candidates' list indices in
+ * pick order (zeros for a chunk of copy number < 2, which has no pick).  Arguments are checked, and refused, before a device is
+ * looked for. */
+#define JTK_LC_DEBUG_FILTER_TABLE 0
+#define JTK_LC_DEBUG_FILTER_ROWS_FUSED 1
+#define JTK_LC_DEBUG_FILTER_ROWS_TABLE 2
+#define JTK_LC_DEBUG_FILTER_TRACE_WORDS 66
+JTK_LC_API int jtk_lc_debug_filter(const jtk_lc_params_t *params, size_t n_chunks, const jtk_lc_chunk_t *chunks,
+                                   const uint8_t *tmpl_bases, const uint8_t *strand, int mode, const double *values,
+                                   const int32_t *exps, const double *lk, double *cand, uint32_t *dim, uint32_t *pos,
+                                   uint32_t *vtype, double *feat, uint32_t *trace, int device);
+
 #ifdef __cplusplus
 }
 #endif

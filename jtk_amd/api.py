@@ -537,6 +537,52 @@ def guided_table(tmpl, reads, opss, radius, device=0):
     return dist[:nr], table
 
 
+def filter_stage(params, chunks, mode, device=0):
+    """jtk_lc_debug_filter (include/jtk_lc_debug.h): the variant filter of a clustering pass on planted input.  A test hook.
+    chunks: dicts with `tmpl` (ASCII bases), `strands` (one per read), `copy_num` and, for mode ffi.DEBUG_FILTER_TABLE, `table`
+    [n, 14 (L + 1)] (minus lk); for the two row-sum modes `rows` [n, L + 1, 16], `exps` [n, L + 1] and `lk` [n].
+    -> per chunk dict(cand [14 (L + 1)], dim, pos [dim], vtype [dim, 2], feat [n, dim], n_cand, order [picks]: the picked
+    candidates' indices among the candidates in pick order)"""
+    rows = mode != ffi.DEBUG_FILTER_TABLE
+    rec = np.zeros(len(chunks) + 1, dtype=ffi.CHUNK_DT)
+    tmpl, strand, values, exps, lk = [], [], [], [], []
+    n_reads = n_bases = 0
+    for c, ch in enumerate(chunks):
+        t = np.frombuffer(ch["tmpl"], dtype=np.uint8) if isinstance(ch["tmpl"], (bytes, bytearray)) else np.asarray(ch["tmpl"], dtype=np.uint8)
+        n, L = len(ch["strands"]), len(t)
+        rec[c] = (c, ch["copy_num"], n, n_bases, L, n_reads)
+        tmpl.append(t)
+        strand.append(np.asarray(ch["strands"], dtype=np.uint8))
+        if rows:
+            assert np.shape(ch["rows"]) == (n, L + 1, 16) and np.shape(ch["exps"]) == (n, L + 1) and np.shape(ch["lk"]) == (n,)
+            values.append(np.asarray(ch["rows"], dtype=np.float64).ravel())
+            exps.append(np.asarray(ch["exps"], dtype=np.int32).ravel())
+            lk.append(np.asarray(ch["lk"], dtype=np.float64))
+        else:
+            assert np.shape(ch["table"]) == (n, ffi.NUM_ROW * (L + 1))
+            values.append(np.asarray(ch["table"], dtype=np.float64).ravel())
+        n_reads, n_bases = n_reads + n, n_bases + L
+    cat = lambda xs, dt: np.ascontiguousarray(np.concatenate(xs + [np.zeros(1, dtype=dt)]))  # noqa: E731
+    tb, st, va = cat(tmpl, np.uint8), cat(strand, np.uint8), cat(values, np.float64)
+    ex, lks = cat(exps, np.int32), cat(lk, np.float64)
+    n_chunks, W = len(chunks), ffi.DEBUG_FILTER_TRACE_WORDS
+    cand = np.zeros(ffi.NUM_ROW * (n_bases + n_chunks) + 1)
+    dim, pos, vtype = np.zeros(n_chunks + 1, dtype=np.uint32), np.zeros((n_chunks + 1, ffi.MAX_DIM), dtype=np.uint32), np.zeros((n_chunks + 1, ffi.MAX_DIM, 2), dtype=np.uint32)
+    feat, trace = np.zeros(n_reads * ffi.MAX_DIM + 1), np.zeros((n_chunks + 1, W), dtype=np.uint32)
+    check(ffi.lib().jtk_lc_debug_filter(C.byref(params), n_chunks, rec.ctypes.data, u8p(tb), u8p(st), int(mode), f64p(va),
+                                        ex.ctypes.data_as(C.POINTER(C.c_int32)) if rows else None, f64p(lks) if rows else None, f64p(cand),
+                                        u32p(dim), u32p(pos), u32p(vtype), f64p(feat), u32p(trace), device))
+    out, co = [], 0
+    for c, ch in enumerate(chunks):
+        n, L, first, d = int(rec["n_reads"][c]), int(rec["tmpl_len"][c]), int(rec["read_first"][c]), int(dim[c])
+        cols = ffi.NUM_ROW * (L + 1)
+        out.append(dict(cand=cand[co:co + cols].copy(), dim=d, pos=pos[c, :d].copy(), vtype=vtype[c, :d].copy(),
+                        feat=feat[ffi.MAX_DIM * first:ffi.MAX_DIM * first + n * d].reshape(n, d).copy(), n_cand=int(trace[c, 0]),
+                        order=trace[c, 2:2 + int(trace[c, 1])].copy()))
+        co += cols
+    return out
+
+
 def gpolish_timing():
     """jtk_lc_debug_gpolish_timing: of the last polish_guided call, pile-ups, reads, rounds enqueued, band cells filled forward,
     kernel ms, the slices of the work area and the bytes all reads take of it by the host's bound"""

@@ -48,15 +48,6 @@ int jtk_require_device(int device) {
 
 namespace {
 
-HmmDev to_dev(const jtk_hmm_t &h) {
-    HmmDev d;
-    const double a[9] = {h.mat_mat, h.mat_ins, h.mat_del, h.ins_mat, h.ins_ins, h.ins_del, h.del_mat, h.del_ins, h.del_del};
-    memcpy(d.a, a, sizeof a);
-    memcpy(d.eM, h.mat_emit, sizeof d.eM);
-    memcpy(d.eI, h.ins_emit, sizeof d.eI);
-    return d;
-}
-
 // The pools below -- g_pool, g_stripes and the pinned-page free list -- stay in THIS translation unit, g_pool first.
 // DevPtr::~DevPtr gives its block to g_pool, and g_stripes[] holds DevPtrs that are destroyed at process exit: within one
 // translation unit objects go in reverse order of definition, so the pool outlives them.  Across translation units the order is
@@ -513,7 +504,7 @@ int session_create_ex(const jtk_lc_params_t *params, size_t n_chunks, const jtk_
     if ((rc = take_lane(s, !polish_only))) return rc;
     tstart(s, -1);
     const std::vector<jtk_lc_params_t> pv(1, *params);
-    const std::vector<HmmDev> hv = {to_dev(params->forward), to_dev(params->reverse)};
+    const std::vector<HmmDev> hv = {hmm_to_dev(params->forward), hmm_to_dev(params->reverse)};
     std::vector<uint64_t> h_rng;
     if ((rc = upload_batch(s, bp, pv, hv, h_tmpl))) return rc;
     if ((rc = stage_reads(s, bp.n_reads, read_bases, read_off, ops, ops_off, bp.raw))) return rc;
@@ -708,7 +699,7 @@ int run_batch(jtk_lc_session_t *s, int skip_polish) {
     // (column_filter_fused_kernel, filter_kernels.hip), so a clustering pass never materialises the N x 14(L+1) table --
     // finalize_kernel runs only where the table itself is the product (window polishing keeps its final-pass call; the
     // modification-table entry point has its own) or where a pile-up is too deep for the fused filter.
-    const bool need_tables = s->polish_only || s->max_n > 65535u;  // (the fused filter counts in 16-bit fields)
+    const bool need_tables = batch_needs_tables(s->polish_only, s->max_n);
     const int max_rounds = skip_polish ? 1 : JTK_POLISH_MAX_ROUNDS + 1;
     for (int round = 0; round < max_rounds; round++) {
         const int only_active = round > 0;

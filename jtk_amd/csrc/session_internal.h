@@ -4,6 +4,7 @@
 // reads a finished session).  The plain records are batch_types.h's; every offset, launch class and wave count of a batch
 // is worked out by session_plan.h, which has no HIP in it.
 #pragma once
+#include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
@@ -40,6 +41,16 @@ struct StripePool {
         return StripeSet{mem.as<double>(), stride, owner.as<uint32_t>(), n};
     }
 };
+
+// a model as the kernels read it
+inline HmmDev hmm_to_dev(const jtk_hmm_t &h) {
+    HmmDev d;
+    const double a[9] = {h.mat_mat, h.mat_ins, h.mat_del, h.ins_mat, h.ins_ins, h.ins_del, h.del_mat, h.del_ins, h.del_del};
+    memcpy(d.a, a, sizeof a);
+    memcpy(d.eM, h.mat_emit, sizeof d.eM);
+    memcpy(d.eI, h.ins_emit, sizeof d.eI);
+    return d;
+}
 
 struct KernelTimer {
     hipEvent_t a = nullptr, b = nullptr;

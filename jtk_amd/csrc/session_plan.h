@@ -293,6 +293,12 @@ inline int plan_batch(const jtk_lc_params_t &params, size_t n_chunks, const jtk_
     return 0;
 }
 
+// Which variant filter a pass takes.  true: the N x 14(L+1) tables are materialised (finalize_kernel) and column_filter_kernel /
+// pick_kernel<true> read them -- where the table itself is the product (window polishing) or a pile-up is too deep for
+// column_filter_fused_kernel, which counts in 16-bit fields.  false: the fused filter, straight from the row sums.
+#define JTK_FUSED_MAX_READS 65535u
+inline bool batch_needs_tables(bool polish_only, uint32_t max_n) { return polish_only || max_n > JTK_FUSED_MAX_READS; }
+
 inline int base_code(uint8_t c) {
     switch (c) {
         case 'A': case 'a': return 0;

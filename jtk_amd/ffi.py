@@ -136,8 +136,11 @@ DEBUG_SYMBOLS = (
     "jtk_lc_debug_gains_keep", "jtk_lc_debug_gains_batches", "jtk_lc_debug_gains_batch_sizes", "jtk_lc_debug_gains_batch",
     "jtk_lc_debug_guided_scratch_cap", "jtk_lc_debug_guided_timing", "jtk_lc_debug_encode_timing",
     "jtk_lc_debug_guided_table", "jtk_lc_debug_gpolish_timing", "jtk_lc_debug_edges_timing",
-    "jtk_lc_debug_session_lane", "jtk_lc_debug_lane_hold", "jtk_lc_debug_lane_state",
+    "jtk_lc_debug_session_lane", "jtk_lc_debug_lane_hold", "jtk_lc_debug_lane_state", "jtk_lc_debug_filter",
 )
+DEBUG_FILTER_TABLE, DEBUG_FILTER_ROWS_FUSED, DEBUG_FILTER_ROWS_TABLE = 0, 1, 2   # modes of jtk_lc_debug_filter
+DEBUG_FILTER_TRACE_WORDS = 66   # JTK_LC_DEBUG_FILTER_TRACE_WORDS
+MAX_DIM = 21                    # JTK_MAX_DIM: the columns a chunk picks at most
 DEBUG_GAINS_OPS_STRIDE = 512   # JTK_LC_DEBUG_GAINS_OPS_STRIDE
 SYNTH_SYMBOLS = ("jtk_synth_pileup",)
 
@@ -240,6 +243,7 @@ def lib():
     sig("jtk_lc_debug_session_lane", i32, vp)
     sig("jtk_lc_debug_lane_hold", i32, i32, i32, i32)
     sig("jtk_lc_debug_lane_state", i32, i32, i32, C.POINTER(LaneState))
+    sig("jtk_lc_debug_filter", i32, PP, sz, vp, PU8, PU8, i32, PD, PI32, PD, PD, PU32, PU32, PU32, PD, PU32, i32)
     _lib = L
     return L
 

@@ -1014,8 +1014,9 @@ def _cosine_similarity(prof, i, j):
 ROUND = 3
 
 
-def pick_filtered_profiles(cands, prof, copy_num):
-    """:516-575 with find_next_variants :590-600 (max_by: the last maximum); returns the selected (pos, lk) in column order"""
+def pick_filtered_profiles(cands, prof, copy_num, order=None):
+    """:516-575 with find_next_variants :590-600 (max_by: the last maximum); returns the selected (pos, lk) in column order.
+    `order`: a list that receives the picked candidates' indices in pick order"""
     sel = [0] * len(cands)
     for _ in range(ROUND):
         sel = [0 if f == 3 else f for f in sel]
@@ -1027,6 +1028,8 @@ def pick_filtered_profiles(cands, prof, copy_num):
             if nx is None:
                 break
             sel[nx] = 1
+            if order is not None:
+                order.append(nx)
             picked = cands[nx][0]
             for i, f in enumerate(sel):
                 if f not in (0, 3):

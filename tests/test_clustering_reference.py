@@ -54,6 +54,7 @@ import pytest
 import clustering_cases as K
 import clustering_reference as R
 import oracle_ffi as O
+from filter_cases import planted_profiles
 from helpers import bits, oracle_params
 from jtk_amd import batch as jb, ffi
 
@@ -454,31 +455,6 @@ def pileup_reference(config):
     local = n / copy_num if copy_num <= 2 else max(n / copy_num, float(p.haploid_coverage))   # mod.rs:108-111
     return R.cluster_profiles(np.array(tabs), tmpl, strands, R.Gains.from_params(p), copy_num, float(p.haploid_coverage), local,
                               int(b.chunks["chunk_id"][0]), R.ProjectMath())
-
-
-def planted_profiles():
-    """A pile-up at the filter's interface: 12 reads (6 per strand, alternating) on a 60 bp template without runs except AAAA
-    at 30..33; every entry -2 (no gain), and columns planted with +6 in the six carriers (three per strand) and -6 elsewhere,
-    one to pass and one to fail each filter of filter_profiles (:440-465) on its own.  Returns (template, profiles, strands,
-    {name: (bp, row)}, {name: the filter that must drop it, None for the columns that must stay})."""
-    tmpl = O.seq("ACGTCAGTCTGACTGATCGATGCATGCTAC" + "AAAA" + "CGTACTGACGTCATGCAGTCGATCGT")
-    tl, n = len(tmpl), 12
-    assert tl == 60
-    strands = [r % 2 == 0 for r in range(n)]
-    carriers = [0, 1, 2, 3, 4, 5]                 # three forward, three reverse
-    forward_only = [r for r in range(n) if strands[r]]
-    prof = np.full((n, 14 * (tl + 1)), -2.0)
-    where = dict(passes=(20, 1), passes_too=(12, 6), edge_low=(6, 1), edge_high=(55, 2), first_kept=(7, 1), last_kept=(54, 0), ins_in_run=(31, 4),
-                 del_in_run=(31, 11), ins_next_to_its_base=(22, 4 + "ACGT".index(chr(tmpl[22]))), strand_biased=(40, 2), small_gain=(46, 3),
-                 copy_row=(26, 9), copy_row_10=(44, 10), del_2=(16, 12))
-    why = dict(passes=None, passes_too=None, edge_low="edge", edge_high="edge", first_kept=None, last_kept=None, ins_in_run="homopolymer",
-               del_in_run="homopolymer", ins_next_to_its_base=None, strand_biased="strand", small_gain="gain_per_count", copy_row="row",
-               copy_row_10="row", del_2="row")
-    for name, (bp, row) in where.items():
-        who = forward_only if name == "strand_biased" else carriers
-        value = 3.0 if name == "small_gain" else 6.0
-        prof[:, bp * 14 + row] = [value if r in who else -6.0 for r in range(n)]
-    return tmpl, prof, strands, where, why
 
 
 def test_planted_columns_are_dropped_by_their_own_filter(oracle):

@@ -144,6 +144,10 @@ int main() {
         const ChainDims x = chain_dims_of(cm);
         printf("DIMS %u %u %u %u\n", copy, x.n, x.d, x.k);
     }
+    // which variant filter a pass takes
+    for (int polish_only = 0; polish_only < 2; polish_only++)
+        for (uint32_t n : {0u, 1u, 65535u, 65536u, 0xffffffffu})
+            printf("TABLES %d %u %d\n", polish_only, n, (int)batch_needs_tables(polish_only != 0, n));
     return 0;
 }
 '''
@@ -408,8 +412,8 @@ def program_output(tmp_path_factory):
         tag, _, rest = line.partition(" ")
         if tag == "CASE":
             cur = got.setdefault(rest, {})
-        elif tag == "DIMS":
-            got.setdefault("DIMS", []).append(tuple(map(int, rest.split())))
+        elif tag in ("DIMS", "TABLES"):
+            got.setdefault(tag, []).append(tuple(map(int, rest.split())))
         else:
             cur.setdefault(tag, []).append(rest)
     return {cs["name"]: cs for cs in cases}, got
@@ -526,3 +530,11 @@ def test_chain_dims_of_a_chunk(program_output):
     _, got = program_output
     assert got["DIMS"] == [(copy,) + chain_dims(copy, 10 + copy) for copy in range(10)]
     assert {d for _, _, d, _ in got["DIMS"]} == {6, 9, 12, 15, 18, 21} and {k for _, _, _, k in got["DIMS"]} == {2, 3, 4, 5, 6, 7}
+
+
+def test_which_filter_a_pass_takes(program_output):
+    """batch_needs_tables, the dispatch of session_run between the fused filter and the table filter: the fused one counts in
+    16-bit fields, so it is taken up to 65,535 reads of the deepest pile-up and not at 65,536; window polishing always has tables"""
+    _, got = program_output
+    assert got["TABLES"] == [(0, 0, 0), (0, 1, 0), (0, 65535, 0), (0, 65536, 1), (0, 0xffffffff, 1),
+                             (1, 0, 1), (1, 1, 1), (1, 65535, 1), (1, 65536, 1), (1, 0xffffffff, 1)]
