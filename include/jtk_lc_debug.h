@@ -123,6 +123,41 @@ JTK_LC_API int jtk_lc_debug_session_lane(jtk_lc_session_t *s);
 JTK_LC_API int jtk_lc_debug_lane_hold(int device, int lane, int hold);
 JTK_LC_API int jtk_lc_debug_lane_state(int device, int lane, jtk_lc_debug_lane_state_t *out);
 
+/* The polish rounds of a lane ("Lanes and the merged round launch"): lane-mates that are in their polish
+ * phase at the same time put their rounds into one launch per kernel.  A session parks at its lane's round gather wherever it
+ * would queue a round -- the opening of its pass (reset + band preparation), then every polish round -- and the launch is made
+ * once every session of the lane that is in its polish phase is parked.  Sessions that do not take part (pair items, wide reads,
+ * per-read tables, jtk_lc_polish_chunks, the sub-sessions of the split branch, JTK_LC_MERGE_ROUNDS=0) never park and never
+ * appear in the records.
+ *
+ * jtk_lc_debug_round_hold(device, lane, 1) holds the lane's round gather: until the matching (device, lane, 0) every arriving
+ * session pends and nothing launches; after the release the launch is made as soon as every session in its polish phase is
+ * parked, in arrival order, at most 8 sessions per call.  (device, lane, 2) is a step: the sessions parked at that moment get
+ * their launch, whoever else is in its polish phase, and the hold stays -- so a test can put sessions of different rounds into
+ * one launch.  Holds count.  A hold of the chain gather (jtk_lc_debug_lane_hold) does not stall rounds, and this one does not
+ * stall chains of sessions that have left their polish phase.
+ *
+ * jtk_lc_debug_round_state: in_rounds = sessions in their polish phase, parked = those waiting for a launch, holds, launch_calls
+ * = round launches the lane has made (a single-session one counts), and the n_records most recent, oldest first.  A record is
+ * read back from the segment table the kernels were given: members = its segments (1 and merged = 0: the single-session
+ * kernels ran), and per member round[i] (JTK_LC_DEBUG_ROUND_OPEN: the opening), chunks[i], and phmm_items[i], its reads in
+ * phmm_kernel's merged item space (0 at the opening). */
+#define JTK_LC_DEBUG_ROUND_RECORDS 64
+#define JTK_LC_DEBUG_ROUND_OPEN 0xffffffffu
+typedef struct jtk_lc_debug_round_launch {
+    uint32_t members, merged;
+    uint32_t round[8];
+    uint32_t chunks[8];
+    uint32_t phmm_items[8];
+} jtk_lc_debug_round_launch_t;
+typedef struct jtk_lc_debug_round_state {
+    uint32_t in_rounds, holds, parked, n_records;
+    uint64_t launch_calls;
+    jtk_lc_debug_round_launch_t records[JTK_LC_DEBUG_ROUND_RECORDS];
+} jtk_lc_debug_round_state_t;
+JTK_LC_API int jtk_lc_debug_round_hold(int device, int lane, int hold);
+JTK_LC_API int jtk_lc_debug_round_state(int device, int lane, jtk_lc_debug_round_state_t *out);
+
 /* The variant filter of a clustering pass by itself ("The filter seam"): homop_kernel, chunk_tables_kernel,
  * the column filter and the pick, through the launch functions and on the batch layout of a session, from planted input
  * instead of a pair-HMM pass.  `chunks` / `tmpl_bases` / `strand` as for jtk_lc_session_create (copy_num <= 7); the reads have

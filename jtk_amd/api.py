@@ -1022,6 +1022,28 @@ def lane_state(lane, device=0):
                 records=records)
 
 
+def round_hold(lane, hold, device=0):
+    """jtk_lc_debug_round_hold (include/jtk_lc_debug.h): hold (True / 1) or release (False / 0) the round launches of a lane, or
+    let the sessions parked now launch once under the hold ("step" / 2)"""
+    code = 2 if hold == "step" else int(hold)
+    check(ffi.lib().jtk_lc_debug_round_hold(int(device), int(lane), code))
+
+
+def round_state(lane, device=0):
+    """jtk_lc_debug_round_state: dict(in_rounds, holds, parked, launch_calls, records); records = the most recent round launches,
+    oldest first, each dict(members, merged, round=[per member; None = the opening of a pass], chunks=[...], phmm_items=[...])"""
+    st = ffi.RoundState()
+    check(ffi.lib().jtk_lc_debug_round_state(int(device), int(lane), C.byref(st)))
+    records = []
+    for r in st.records[:st.n_records]:
+        n = int(r.members)
+        records.append(dict(members=n, merged=bool(r.merged),
+                            round=[None if r.round[i] == ffi.DEBUG_ROUND_OPEN else int(r.round[i]) for i in range(n)],
+                            chunks=[int(r.chunks[i]) for i in range(n)], phmm_items=[int(r.phmm_items[i]) for i in range(n)]))
+    return dict(in_rounds=int(st.in_rounds), holds=int(st.holds), parked=int(st.parked), launch_calls=int(st.launch_calls),
+                records=records)
+
+
 def normalize_pileup(label, log_post, cluster_num):
     """normalize_local_clustering for one pile-up (normalize.rs:21-50), in place."""
     label = np.ascontiguousarray(label, dtype=np.uint32)

@@ -105,6 +105,82 @@ void launch_polish_round(hipStream_t s, uint32_t n_chunks, uint32_t n_reads, con
                          const double *table, double *total, Edit *edits, uint32_t *new_len, uint32_t max_tmpl,
                          uint32_t ignore_edge, int final_pass, uint32_t *n_active_out, uint32_t *n_active_host);
                          // (`total` holds the round's column totals: launch_sum_final)
+// The polish rounds of several sessions in one launch per kernel (the sessions of a lane, session_lanes.h: RoundGather).  A
+// segment is one session's round: its pointers, its own flags, and which step of its pass it is at -- the opening (`open`:
+// reset_pass + band_prep of every read) or polish round `round` (phmm, sum_final, select_edits, rethread, commit, band_prep
+// of the active chunks; a final pass ends after select_edits).  Lane-mates need not be at the same step.  Every merged kernel
+// takes the table by value plus its own prefix of first blocks / items (a segment that has no part in the kernel has no
+// width), finds its segment by a scalar scan of the prefix and runs the single-session kernel's body on that segment's
+// pointers with a rebased index: the same arithmetic on the same buffers in the same order.  Nothing waits for anything.
+#define JTK_ROUND_MAX_SEGMENTS 8
+struct RoundSegment {
+    uint32_t n_chunks, n_reads;
+    const ReadMeta *reads;
+    const ChunkMeta *chunks;
+    ChunkState *state;
+    const ChunkState *state0;
+    DevBufs bufs;
+    const uint8_t *ey;
+    uint64_t *delta;
+    const HmmDev *hmm2;
+    double *raw;
+    int *rawG;
+    double *lk;
+    double *total;
+    Edit *edits;
+    uint32_t *new_len;
+    uint32_t *n_active;       // the session's JTK_NACTIVE_SLOTS counters; round r's is n_active[r]
+    uint32_t *n_active_host;  // their pinned mirror as the device addresses it (or null)
+    uint32_t max_tmpl, max_read, n_waves;
+    uint32_t open, round;     // the pass's opening, or polish round `round`
+    uint32_t ignore_edge, skip_le_radius;
+    int only_active, final_pass;
+};
+struct RoundSegTable {
+    RoundSegment seg[JTK_ROUND_MAX_SEGMENTS];
+    uint32_t n;
+};
+// what a merged launch carried, read back from the tables the kernels were given (the lane's round ledger)
+struct RoundLaunchInfo {
+    uint32_t segments;                           // of the table
+    uint32_t round[JTK_ROUND_MAX_SEGMENTS];      // 0xffffffff: the opening
+    uint32_t chunks[JTK_ROUND_MAX_SEGMENTS];
+    uint32_t phmm_items[JTK_ROUND_MAX_SEGMENTS]; // the segment's width in phmm_kernel's item space
+};
+// a merged kernel's own prefix: first[i] = the first block (or item) of segment i, first[JTK_ROUND_MAX_SEGMENTS] = their number;
+// entries past the table's last segment hold that number too, so the scan needs no segment count
+struct RoundFirst {
+    uint32_t first[JTK_ROUND_MAX_SEGMENTS + 1];
+};
+template <class Width>
+inline uint32_t round_prefix(const RoundSegTable &t, RoundFirst &f, Width &&width) {
+    uint32_t at = 0;
+    for (uint32_t i = 0; i <= JTK_ROUND_MAX_SEGMENTS; i++) {
+        f.first[i] = at;
+        if (i < t.n) at += width(t.seg[i]);
+    }
+    return at;
+}
+#ifdef __HIPCC__
+// idx < first[JTK_ROUND_MAX_SEGMENTS]: the segment that holds it (a segment without width is never found).  Everything here
+// is uniform and comes from the kernel-argument segment: scalar loads and compares.
+__device__ __forceinline__ uint32_t round_segment_of(const RoundFirst &f, uint32_t idx) {
+    uint32_t i = 0;
+#pragma unroll
+    for (uint32_t j = 1; j < JTK_ROUND_MAX_SEGMENTS; j++)
+        if (idx >= f.first[j]) i = j;
+    return i;
+}
+#endif
+void round_table_info(const RoundSegTable &t, RoundLaunchInfo *info);
+void launch_reset_pass_merged(hipStream_t s, const RoundSegTable &t);
+void launch_band_prep_merged(hipStream_t s, const RoundSegTable &t);
+// `work_counter` / `ticket_base`: the LANE's never-reset ticket counter and its host mirror; `stripes`: a set whose stripes are
+// long enough for every segment; n_waves: of the largest segment (at most the set's stripes)
+void launch_phmm_merged(hipStream_t s, const RoundSegTable &t, StripeSet stripes, uint32_t n_waves, uint32_t *work_counter,
+                        uint32_t *ticket_base, RoundLaunchInfo *info);
+void launch_sum_final_merged(hipStream_t s, const RoundSegTable &t);
+void launch_polish_round_merged(hipStream_t s, const RoundSegTable &t);
 // filter_kernels.hip: the variant search of a clustering pass, and one chunk's pick once more with its trace arrays
 void launch_filter(hipStream_t s, uint32_t n_chunks, const ReadMeta *reads, const ChunkMeta *chunks,
                    ChunkState *state, DevBufs bufs, const jtk_lc_params_t *params, const double *table,

@@ -28,6 +28,8 @@
 //    registers the prefetch queue used to occupy and enter the 8-slot LDS ring one per step as before.  Which groups replay is
 //    a bit per group, worked out once per read from the band deltas (bf bits: the backward group is fast AND both forward
 //    groups that produce its pairs were).
+#include <cstring>
+
 #include "device_common.h"
 
 
@@ -884,24 +886,44 @@ __global__ __launch_bounds__(64, 3) __attribute__((amdgpu_num_vgpr(JTK_PHMM_NUM_
         if (lane == 0) item = atomicAdd(work_counter, 1u) - ticket_base;  // tickets: the counter is never reset
         item = __builtin_amdgcn_readfirstlane(item);
         if (item >= n_reads) break;
-        const ReadMeta rm = reads[item];
-        const ChunkMeta cm = chunks[rm.chunk];
-        const ChunkState st = state[rm.chunk];
-        if (st.status != 0) continue;
-        if (only_active && !st.active) continue;
-        if (cm.take_num && item - cm.read_first >= cm.take_num) continue;  // this read does not vote
-        if (cm.radius > JTK_MAX_RADIUS) continue;                          // phmm_wide_kernel's read
-        if (cm.radius <= skip_le_radius) continue;                         // phmm_pair_kernel's read
-        const uint64_t *delta = delta_all + rm.delta_off;
-        // the interval of diagonals whose whole band lies inside the DP matrix (band_prep_kernel)
-        const uint64_t fastw = delta[((cm.tmpl_cap + rm.read_len) >> 6) + 2];
-        // everything below was loaded through the vector memory path: make it scalar again (it is the same in every lane),
-        // or the sweeps' control flow and addressing would be per-lane
-        const int strand = uni((int)rm.strand), buf = uni((int)st.buf);
-        sweep_read(uni((int)st.tmpl_len), uni((int)rm.read_len), uni((int)cm.radius), uni((int)(uint32_t)fastw),
-                   uni((int)(uint32_t)(fastw >> 32)), hmm2 + (strand ? 0 : 1), bufs.tmpl[buf] + uni64(cm.tmpl_off),
-                   ey_all + uni64(rm.ey_off), delta_all + uni64(rm.delta_off), scratch, raw_all + uni64(rm.raw_off),
-                   rawG_all + uni64(rm.row_off), lk_all + item, lds_tmpl, lds_read);
+#include "phmm_item_body.h"
+    }
+    jtk_stripe_release(stripes, stripe);
+}
+
+// The rounds of several sessions: the items are the segments' reads back to back (f.first[i] = segment i's first item,
+// f.first[JTK_ROUND_MAX_SEGMENTS] = their number), the tickets come from a counter of the LANE.  A wave resolves the segment
+// of every item it takes; the item index is wave-uniform (readfirstlane), so the scan, the segment's pointers and its flags
+// are scalar loads from the kernel-argument segment and live in SGPRs: the sweep's register budget is phmm_kernel's.
+__global__ __launch_bounds__(64, 3) __attribute__((amdgpu_num_vgpr(JTK_PHMM_NUM_VGPR))) void phmm_merged_kernel(
+    const RoundSegTable t, const RoundFirst f, StripeSet stripes, uint32_t *work_counter, uint32_t ticket_base, uint32_t lds_tmpl,
+    uint32_t lds_read) {
+    const int lane = threadIdx.x;
+    const uint32_t stripe = jtk_stripe_acquire(stripes);
+    double2 *scratch = reinterpret_cast<double2 *>(stripes.mem + (uint64_t)stripe * stripes.stride) + JTK_SCRATCH_GUARD * 64;
+#pragma unroll
+    for (int g = 1; g <= JTK_SCRATCH_GUARD; g++) scratch[-g * 64 + lane] = make_double2(0.0, 0.0);
+    const uint32_t n_items = f.first[JTK_ROUND_MAX_SEGMENTS];
+    for (;;) {
+        uint32_t item = 0;
+        if (lane == 0) item = atomicAdd(work_counter, 1u) - ticket_base;
+        item = __builtin_amdgcn_readfirstlane(item);
+        if (item >= n_items) break;
+        const uint32_t i = round_segment_of(f, item);
+        const RoundSegment &g = t.seg[i];
+        item -= f.first[i];
+        const ReadMeta *reads = g.reads;
+        const ChunkMeta *chunks = g.chunks;
+        const ChunkState *state = g.state;
+        const DevBufs &bufs = g.bufs;
+        const uint8_t *ey_all = g.ey;
+        const uint64_t *delta_all = g.delta;
+        const HmmDev *hmm2 = g.hmm2;
+        double *raw_all = g.raw, *lk_all = g.lk;
+        int *rawG_all = g.rawG;
+        const int only_active = g.only_active;
+        const uint32_t skip_le_radius = g.skip_le_radius;
+#include "phmm_item_body.h"
     }
     jtk_stripe_release(stripes, stripe);
 }
@@ -927,4 +949,38 @@ void launch_phmm(hipStream_t s, uint32_t n_reads, const ReadMeta *reads, const C
     // the host mirror of the never-reset ticket counter moves only when the launch was accepted: a rejected launch (LDS, grid
     // or an earlier sticky error) takes no tickets, and a mirror that ran ahead would make every later launch exit at once
     if (hipPeekAtLastError() == hipSuccess) *ticket_base = base + n_reads + n_waves;
+}
+
+// what a merged launch carries, from its table (and phmm_merged_kernel's own prefix)
+static uint32_t phmm_prefix(const RoundSegTable &t, RoundFirst &f) {
+    return round_prefix(t, f, [](const RoundSegment &g) { return g.open ? 0u : g.n_reads; });
+}
+void round_table_info(const RoundSegTable &t, RoundLaunchInfo *info) {
+    RoundFirst f;
+    phmm_prefix(t, f);
+    memset(info, 0, sizeof *info);
+    info->segments = t.n;
+    for (uint32_t i = 0; i < t.n && i < JTK_ROUND_MAX_SEGMENTS; i++) {
+        info->round[i] = t.seg[i].open ? 0xffffffffu : t.seg[i].round;
+        info->chunks[i] = t.seg[i].n_chunks;
+        info->phmm_items[i] = f.first[i + 1] - f.first[i];
+    }
+}
+
+void launch_phmm_merged(hipStream_t s, const RoundSegTable &t, StripeSet stripes, uint32_t n_waves, uint32_t *work_counter,
+                        uint32_t *ticket_base, RoundLaunchInfo *info) {
+    RoundFirst f;
+    const uint32_t n_items = phmm_prefix(t, f);
+    if (info) round_table_info(t, info);
+    if (n_items == 0 || n_waves == 0) return;
+    uint32_t max_tmpl = 0, max_read = 0;
+    for (uint32_t i = 0; i < t.n; i++) {
+        if (t.seg[i].open) continue;
+        max_tmpl = t.seg[i].max_tmpl > max_tmpl ? t.seg[i].max_tmpl : max_tmpl;
+        max_read = t.seg[i].max_read > max_read ? t.seg[i].max_read : max_read;
+    }
+    const size_t lds = phmm_lds_bytes(max_tmpl, max_read);
+    const uint32_t base = *ticket_base;
+    phmm_merged_kernel<<<n_waves, 64, lds, s>>>(t, f, stripes, work_counter, base, max_tmpl, max_read);
+    if (hipPeekAtLastError() == hipSuccess) *ticket_base = base + n_items + n_waves;  // (as launch_phmm)
 }

@@ -137,10 +137,22 @@ struct LaneLedger {
     int holds = 0;
 };
 static_assert(JTK_LANE_LEDGER == JTK_LC_DEBUG_LANE_RECORDS && JTK_LANE_MAX_SEGMENTS == 8, "jtk_lc_debug_lane_launch_t");
+// The same for the lane's round launches (launch_lane_rounds): what each of the last calls carried.
+struct RoundLedger {
+    std::mutex m;
+    unsigned long long calls = 0;
+    jtk_lc_debug_round_launch_t ring[JTK_LC_DEBUG_ROUND_RECORDS] = {};
+};
+static_assert(JTK_ROUND_MAX_SEGMENTS == 8 && JTK_LANE_MAX_SEGMENTS <= JTK_ROUND_MAX_SEGMENTS, "jtk_lc_debug_round_launch_t");
 struct LaneStreams {
     hipStream_t stream = nullptr, side = nullptr;
     hipEvent_t ev_chain[2] = {nullptr, nullptr};
     LaneLedger ledger;
+    // merged polish rounds: phmm_merged_kernel's never-reset ticket counter (device, zeroed once on the lane's stream) and its
+    // host mirror, both touched only by launch_lane_rounds, which runs under the round gather's mutex
+    uint32_t *d_round_counter = nullptr;
+    uint32_t tk_round = 0;
+    RoundLedger round_ledger;
 };
 typedef LaneTable<LaneStreams, jtk_lc_session> DeviceLanes;
 std::mutex g_lanes_mutex;  // the map, and the late creation of a lane's side stream
@@ -167,6 +179,16 @@ int take_lane(jtk_lc_session *s, bool want_side) {
     s->gather = &L.gather;
     s->stream = L.streams.stream;
     JTK_HIP_TRY(hipEventCreateWithFlags(&s->ev_done, hipEventDisableTiming));
+    {
+        std::lock_guard<std::mutex> lock(g_lanes_mutex);
+        if (!L.streams.d_round_counter) {  // (kept with the lane for the life of the process, like its streams)
+            uint32_t *c = nullptr;
+            JTK_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c), 4 * sizeof(uint32_t)));
+            JTK_HIP_TRY(hipMemsetAsync(c, 0, 4 * sizeof(uint32_t), L.streams.stream));
+            L.streams.d_round_counter = c;
+        }
+    }
+    s->rounds = &L.rounds;
     if (want_side && lp.side) {
         std::lock_guard<std::mutex> lock(g_lanes_mutex);
         if (!L.streams.side) {
@@ -226,12 +248,18 @@ int session_wait(jtk_lc_session *s) {
     return 0;
 }
 
-jtk_lc_session::~jtk_lc_session() {
-    if (stream) (void)session_wait(this);  // blocks go back to the pool, not through hipFree's implicit sync
+void timers_clear(std::vector<KernelTimer> &timers) {
     for (auto &t : timers) {
+        if (t.shared) continue;
         if (t.a) (void)hipEventDestroy(t.a);
         if (t.b) (void)hipEventDestroy(t.b);
     }
+    timers.clear();
+}
+
+jtk_lc_session::~jtk_lc_session() {
+    if (stream) (void)session_wait(this);  // blocks go back to the pool, not through hipFree's implicit sync
+    timers_clear(timers);
     if (ev_done) (void)hipEventDestroy(ev_done);
     if (lane >= 0)   // the streams and the chain events stay with the lane
         device_lanes(device).release(lane);
@@ -654,6 +682,262 @@ int jtk_lc_debug_lane_state(int device, int lane, jtk_lc_debug_lane_state_t *out
     return jtk_fail(JTK_ERR_INTERNAL, "jtk_lc_debug_lane_state: the lane kept launching; read it while it is held or idle");
 }
 
+// include/jtk_lc_debug.h: a hold on a lane's round gather, and what the lane's round launches carried
+int jtk_lc_debug_round_hold(int device, int lane, int hold) {
+    g_last_error.clear();
+    DeviceLanes::Lane *L = existing_lane(device, lane);
+    if (!L || hold < 0 || hold > 2)
+        return jtk_fail(JTK_ERR_INVALID_ARG, "jtk_lc_debug_round_hold: device " + std::to_string(device) + " has no lane " + std::to_string(lane) + ", or an unknown request");
+    if (hold == 1) L->rounds.hold();
+    else if (hold == 2) L->rounds.step();
+    else if (!L->rounds.release()) return jtk_fail(JTK_ERR_INVALID_ARG, "jtk_lc_debug_round_hold: release of a lane that is not held");
+    return JTK_OK;
+}
+int jtk_lc_debug_round_state(int device, int lane, jtk_lc_debug_round_state_t *out) {
+    g_last_error.clear();
+    DeviceLanes::Lane *L = existing_lane(device, lane);
+    if (!L || !out) return jtk_fail(JTK_ERR_INVALID_ARG, "jtk_lc_debug_round_state: no such lane, or a null pointer");
+    memset(out, 0, sizeof *out);
+    int members[JTK_LANE_LEDGER], in_rounds = 0, parked = 0, holds = 0;
+    (void)L->rounds.recent(members, &in_rounds, &parked, nullptr, &holds);
+    out->in_rounds = (uint32_t)in_rounds;
+    out->parked = (uint32_t)parked;
+    out->holds = (uint32_t)holds;
+    RoundLedger &lg = L->streams.round_ledger;
+    std::lock_guard<std::mutex> lock(lg.m);
+    out->launch_calls = lg.calls;
+    const unsigned long long have = std::min<unsigned long long>(lg.calls, JTK_LC_DEBUG_ROUND_RECORDS);
+    out->n_records = (uint32_t)have;
+    for (unsigned long long i = 0; i < have; i++) out->records[i] = lg.ring[(lg.calls - have + i) % JTK_LC_DEBUG_ROUND_RECORDS];
+    return JTK_OK;
+}
+
+// ---- the polish rounds of a pass: alone on the stream, or with the lane-mates' in one launch per kernel
+
+// the opening of a pass: every chunk back to the batch as uploaded (buffer set 0 is never written, so there is nothing to
+// copy) and the per-round counters to zero -- one small kernel, no blits -- then the bands of every read
+static int queue_open_alone(jtk_lc_session *s) {
+    hipStream_t st = s->stream;
+    launch_reset_pass(st, s->n_chunks, s->d_state.as<ChunkState>(), s->d_state0.as<ChunkState>(), s->d_nactive.as<uint32_t>(), JTK_NACTIVE_SLOTS);
+    tstart(s, JTK_K_POLISH);
+    launch_band_prep(st, s->n_reads, s->d_reads.as<ReadMeta>(), s->d_chunks.as<ChunkMeta>(), s->d_state.as<ChunkState>(), s->bufs,
+                     s->d_delta.as<uint64_t>(), 0, s->max_tmpl, s->max_read);
+    tstop(s);
+    return 0;
+}
+
+// one polish round of one session, as a pass has always queued it; the round's event is recorded behind it
+static int queue_round_alone(jtk_lc_session *s, int round, int only_active, int final_pass) {
+    hipStream_t st = s->stream;
+    const ReadMeta *reads = s->d_reads.as<ReadMeta>();
+    const ChunkMeta *chunks = s->d_chunks.as<ChunkMeta>();
+    ChunkState *state = s->d_state.as<ChunkState>();
+    const HmmDev *hmm2 = s->d_hmm2.as<HmmDev>();
+    // Round 6: the variant filter takes its column statistics and the picked columns' entries straight from the row sums
+    // (column_filter_fused_kernel, filter_kernels.hip), so a clustering pass never materialises the N x 14(L+1) table --
+    // finalize_kernel runs only where the table itself is the product (window polishing keeps its final-pass call; the
+    // modification-table entry point has its own) or where a pile-up is too deep for the fused filter.
+    const bool need_tables = batch_needs_tables(s->polish_only, s->max_n);
+    tstart(s, JTK_K_PHMM);
+    launch_phmm(st, s->n_reads, reads, chunks, state, s->bufs, s->d_ey.as<uint8_t>(), s->d_delta.as<uint64_t>(),
+                hmm2, s->stripes->set(), s->n_waves, s->d_counter.as<uint32_t>(), &s->tk_phmm,
+                s->d_raw.as<double>(), s->d_rawG.as<int>(), s->d_lk.as<double>(), s->max_tmpl, s->max_read,
+                only_active, s->n_pair_items ? JTK_PAIR_MAX_RADIUS : 0);
+    if (s->n_pair_items)
+        launch_phmm_pair(st, s->n_pair_items, s->d_pair_items.as<uint32_t>(), reads, chunks, state, s->bufs,
+                         s->d_ey.as<uint8_t>(), s->d_delta.as<uint64_t>(), hmm2, s->stripes->set(),
+                         s->n_pair_waves, s->d_counter.as<uint32_t>() + 1, &s->tk_pair, s->d_raw.as<double>(), s->d_rawG.as<int>(),
+                         s->d_lk.as<double>(), s->max_tmpl, s->max_read, only_active);
+    if (s->n_wide_reads)
+        launch_phmm_wide(st, s->n_reads, reads, chunks, state, s->bufs, s->d_ey.as<uint8_t>(), s->d_delta.as<uint64_t>(),
+                         hmm2, s->d_wide_scratch.as<double>(), s->wide_stride, s->n_wide_waves,
+                         s->d_wide_counter.as<uint32_t>(), &s->tk_wide, s->d_raw.as<double>(), s->d_rawG.as<int>(),
+                         s->d_lk.as<double>(), s->max_tmpl, s->max_read, only_active, s->max_wide_radius);
+    // A polish round needs the column totals of the active chunks, not their per-read tables: the totals come straight from
+    // the row sums (sum_final_kernel), and only a chunk that turns out to have converged -- no edit selected -- gets its
+    // table, once, from the row sums it still holds.  The last pass materialises the tables of whatever is still active.
+    if (final_pass) {
+        if (need_tables)
+            launch_finalize(st, s->n_reads, reads, chunks, state, hmm2, s->d_raw.as<double>(), s->d_rawG.as<int>(),
+                            s->d_lk.as<double>(), s->max_tmpl, only_active);
+    } else
+        launch_sum_final(st, s->n_chunks, reads, chunks, state, hmm2, s->d_raw.as<double>(), s->d_rawG.as<int>(),
+                         s->d_lk.as<double>(), s->d_total.as<double>(), s->max_tmpl);
+    tstop(s);
+    tstart(s, JTK_K_POLISH);
+    launch_polish_round(st, s->n_chunks, s->n_reads, reads, chunks, state, s->bufs, s->d_ey.as<uint8_t>(),
+                        s->d_raw.as<double>(), s->d_total.as<double>(), s->d_edits.as<Edit>(),
+                        s->d_newlen.as<uint32_t>(), s->max_tmpl, s->ignore_edge, final_pass,
+                        s->d_nactive.as<uint32_t>() + round, s->h_nactive_dev + round);
+    if (!final_pass)
+        launch_band_prep(st, s->n_reads, reads, chunks, state, s->bufs, s->d_delta.as<uint64_t>(), 1, s->max_tmpl, s->max_read);
+    tstop(s);
+    if (!final_pass && !s->polish_only && need_tables) {  // the chunks that converged in this round: their tables, for the variant search
+        tstart(s, JTK_K_PHMM);
+        launch_finalize(st, s->n_reads, reads, chunks, state, hmm2, s->d_raw.as<double>(), s->d_rawG.as<int>(),
+                        s->d_lk.as<double>(), s->max_tmpl, 0, round);
+        tstop(s);
+    }
+    // commit_kernel has stored the round's count in h_nactive[round] itself (mapped pinned memory): no read-back copy
+    if (!final_pass) JTK_HIP_TRY(hipEventRecord(s->ev_round[round & 1], st));
+    return 0;
+}
+
+static int queue_request_alone(jtk_lc_session *s) {
+    const jtk_lc_session::RoundRequest &rq = s->round_request;
+    return rq.open ? queue_open_alone(s) : queue_round_alone(s, rq.round, rq.only_active, rq.final_pass);
+}
+
+static void round_ledger_add(jtk_lc_session *s, const jtk_lc_debug_round_launch_t &rec) {
+    RoundLedger &lg = device_lanes(s->device).lane(s->lane).streams.round_ledger;
+    std::lock_guard<std::mutex> lock(lg.m);
+    lg.ring[lg.calls++ % JTK_LC_DEBUG_ROUND_RECORDS] = rec;
+}
+
+// a timed stretch of a merged launch: one event pair on the lane's stream, shared by the members it is booked to
+struct SharedPair {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~SharedPair() {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+    }
+};
+static std::shared_ptr<SharedPair> pair_start(hipStream_t st) {  // null: an event could not be made or recorded
+    auto p = std::make_shared<SharedPair>();
+    if (hipEventCreate(&p->a) != hipSuccess || hipEventCreate(&p->b) != hipSuccess || hipEventRecord(p->a, st) != hipSuccess) return nullptr;
+    return p;
+}
+static void pair_book(jtk_lc_session *s, int kind, const std::shared_ptr<SharedPair> &p) {
+    KernelTimer t;
+    t.a = p->a;
+    t.b = p->b;
+    t.kind = kind;
+    t.shared = p;
+    s->timers.push_back(t);
+}
+
+// The round launch of `n` sessions of one lane (RoundGather::arrive calls it, under the gather's mutex, from the thread of
+// the member that found the lane's rounds gathered).  One member: exactly what it queues without a gather.  Several: one
+// segment per member, whatever step each is at, and one launch per kernel; the phmm / polish event pairs are the launch's,
+// booked to every member they cover (kernel_launches counts a merged launch once per member it carried), and every member's
+// own round event is recorded behind the sequence.  What was launched goes into the lane's round ledger, from the table.
+static int launch_lane_rounds_on_this_thread(jtk_lc_session *const *members, int n);
+static int launch_lane_rounds(jtk_lc_session *const *members, int n) {
+    // the launch runs on ONE member's thread and g_last_error is per thread: a failure's text is left with every member it
+    // carried, and each puts it into its own thread's g_last_error when arrive() returns (run_batch)
+    const int rc = launch_lane_rounds_on_this_thread(members, n);
+    for (int i = 0; i < n; i++) members[i]->round_error = rc ? g_last_error : std::string();
+    return rc;
+}
+static int launch_lane_rounds_on_this_thread(jtk_lc_session *const *members, int n) {
+    uint64_t chunk_rows = 0;
+    for (int i = 0; i < n; i++) chunk_rows += members[i]->n_chunks;
+    if (n == 1 || chunk_rows > 65535u) {  // (sum_final's merged grid has the chunks of all members in one dimension)
+        for (int i = 0; i < n; i++) {
+            jtk_lc_session *s = members[i];
+            jtk_lc_debug_round_launch_t rec;
+            memset(&rec, 0, sizeof rec);
+            rec.members = 1;
+            rec.round[0] = s->round_request.open ? JTK_LC_DEBUG_ROUND_OPEN : (uint32_t)s->round_request.round;
+            rec.chunks[0] = s->n_chunks;
+            rec.phmm_items[0] = s->round_request.open ? 0 : s->n_reads;
+            round_ledger_add(s, rec);
+            if (int rc = queue_request_alone(s)) return rc;
+        }
+        return 0;
+    }
+    LaneStreams &ls = device_lanes(members[0]->device).lane(members[0]->lane).streams;
+    hipStream_t st = members[0]->stream;
+    RoundSegTable t;
+    memset(&t, 0, sizeof t);
+    t.n = (uint32_t)n;
+    bool any_open = false, any_round = false;
+    uint32_t n_waves = 0;
+    const StripePool *stripes = nullptr;
+    for (int i = 0; i < n; i++) {
+        jtk_lc_session *s = members[i];
+        const jtk_lc_session::RoundRequest &rq = s->round_request;
+        RoundSegment &g = t.seg[i];
+        g.n_chunks = s->n_chunks;
+        g.n_reads = s->n_reads;
+        g.reads = s->d_reads.as<ReadMeta>();
+        g.chunks = s->d_chunks.as<ChunkMeta>();
+        g.state = s->d_state.as<ChunkState>();
+        g.state0 = s->d_state0.as<ChunkState>();
+        g.bufs = s->bufs;
+        g.ey = s->d_ey.as<uint8_t>();
+        g.delta = s->d_delta.as<uint64_t>();
+        g.hmm2 = s->d_hmm2.as<HmmDev>();
+        g.raw = s->d_raw.as<double>();
+        g.rawG = s->d_rawG.as<int>();
+        g.lk = s->d_lk.as<double>();
+        g.total = s->d_total.as<double>();
+        g.edits = s->d_edits.as<Edit>();
+        g.new_len = s->d_newlen.as<uint32_t>();
+        g.n_active = s->d_nactive.as<uint32_t>();
+        g.n_active_host = s->h_nactive_dev;
+        g.max_tmpl = s->max_tmpl;
+        g.max_read = s->max_read;
+        g.n_waves = s->n_waves;
+        g.open = rq.open ? 1u : 0u;
+        g.round = (uint32_t)rq.round;
+        g.ignore_edge = s->ignore_edge;
+        g.skip_le_radius = 0;  // (a session with pair items does not merge)
+        g.only_active = rq.only_active;
+        g.final_pass = rq.final_pass;
+        if (rq.open) {
+            any_open = true;
+            continue;
+        }
+        any_round = true;
+        n_waves = std::max(n_waves, s->n_waves);
+        // the forward scratch: the members' set with the longest stripes serves every segment
+        const StripePool *sp = s->stripes.get();
+        if (!stripes || sp->stride > stripes->stride || (sp->stride == stripes->stride && sp->n > stripes->n)) stripes = sp;
+    }
+    jtk_lc_debug_round_launch_t rec;
+    memset(&rec, 0, sizeof rec);
+    RoundLaunchInfo info;
+    round_table_info(t, &info);
+    if (any_open) launch_reset_pass_merged(st, t);
+    if (any_round) {
+        auto p = pair_start(st);
+        if (!p) return jtk_fail(JTK_ERR_INTERNAL, "hipEventCreate / hipEventRecord failed for a merged round");
+        launch_phmm_merged(st, t, stripes->set(), std::min(n_waves, stripes->n), ls.d_round_counter, &ls.tk_round, &info);
+        launch_sum_final_merged(st, t);
+        JTK_HIP_TRY(hipEventRecord(p->b, st));
+        for (int i = 0; i < n; i++)
+            if (!members[i]->round_request.open) pair_book(members[i], JTK_K_PHMM, p);
+    }
+    {
+        auto p = pair_start(st);
+        if (!p) return jtk_fail(JTK_ERR_INTERNAL, "hipEventCreate / hipEventRecord failed for a merged round");
+        if (any_round) launch_polish_round_merged(st, t);
+        launch_band_prep_merged(st, t);
+        JTK_HIP_TRY(hipEventRecord(p->b, st));
+        for (int i = 0; i < n; i++) pair_book(members[i], JTK_K_POLISH, p);
+    }
+    rec.members = info.segments;
+    rec.merged = 1;
+    for (int i = 0; i < JTK_ROUND_MAX_SEGMENTS; i++) {
+        rec.round[i] = info.round[i];
+        rec.chunks[i] = info.chunks[i];
+        rec.phmm_items[i] = info.phmm_items[i];
+    }
+    round_ledger_add(members[0], rec);
+    for (int i = 0; i < n; i++) {
+        const jtk_lc_session::RoundRequest &rq = members[i]->round_request;
+        if (!rq.open && !rq.final_pass) JTK_HIP_TRY(hipEventRecord(members[i]->ev_round[rq.round & 1], st));
+    }
+    return 0;
+}
+
+// Lane-mates' rounds go out in one launch per kernel unless JTK_LC_MERGE_ROUNDS=0 (read at every pass).
+static bool merge_rounds_enabled() {
+    const char *e = getenv("JTK_LC_MERGE_ROUNDS");
+    return !e || atoi(e) != 0;
+}
+
 // one pass of the kernel sequence over the resident batch
 int run_batch(jtk_lc_session_t *s, int skip_polish) {
     JTK_HIP_TRY(hipSetDevice(s->device));
@@ -664,11 +948,7 @@ int run_batch(jtk_lc_session_t *s, int skip_polish) {
     const double h2d = g_timing.h2d_ms;
     memset(&g_timing, 0, sizeof g_timing);
     g_timing.h2d_ms = h2d;
-    for (auto &t : s->timers) {
-        if (t.a) (void)hipEventDestroy(t.a);
-        if (t.b) (void)hipEventDestroy(t.b);
-    }
-    s->timers.clear();
+    timers_clear(s->timers);
     hipStream_t st = s->stream;
     const ReadMeta *reads = s->d_reads.as<ReadMeta>();
     const ChunkMeta *chunks = s->d_chunks.as<ChunkMeta>();
@@ -678,13 +958,6 @@ int run_batch(jtk_lc_session_t *s, int skip_polish) {
     JTK_HIP_TRY(hipEventCreate(&ev0));
     JTK_HIP_TRY(hipEventCreate(&ev1));
     JTK_HIP_TRY(hipEventRecord(ev0, st));
-    // reset the mutable state: every chunk back to the batch as uploaded (buffer set 0 is never written, so there is
-    // nothing to copy) and the per-round counters to zero -- one small kernel, no blits
-    launch_reset_pass(st, s->n_chunks, state, s->d_state0.as<ChunkState>(), s->d_nactive.as<uint32_t>(), JTK_NACTIVE_SLOTS);
-
-    tstart(s, JTK_K_POLISH);
-    launch_band_prep(st, s->n_reads, reads, chunks, state, s->bufs, s->d_delta.as<uint64_t>(), 0, s->max_tmpl, s->max_read);
-    tstop(s);
     // The host has to learn when every chunk has converged, but the device never waits for it: round r+1 is queued BEFORE the
     // host looks at round r's counter (a round without active chunks does nothing: every kernel of a round >= 1 skips the
     // chunks that are not active), so a pass costs at most one empty round instead of a host round trip per round.
@@ -695,63 +968,38 @@ int run_batch(jtk_lc_session_t *s, int skip_polish) {
         JTK_HIP_TRY(hipEventCreateWithFlags(&s->ev_round[0], hipEventDisableTiming));
         JTK_HIP_TRY(hipEventCreateWithFlags(&s->ev_round[1], hipEventDisableTiming));
     }
-    // Round 6: the variant filter takes its column statistics and the picked columns' entries straight from the row sums
-    // (column_filter_fused_kernel, filter_kernels.hip), so a clustering pass never materialises the N x 14(L+1) table --
-    // finalize_kernel runs only where the table itself is the product (window polishing keeps its final-pass call; the
-    // modification-table entry point has its own) or where a pile-up is too deep for the fused filter.
+    // The rounds go through the lane's round gather (session_lanes.h): lane-mates that are in their polish phase at the same
+    // time get one launch per kernel for all of them; a session that is alone there launches what it always has.  Sessions
+    // whose rounds hold kernels the segment tables do not cover queue them alone: pair items, wide reads, per-read tables,
+    // and the passes that enter no chain gather either.
+    const bool gathers = pass.g && s->rounds && !skip_polish && !s->n_pair_items && !s->n_wide_reads &&
+                         !batch_needs_tables(s->polish_only, s->max_n) && merge_rounds_enabled();
+    RoundPass<jtk_lc_session> rounds(gathers ? s->rounds : nullptr);
+    auto queue = [&](int open, int round, int only_active, int final_pass) -> int {
+        s->round_request.open = open;
+        s->round_request.round = round;
+        s->round_request.only_active = only_active;
+        s->round_request.final_pass = final_pass;
+        if (!rounds.g) return queue_request_alone(s);
+        const int arc = rounds.g->arrive(s, launch_lane_rounds);
+        if (arc) g_last_error = s->round_error;   // (the launch may have run on a lane-mate's thread)
+        return arc;
+    };
+    int rc = queue(1, 0, 0, 0);
+    if (rc) return rc;
     const bool need_tables = batch_needs_tables(s->polish_only, s->max_n);
     const int max_rounds = skip_polish ? 1 : JTK_POLISH_MAX_ROUNDS + 1;
     for (int round = 0; round < max_rounds; round++) {
         const int only_active = round > 0;
         const int final_pass = skip_polish || round == JTK_POLISH_MAX_ROUNDS;
-        tstart(s, JTK_K_PHMM);
-        launch_phmm(st, s->n_reads, reads, chunks, state, s->bufs, s->d_ey.as<uint8_t>(), s->d_delta.as<uint64_t>(),
-                    hmm2, s->stripes->set(), s->n_waves, s->d_counter.as<uint32_t>(), &s->tk_phmm,
-                    s->d_raw.as<double>(), s->d_rawG.as<int>(), s->d_lk.as<double>(), s->max_tmpl, s->max_read,
-                    only_active, s->n_pair_items ? JTK_PAIR_MAX_RADIUS : 0);
-        if (s->n_pair_items)
-            launch_phmm_pair(st, s->n_pair_items, s->d_pair_items.as<uint32_t>(), reads, chunks, state, s->bufs,
-                             s->d_ey.as<uint8_t>(), s->d_delta.as<uint64_t>(), hmm2, s->stripes->set(),
-                             s->n_pair_waves, s->d_counter.as<uint32_t>() + 1, &s->tk_pair, s->d_raw.as<double>(), s->d_rawG.as<int>(),
-                             s->d_lk.as<double>(), s->max_tmpl, s->max_read, only_active);
-        if (s->n_wide_reads)
-            launch_phmm_wide(st, s->n_reads, reads, chunks, state, s->bufs, s->d_ey.as<uint8_t>(), s->d_delta.as<uint64_t>(),
-                             hmm2, s->d_wide_scratch.as<double>(), s->wide_stride, s->n_wide_waves,
-                             s->d_wide_counter.as<uint32_t>(), &s->tk_wide, s->d_raw.as<double>(), s->d_rawG.as<int>(),
-                             s->d_lk.as<double>(), s->max_tmpl, s->max_read, only_active, s->max_wide_radius);
-        // A polish round needs the column totals of the active chunks, not their per-read tables: the totals come straight from
-        // the row sums (sum_final_kernel), and only a chunk that turns out to have converged -- no edit selected -- gets its
-        // table, once, from the row sums it still holds.  The last pass materialises the tables of whatever is still active.
-        if (final_pass) {
-            if (need_tables)
-                launch_finalize(st, s->n_reads, reads, chunks, state, hmm2, s->d_raw.as<double>(), s->d_rawG.as<int>(),
-                                s->d_lk.as<double>(), s->max_tmpl, only_active);
-        } else
-            launch_sum_final(st, s->n_chunks, reads, chunks, state, hmm2, s->d_raw.as<double>(), s->d_rawG.as<int>(),
-                             s->d_lk.as<double>(), s->d_total.as<double>(), s->max_tmpl);
-        tstop(s);
-        tstart(s, JTK_K_POLISH);
-        launch_polish_round(st, s->n_chunks, s->n_reads, reads, chunks, state, s->bufs, s->d_ey.as<uint8_t>(),
-                            s->d_raw.as<double>(), s->d_total.as<double>(), s->d_edits.as<Edit>(),
-                            s->d_newlen.as<uint32_t>(), s->max_tmpl, s->ignore_edge, final_pass,
-                            s->d_nactive.as<uint32_t>() + round, s->h_nactive_dev + round);
-        if (!final_pass)
-            launch_band_prep(st, s->n_reads, reads, chunks, state, s->bufs, s->d_delta.as<uint64_t>(), 1, s->max_tmpl, s->max_read);
-        tstop(s);
-        if (!final_pass && !s->polish_only && need_tables) {  // the chunks that converged in this round: their tables, for the variant search
-            tstart(s, JTK_K_PHMM);
-            launch_finalize(st, s->n_reads, reads, chunks, state, hmm2, s->d_raw.as<double>(), s->d_rawG.as<int>(),
-                            s->d_lk.as<double>(), s->max_tmpl, 0, round);
-            tstop(s);
-        }
+        if ((rc = queue(0, round, only_active, final_pass))) return rc;
         if (final_pass) break;
-        // commit_kernel has stored the round's count in h_nactive[round] itself (mapped pinned memory): no read-back copy
-        JTK_HIP_TRY(hipEventRecord(s->ev_round[round & 1], st));
         if (round >= 1) {
             JTK_HIP_TRY(hipEventSynchronize(s->ev_round[(round - 1) & 1]));
             if (s->h_nactive[round - 1] == 0) break;  // round `round` was already queued and finds nothing to do
         }
     }
+    rounds.leave();  // before the chain point: the lane-mates' rounds do not wait for this session any more
     if (!s->polish_only) {
         tstart(s, JTK_K_FILTER);
         launch_filter(st, s->n_chunks, reads, chunks, state, s->bufs, s->d_params.as<jtk_lc_params_t>(),

@@ -55,7 +55,11 @@ inline HmmDev hmm_to_dev(const jtk_hmm_t &h) {
 struct KernelTimer {
     hipEvent_t a = nullptr, b = nullptr;
     int kind = 0;
+    // set: the pair belongs to a merged round launch and is shared by the sessions it carried (a family's time then includes
+    // the lane-mates'); the last holder destroys the events
+    std::shared_ptr<void> shared;
 };
+void timers_clear(std::vector<KernelTimer> &timers);  // session.hip: destroys the events a session owns alone
 
 // result of one clustering_recursive call (ClusteringDevResult, mod.rs:124)
 struct SplitResult {
@@ -75,6 +79,13 @@ struct jtk_lc_session {
     hipStream_t stream = nullptr;
     int lane = -1;
     LaneGather<jtk_lc_session> *gather = nullptr;
+    // the lane's round gather (session_lanes.h: RoundGather) and what the session asks of it when it parks there: the opening of
+    // its pass, or polish round `round` with its own flags
+    RoundGather<jtk_lc_session> *rounds = nullptr;
+    struct RoundRequest {
+        int open = 0, round = 0, only_active = 0, final_pass = 0;
+    } round_request;
+    std::string round_error;   // the text of a failed round launch that carried this session (written under the gather's mutex)
     hipEvent_t ev_done = nullptr;
     jtk_lc_params_t params;
     uint32_t n_chunks = 0, n_reads = 0, post_stride = 1;

@@ -163,6 +163,152 @@ struct LanePass {
     }
 };
 
+// The polish rounds of one lane.  The sessions of a lane queue their rounds on one stream, where they run one behind the
+// other although they are independent; a round's kernels are latency-bound once few chunks are still active.  So lane-mates
+// that are in their polish phase at the same time put their rounds into ONE launch sequence (the segment-table kernels).
+//
+// A member is "in its rounds" from enter() to leave() -- the polish phase of a pass, which ends BEFORE the chain point.  At
+// every point where it would queue a round (the pass's opening, then each round) it calls arrive() and is parked.  The launch
+// is made as soon as every member that is in its rounds is parked and nobody holds the gather: whoever completes that
+// condition (the last to arrive, or a parked member woken by a mate that left) calls `launch` for all parked members in
+// arrival order, at most JTK_LANE_MAX_SEGMENTS per call and the rest in the next call; `launch` itself takes the
+// single-session path for a call of one.  Every member returns once its own launch has been made, and goes back to its own
+// bookkeeping (it stays exactly one round queued ahead, as without the gather).
+//
+// Invariants.  No timers: the only waits are on the condition variable.  A member leaves on every path out of its scope
+// (RoundPass).  A parked member waits only for members that are in their rounds and NOT parked, i.e. whose host threads are
+// running towards arrive() or leave(); such a thread waits for nothing but events of work already queued.  A member at its
+// chain point (LaneGather::arrive) has left its rounds before, so the round gather never waits for it, and the chain gather
+// waits only for members that this gather lets run: there is no wait cycle.  A hold of the chain gather therefore does not
+// stall rounds either.
+//
+// hold() / release() are an outsider's (a test's, include/jtk_lc_debug.h): while held nothing launches and arriving members
+// pend; the release launches once the condition above holds.  step() lets the members parked at that moment launch once,
+// whoever else is in its rounds, and leaves the hold in place: that is how a test puts members of different rounds into one
+// launch.  launch_calls() / recent() as LaneGather's.
+template <class Member>
+class RoundGather {
+public:
+    void enter() {
+        std::lock_guard<std::mutex> lock(m_);
+        in_rounds_++;
+    }
+    void leave() {
+        {
+            std::lock_guard<std::mutex> lock(m_);
+            in_rounds_--;
+        }
+        cv_.notify_all();  // a parked member may now be the one that launches
+    }
+    void hold() {
+        std::lock_guard<std::mutex> lock(m_);
+        holds_++;
+    }
+    bool release() {  // false: not held
+        {
+            std::lock_guard<std::mutex> lock(m_);
+            if (holds_ == 0) return false;
+            holds_--;
+        }
+        cv_.notify_all();
+        return true;
+    }
+    void step() {
+        {
+            std::lock_guard<std::mutex> lock(m_);
+            if (parked_.empty()) return;
+            step_ = true;
+        }
+        cv_.notify_all();
+    }
+    int in_rounds() {
+        std::lock_guard<std::mutex> lock(m_);
+        return in_rounds_;
+    }
+    int parked() {
+        std::lock_guard<std::mutex> lock(m_);
+        return (int)parked_.size();
+    }
+    int holds() {
+        std::lock_guard<std::mutex> lock(m_);
+        return holds_;
+    }
+    unsigned long long launch_calls() {
+        std::lock_guard<std::mutex> lock(m_);
+        return calls_;
+    }
+    int recent(int *members, int *in_rounds = nullptr, int *parked = nullptr, unsigned long long *calls = nullptr, int *holds = nullptr) {
+        std::lock_guard<std::mutex> lock(m_);
+        const int have = (int)std::min<unsigned long long>(calls_, JTK_LANE_LEDGER);
+        for (int i = 0; i < have; i++) members[i] = ring_[(calls_ - have + i) % JTK_LANE_LEDGER];
+        if (in_rounds) *in_rounds = in_rounds_;
+        if (parked) *parked = (int)parked_.size();
+        if (calls) *calls = calls_;
+        if (holds) *holds = holds_;
+        return have;
+    }
+    // launch(Member *const *members, int n) -> int, called under the gather's mutex (a lane's round launches never interleave);
+    // returns what the launch that carried `me` returned
+    template <class Launch>
+    int arrive(Member *me, Launch &&launch) {
+        std::unique_lock<std::mutex> lock(m_);
+        Ticket t;
+        t.member = me;
+        parked_.push_back(&t);
+        for (;;) {
+            if (t.launched) return t.rc;
+            if (step_ || (holds_ == 0 && (int)parked_.size() == in_rounds_)) {
+                step_ = false;
+                while (!parked_.empty()) {
+                    const size_t n = std::min<size_t>(parked_.size(), JTK_LANE_MAX_SEGMENTS);
+                    Member *group[JTK_LANE_MAX_SEGMENTS];
+                    for (size_t i = 0; i < n; i++) group[i] = parked_[i]->member;
+                    ring_[calls_++ % JTK_LANE_LEDGER] = (int)n;
+                    const int rc = launch(static_cast<Member *const *>(group), (int)n);
+                    for (size_t i = 0; i < n; i++) {
+                        parked_[i]->rc = rc;
+                        parked_[i]->launched = true;
+                    }
+                    parked_.erase(parked_.begin(), parked_.begin() + n);
+                }
+                cv_.notify_all();
+                continue;
+            }
+            cv_.wait(lock);
+        }
+    }
+
+private:
+    struct Ticket {
+        Member *member = nullptr;
+        bool launched = false;
+        int rc = 0;
+    };
+    std::mutex m_;
+    std::condition_variable cv_;
+    int in_rounds_ = 0, holds_ = 0;
+    bool step_ = false;
+    std::vector<Ticket *> parked_;   // tickets live on their members' stacks until launched
+    unsigned long long calls_ = 0;
+    int ring_[JTK_LANE_LEDGER] = {};
+};
+
+// a session's polish phase in its lane's round gather: leaves it on every path out of the scope
+template <class Member>
+struct RoundPass {
+    RoundGather<Member> *g;
+    explicit RoundPass(RoundGather<Member> *gather) : g(gather) {
+        if (g) g->enter();
+    }
+    ~RoundPass() { leave(); }
+    RoundPass(const RoundPass &) = delete;
+    RoundPass &operator=(const RoundPass &) = delete;
+    void leave() {
+        if (g) g->leave();
+        g = nullptr;
+    }
+};
+
 // The lanes of one device: made on demand, kept for the life of the process.  acquire() gives the lane with the fewest live
 // sessions among the first max_lanes (the lowest index on a tie) and makes a new one -- make(Streams &) -> bool -- only when
 // every existing one is taken and there is room.  Returns the lane's index, or -1 if `make` failed.
@@ -173,6 +319,7 @@ public:
         Streams streams{};
         int live = 0;
         LaneGather<Member> gather;
+        RoundGather<Member> rounds;
     };
     template <class Make>
     int acquire(int max_lanes, Make &&make) {

@@ -78,6 +78,22 @@ class LaneState(C.Structure):
                 ("launch_calls", C.c_uint64), ("records", LaneLaunch * DEBUG_LANE_RECORDS)]
 
 
+DEBUG_ROUND_RECORDS = 64          # JTK_LC_DEBUG_ROUND_RECORDS
+DEBUG_ROUND_OPEN = 0xffffffff     # JTK_LC_DEBUG_ROUND_OPEN
+
+
+class RoundLaunch(C.Structure):
+    """jtk_lc_debug_round_launch_t: one call of a lane's round launch"""
+    _fields_ = [("members", C.c_uint32), ("merged", C.c_uint32), ("round", C.c_uint32 * 8), ("chunks", C.c_uint32 * 8),
+                ("phmm_items", C.c_uint32 * 8)]
+
+
+class RoundState(C.Structure):
+    """jtk_lc_debug_round_state_t"""
+    _fields_ = [("in_rounds", C.c_uint32), ("holds", C.c_uint32), ("parked", C.c_uint32), ("n_records", C.c_uint32),
+                ("launch_calls", C.c_uint64), ("records", RoundLaunch * DEBUG_ROUND_RECORDS)]
+
+
 class SquishConfig(C.Structure):
     """jtk_squish_config_t; the defaults are SquishConfig::default() (squish_erroneous_clusters.rs:29-38)."""
     _fields_ = [("ari_thr", C.c_double), ("match_score", C.c_double), ("mismatch_score", C.c_double), ("count_thr", C.c_uint64)]
@@ -137,6 +153,7 @@ DEBUG_SYMBOLS = (
     "jtk_lc_debug_guided_scratch_cap", "jtk_lc_debug_guided_timing", "jtk_lc_debug_encode_timing",
     "jtk_lc_debug_guided_table", "jtk_lc_debug_gpolish_timing", "jtk_lc_debug_edges_timing",
     "jtk_lc_debug_session_lane", "jtk_lc_debug_lane_hold", "jtk_lc_debug_lane_state", "jtk_lc_debug_filter",
+    "jtk_lc_debug_round_hold", "jtk_lc_debug_round_state",
 )
 DEBUG_FILTER_TABLE, DEBUG_FILTER_ROWS_FUSED, DEBUG_FILTER_ROWS_TABLE = 0, 1, 2   # modes of jtk_lc_debug_filter
 DEBUG_FILTER_TRACE_WORDS = 66   # JTK_LC_DEBUG_FILTER_TRACE_WORDS
@@ -243,6 +260,9 @@ def lib():
     sig("jtk_lc_debug_session_lane", i32, vp)
     sig("jtk_lc_debug_lane_hold", i32, i32, i32, i32)
     sig("jtk_lc_debug_lane_state", i32, i32, i32, C.POINTER(LaneState))
+    if hasattr(L, "jtk_lc_debug_round_hold"):   # (a JTK_LC_LIB build of an earlier revision has none: scripts/build_rev.py)
+        sig("jtk_lc_debug_round_hold", i32, i32, i32, i32)
+        sig("jtk_lc_debug_round_state", i32, i32, i32, C.POINTER(RoundState))
     sig("jtk_lc_debug_filter", i32, PP, sz, vp, PU8, PU8, i32, PD, PI32, PD, PD, PU32, PU32, PU32, PD, PU32, i32)
     _lib = L
     return L
