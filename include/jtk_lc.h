@@ -668,6 +668,52 @@ JTK_LC_API int jtk_lc_encode_edges(size_t n_trials, const jtk_edge_trial_t *tria
                         jtk_edge_result_t *result, jtk_edge_node_t *nodes, uint8_t *ops_out, uint64_t *ops_out_off,
                         uint64_t ops_cap, int device);
 
+/* ---- correct_deletion's list surgery: node statistics and the settle step --------------------------------------------------
+ * What `correct_deletion_error` does to a read's nodes once the trials are in (encode/deletion_fill.rs:349-361), what
+ * `re_encode_read` (determine_chunks.rs:548-562) and dense_encoding.rs do after their own appends, and the per-node numbers
+ * `purge_large_deletion_nodes` (purge_diverged.rs:73-88) reads.  Read r's nodes are nodes[node_off[r] .. node_off[r+1]) in the
+ * order the caller holds them (new nodes appended); node e's cigar is given per base, ops[ops_off[e] .. ops_off[e+1]), Match and
+ * Mismatch both standing for a cigar Match.
+ * stats[e], for every node of every mode:
+ *   total    the ops; indel = the Ins and Del among them (remove_overlapping_encoding's identity is 1.0 - indel / total in f64)
+ *   score    (Match + Mismatch) - (Ins + Del): remove_slippy_alignment::score (encode/mod.rs:289-297)
+ *   del_size misc::max_region (misc.rs:345-358) over the run-length cigar with -l for a Match run and 2 l for an Ins or Del run,
+ *            divided by 2 toward zero (purge_diverged.rs:75-80).  On the per-base ops that is the largest sum of a non-empty
+ *            range of (-1, +2) weights where the node has an indel, and -(total) / 2 where it has none (one Match run).
+ * mode JTK_SETTLE_STATS_ONLY stops there (keep = 1, order = 0 .. n - 1, n_kept = n).  The other two run, per read:
+ *   (a) a stable sort by (chunk, position_from_start) -- JTK_SETTLE_BY_CHUNK_POS, deletion_fill.rs:354 -- or by chunk alone --
+ *       JTK_SETTLE_BY_CHUNK, determine_chunks.rs:555, encode/mod.rs:134;
+ *   (b) remove_slippy_alignment (encode/mod.rs:288-313): `prev` gives way to a node of the same chunk and direction that is not
+ *       disjoint from it (prev.position + prev.query_len < node.position is disjoint) and scores higher; a node that scores
+ *       no higher is dropped;
+ *   (c) a stable sort by position_from_start;  (d) remove_slippy_alignment again;
+ *   (e) remove_overlapping_encoding (encode/mod.rs:248-286): of the first adjacent pair in which one node strictly contains the
+ *       other (a.start <= b.start && b.end < a.end, end = start + query_len) the one of lower identity goes, the later one on
+ *       a tie, until no such pair is left.
+ * order[node_off[r] + k], k < n_kept[r]: the index inside read r of the k-th surviving node; the entries behind them are
+ * UINT32_MAX.  keep[e] = 1 for a survivor.  The caller rebuilds the read from them (encode::nodes_to_encoded_read).
+ * A read without nodes has n_kept 0 (the reference never settles one).  A read with a node that has no ops, or whose ops take a
+ * number of read bases (Match, Mismatch, Ins) other than query_len, gets read_status[r] = JTK_ERR_UNSUPPORTED, or
+ * JTK_ERR_INVALID_ARG for an op above 3: its nodes are left as they came (keep 1, order 0 .. n - 1), the other reads finish and
+ * the call returns JTK_ERR_CHUNK_FAILED.  JTK_ERR_INVALID_ARG: offsets that do not start at 0 or decrease, an unknown mode, a
+ * null pointer.  JTK_ERR_UNSUPPORTED: 2^32 - 1 nodes or more, a node of 2^31 ops or more. */
+enum jtk_settle_mode { JTK_SETTLE_STATS_ONLY = 0, JTK_SETTLE_BY_CHUNK_POS = 1, JTK_SETTLE_BY_CHUNK = 2 };
+typedef struct jtk_settle_node {
+    uint64_t chunk;                 /* Node.chunk */
+    uint64_t position_from_start;   /* Node.position_from_start */
+    uint32_t is_forward;            /* Node.is_forward */
+    uint32_t query_len;             /* Node.query_length() */
+} jtk_settle_node_t;
+typedef struct jtk_node_stats {
+    int32_t score;
+    uint32_t total;
+    uint32_t indel;
+    int64_t del_size;
+} jtk_node_stats_t;
+JTK_LC_API int jtk_lc_settle_nodes(size_t n_reads, const uint64_t *node_off, const jtk_settle_node_t *nodes, const uint8_t *ops,
+                        const uint64_t *ops_off, int mode, jtk_node_stats_t *stats, uint32_t *n_kept, uint32_t *order,
+                        uint8_t *keep, int32_t *read_status, int device);
+
 /* ---- consensus polishing that votes with banded edit distances -----------------------------------------------------------
  * What the reference gets from kiley::bialignment::guided::polish_until_converge / polish_until_converge_with:
  * `take_consensus_sequence` (encode/deletion_fill.rs:260-285, whose output is the cons_bases of jtk_lc_encode_nodes),

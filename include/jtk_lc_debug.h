@@ -45,6 +45,11 @@ JTK_LC_API int jtk_lc_debug_fill_pairs(size_t n_reads, const uint64_t *node_off,
  * the whole call on its stream in ms (upload to the last copy back) and of the pair kernels in ms. */
 JTK_LC_API void jtk_lc_debug_fill_timing(double *out);
 
+/* Of this thread's last jtk_lc_settle_nodes call, 4 doubles: the reads, the reads whose work area lay in global memory (more
+ * nodes than the LDS slot of a wave holds), the HIP-event time of the kernel in ms, and of the whole call on its stream in ms
+ * (upload to the last copy back). */
+JTK_LC_API void jtk_lc_debug_settle_timing(double *out);
+
 /* The work-area budget of jtk_lc_align_guided / jtk_lc_encode_nodes on this thread, in bytes (traceback cells and row tables
  * per slice of the batch; 0 = the default, 4 GiB): a small value makes a small batch run in several slices.  A pair that
  * alone needs more still runs, in a slice of its own. */

@@ -373,6 +373,42 @@ def purge_timing():
     return dict(upload_ms=out[0], walk_ms=out[1], device_ms=out[2], n_iter=int(out[3]))
 
 
+def settle_nodes(node_off, nodes, ops, ops_off, mode=ffi.SETTLE_BY_CHUNK_POS, device=0):
+    """jtk_lc_settle_nodes: the node statistics and, unless mode is ffi.SETTLE_STATS_ONLY, the list surgery of
+    correct_deletion_error (encode/deletion_fill.rs:349-361): a stable sort by (chunk, position) -- ffi.SETTLE_BY_CHUNK: by chunk
+    alone, as re_encode_read does -- remove_slippy_alignment, a stable sort by position, remove_slippy_alignment,
+    remove_overlapping_encoding.  nodes (ffi.SETTLE_NODE_DT) lists read r's nodes at node_off[r] .. node_off[r+1]; ops holds node
+    e's per-base cigar at ops_off[e] .. ops_off[e+1].  Returns dict(stats, keep, order, n_kept, status, rc): stats
+    (ffi.NODE_STATS_DT) and keep per node, order = per read the indices (inside the read) of its surviving nodes in their final
+    order, n_kept and status per read.  rc is 0, or -6 where a read was left as it came (status[r] != 0: a node without ops or
+    whose ops do not take query_len bases); every other failure raises."""
+    nodes = np.ascontiguousarray(nodes, dtype=ffi.SETTLE_NODE_DT)
+    node_off = np.ascontiguousarray(node_off, dtype=np.uint64)
+    ops, ops_off = np.ascontiguousarray(ops, dtype=np.uint8), np.ascontiguousarray(ops_off, dtype=np.uint64)
+    if len(node_off) == 0 or int(node_off[-1]) != len(nodes):
+        raise ValueError("node_off must hold n_reads + 1 offsets that end at len(nodes)")
+    if len(ops_off) != len(nodes) + 1 or int(ops_off[-1]) != len(ops):
+        raise ValueError("ops_off must hold one offset per node and one more, ending at len(ops)")
+    n_reads, n = len(node_off) - 1, len(nodes)
+    stats, keep = np.zeros(n + 1, dtype=ffi.NODE_STATS_DT), np.zeros(n + 1, dtype=np.uint8)
+    order, n_kept = np.zeros(n + 1, dtype=np.uint32), np.zeros(n_reads + 1, dtype=np.uint32)
+    status = np.zeros(n_reads + 1, dtype=np.int32)
+    rc = ffi.lib().jtk_lc_settle_nodes(n_reads, u64p(node_off), nodes.ctypes.data, u8p(ops), u64p(ops_off), int(mode), stats.ctypes.data,
+                                       u32p(n_kept), u32p(order), u8p(keep), status.ctypes.data_as(C.POINTER(C.c_int32)), device)
+    if rc != 0 and rc != -6:
+        check(rc)
+    per_read = [order[int(node_off[r]):int(node_off[r]) + int(n_kept[r])].copy() for r in range(n_reads)]
+    return dict(stats=stats[:n], keep=keep[:n], order=per_read, n_kept=n_kept[:n_reads], status=status[:n_reads], rc=rc)
+
+
+def settle_timing():
+    """jtk_lc_debug_settle_timing (include/jtk_lc_debug.h): reads, reads whose work area lay in global memory, kernel ms and ms
+    of the whole call on its stream, of the last settle_nodes call"""
+    out = (C.c_double * 4)()
+    ffi.lib().jtk_lc_debug_settle_timing(out)
+    return dict(n_reads=int(out[0]), n_global=int(out[1]), kernel_ms=out[2], call_ms=out[3])
+
+
 def _fill_reads(node_off, nodes):
     nodes = np.ascontiguousarray(nodes, dtype=ffi.FILL_NODE_DT)
     node_off = np.ascontiguousarray(node_off, dtype=np.uint64)

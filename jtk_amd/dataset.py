@@ -23,8 +23,10 @@ are tested against each other (tests/test_dataset_json.py)."""
 import argparse
 import ctypes as C
 import json
+import math
 import re
 import sys
+import time
 
 import numpy as np
 
@@ -426,13 +428,10 @@ def nodes_to_encoded_read(read, raw_seq):
                               "label": "" if start <= end else seq[:start][end:]})
 
 
-def purge_diverged_nodes(ds, device=0, thr=0.1):
-    """purge_diverged_nodes (purge_diverged.rs:238-322) on the parsed JSON object `ds` (modified in place):
-    jtk_lc_purge_diverged on the flattened nodes with their sequences, then the write-back -- the flagged clusters' nodes go
-    (:271-272), the other nodes of those chunks are renumbered and lose the flagged posterior entries (:311-322), reads left
-    without nodes are dropped (:283), every other read gets its gaps and edges rebuilt from its raw read (:284-290).  Returns
-    the ids of the chunks that lost a cluster, ascending: what `purge` (:42-48) hands to re_cluster, whose copy-number
-    estimation (estimate_multiplicity, :210-212) is not part of this library."""
+def _flat_nodes(ds):
+    """The data set as jtk_lc_node_errors / jtk_lc_purge_diverged take it: node_off, nodes (ffi.CC_NODE_DT), the length of the
+    flat posterior array, chunks (ffi.CC_CHUNK_DT) and the sequences (node seqs, their offsets, per-base ops, their offsets, chunk
+    seqs, their offsets)."""
     n_nodes = sum(len(r["nodes"]) for r in ds["encoded_reads"])
     nodes = np.zeros(n_nodes, dtype=ffi.CC_NODE_DT)
     node_off = np.zeros(len(ds["encoded_reads"]) + 1, dtype=np.uint64)
@@ -456,8 +455,18 @@ def purge_diverged_nodes(ds, device=0, thr=0.1):
         chunks[i] = (c["id"], c["cluster_num"], c["copy_num"], c["score"])
         tmpl_off[i + 1] = tmpl_off[i] + len(tmpls[i])
     cat = lambda parts: np.concatenate(parts) if parts else np.zeros(0, np.uint8)   # noqa: E731
-    out = api.purge_diverged(node_off, nodes, n_post, chunks, (cat(seqs), seq_off, cat(ops), ops_off, cat(tmpls), tmpl_off), thr=thr,
-                             device=device)
+    return node_off, nodes, n_post, chunks, (cat(seqs), seq_off, cat(ops), ops_off, cat(tmpls), tmpl_off)
+
+
+def purge_diverged_nodes(ds, device=0, thr=0.1):
+    """purge_diverged_nodes (purge_diverged.rs:238-322) on the parsed JSON object `ds` (modified in place):
+    jtk_lc_purge_diverged on the flattened nodes with their sequences, then the write-back -- the flagged clusters' nodes go
+    (:271-272), the other nodes of those chunks are renumbered and lose the flagged posterior entries (:311-322), reads left
+    without nodes are dropped (:283), every other read gets its gaps and edges rebuilt from its raw read (:284-290).  Returns
+    the ids of the chunks that lost a cluster, ascending: what `purge` (:42-48) hands to re_cluster, whose copy-number
+    estimation (estimate_multiplicity, :210-212) is not part of this library."""
+    node_off, nodes, n_post, chunks, seqs = _flat_nodes(ds)
+    out = api.purge_diverged(node_off, nodes, n_post, chunks, seqs, thr=thr, device=device)
     for i, c in enumerate(ds["selected_chunks"]):
         c["cluster_num"] = int(chunks["cluster_num"][i])                     # :261-265
     raw = {r["id"]: r["seq"] for r in ds["raw_reads"]}
@@ -594,9 +603,320 @@ def correct_clustering(ds, device=0, min_gain=None):
     sanity_check(ds)
 
 
+OUTER_LOOP, INNER_LOOP = 3, 12     # encode/deletion_fill.rs:137,172
+FILL_THR = 10.0                    # :369: the stddevs a trial's error rate may lie above its expectation
+TAKE_THR = 0.999                   # determine_chunks.rs:29
+MAX_ALLOWED_GAP = 100              # haplotyper/src/lib.rs:43
+OCCUPY_FRACTION = 0.5              # deletion_fill.rs:39
+ACCEPT_RATE = 0.5                  # purge_diverged.rs:63
+
+
+_stage_timing = None     # scripts/settle_timing.py sets a dict here: wall seconds per primitive are added into it
+
+
+class _Clock:
+    """the wall time of one primitive's call, added into _stage_timing where that is a dict"""
+    def __init__(self, key):
+        self.key = key
+
+    def __enter__(self):
+        self.t0 = time.perf_counter()
+
+    def __exit__(self, *exc):
+        if _stage_timing is not None:
+            _stage_timing[self.key] = _stage_timing.get(self.key, 0.0) + (time.perf_counter() - self.t0)
+
+
+def _settle_arrays(reads):
+    """api.settle_nodes' arrays for a list of node lists (JSON nodes)"""
+    node_off = np.zeros(len(reads) + 1, dtype=np.uint64)
+    flat = [n for nodes in reads for n in nodes]
+    node_off[1:] = np.cumsum([len(nodes) for nodes in reads])
+    rec = np.array([(n["chunk"], n["position_from_start"], 1 if n["is_forward"] else 0, query_length(n)) for n in flat],
+                   dtype=ffi.SETTLE_NODE_DT) if flat else np.zeros(0, dtype=ffi.SETTLE_NODE_DT)
+    ops = [cigar_to_ops(n["cigar"]) for n in flat]
+    ops_off = np.zeros(len(flat) + 1, dtype=np.uint64)
+    ops_off[1:] = np.cumsum([len(o) for o in ops])
+    return node_off, rec, (np.concatenate(ops) if ops else np.zeros(0, np.uint8)), ops_off
+
+
+def _fill_round(ds, state, consensi, read_err, chunk_err, stddev, device):
+    """One pass of filling_until's loop body (deletion_fill.rs:192-204): correct_deletion_error (:301-367) for every live read,
+    with one device call per primitive.  The reference goes through a read slot by slot, head before tail, and a slot's head
+    candidates that fail are in `failed_trials` (:325) before the same slot's tail candidates are filtered (:328): the trials of
+    every group are made and encoded at once here, and the pick then goes through the groups in that order and drops from a tail
+    group what its head group has just failed.  Returns the chunk ids of the nodes that were inserted."""
+    reads = ds["encoded_reads"]
+    raw = {r["id"]: r["seq"] for r in ds["raw_reads"]}
+    chunk_of = {c["id"]: c for c in ds["selected_chunks"]}
+    live = [r for r, read in enumerate(reads) if read["nodes"] and state[r]["alive"]]                 # :196
+    node_off = np.zeros(len(reads) + 1, dtype=np.uint64)
+    flat = []
+    for r, read in enumerate(reads):
+        flat += [(n["chunk"], n["cluster"], int(bool(n["is_forward"])), query_length(n), n["position_from_start"]) for n in read["nodes"]]
+        node_off[r + 1] = len(flat)
+    target = np.zeros(len(reads), dtype=np.uint8)
+    target[live] = 1
+    with _Clock("fill_candidates"):
+        found = api.fill_candidates(node_off, np.array(flat, dtype=ffi.FILL_NODE_DT) if flat else np.zeros(0, dtype=ffi.FILL_NODE_DT),
+                                    target=target, device=device)
+    # ---- the trials of every (read, slot, side): try_encoding_head / _tail up to encode_node (:370-446)
+    cons_at, chunk_at, read_at = {}, {}, {}              # where a sequence lies in its flat buffer: key -> (offset, length)
+    cons_parts, chunk_parts, read_parts = [], [], []
+
+    def place(table, parts, key, text):
+        if key not in table:
+            last = table[next(reversed(table))] if table else (0, 0)
+            table[key] = (last[0] + last[1], len(text))
+            parts.append(_seq(text))
+        return table[key]
+
+    def cons_len_of(chunk, cluster):
+        return len(consensi[chunk, cluster]) if chunk in chunk_of and (chunk, cluster) in consensi else None
+
+    groups, trials, keys = [], [], []   # group: (read, slot, the candidates left after the failed-trial filter, first trial, trials)
+    cand_of = []                        # per trial: its candidate's index in the group's list
+    for r in live:
+        read, nodes = reads[r], reads[r]["nodes"]
+        seq = raw[read["id"]]
+        by_slot = {}
+        for c in found["cands"][int(found["cand_off"][r]):int(found["cand_off"][r + 1])]:
+            by_slot.setdefault((int(c["slot"]), int(c["side"])), []).append(
+                (int(c["chunk"]), int(c["cluster"]), bool(c["is_forward"]), int(c["position"])))
+        for slot in range(len(nodes) + 1):
+            for side in (0, 1):                                                                      # head, then tail (:317-336)
+                left = [c for c in by_slot.get((slot, side), []) if (slot, c[:3]) not in state[r]["failed"]]   # :318, :328
+                nxt = (nodes[slot]["chunk"], nodes[slot]["position_from_start"]) if slot < len(nodes) else None
+                first = len(trials)
+                for k, start, end in api.fill_trials(side, left, len(seq), nxt, cons_len_of):
+                    chunk, cluster, forward, _ = left[k]
+                    bound = (read_err[read["id"]] + chunk_err[chunk, cluster]) + FILL_THR * stddev   # :399-400, :441-442
+                    cons_off, cons_len = place(cons_at, cons_parts, (chunk, cluster), consensi[chunk, cluster])
+                    chunk_off, chunk_len = place(chunk_at, chunk_parts, chunk, chunk_of[chunk]["seq"].upper())
+                    read_off, _ = place(read_at, read_parts, read["id"], seq)
+                    trials.append((read_off, start, end, 1 if forward else 0, cons_len, cons_off, chunk_off, chunk_len, 0, bound))
+                    keys.append((chunk, cluster))
+                    cand_of.append(k)
+                groups.append((r, slot, left, first, len(trials) - first))
+    cat = lambda parts: np.concatenate(parts) if parts else np.zeros(0, np.uint8)   # noqa: E731
+    read_bases = cat(read_parts)
+    enc = None
+    if trials:
+        with _Clock("encode_nodes"):
+            enc = api.encode_nodes(np.array(trials, dtype=ffi.ENCODE_TRIAL_DT), read_bases, cat(cons_parts), cat(chunk_parts), device=device,
+                                   raise_on_trial_failure=False)
+    # ---- the pick (:405, :445), the failed trials (:325, :335), the append (:344)
+    inserts = {r: [] for r in live}
+    for r, slot, left, first, n in groups:                 # per read in (slot, head, tail) order, as :316-337 goes
+        gone = {k for k, c in enumerate(left) if (slot, c[:3]) in state[r]["failed"]}   # failed by this slot's head group (:325, :328)
+        best = None
+        for t in range(first, first + n):
+            res = enc["result"][t]
+            if cand_of[t] in gone or int(res["status"]) != 0 or int(res["verdict"]) != ffi.ENCODE_ACCEPTED:
+                continue                                   # (a trial the device refuses is a trial that fails: encode_node's None)
+            if best is None or int(enc["result"][best]["score"]) <= int(res["score"]):
+                best = t                                   # max_by_key: of equal scores the last in candidate order
+        if best is None:
+            state[r]["failed"].update((slot, c[:3]) for k, c in enumerate(left) if k not in gone)
+            continue
+        res, trial = enc["result"][best], trials[best]
+        window = api._oriented_window(read_bases, trial[0], trial[1], trial[2], trial[3])
+        query = window[int(res["trim_head"]):len(window) - int(res["trim_tail"])]
+        chunk, cluster = keys[best]
+        k = int(chunk_of[chunk]["cluster_num"])
+        inserts[r].append({"position_from_start": int(res["position_from_start"]), "chunk": chunk, "cluster": cluster,
+                           "seq": query.decode("ascii"), "is_forward": bool(trial[3]),
+                           "cigar": ops_to_cigar(enc["ops"][int(enc["ops_off"][best]):int(enc["ops_off"][best + 1])]),
+                           "posterior": [math.log(1.0 / max(k, 1))] * k})                           # Node::new, lib.rs:723-731
+    new_ids, changed = [], []
+    for r in live:
+        state[r]["alive"] = bool(inserts[r])                                                         # :341
+        if inserts[r]:
+            state[r]["failed"].clear()                                                               # revive, :343
+            new_ids += [n["chunk"] for n in inserts[r]]
+            reads[r]["nodes"].extend(inserts[r])
+            changed.append(r)
+    # ---- the settle step (:349-361), every changed read in one call
+    if changed:
+        node_off, rec, ops, ops_off = _settle_arrays([reads[r]["nodes"] for r in changed])
+        with _Clock("settle_nodes"):
+            out = api.settle_nodes(node_off, rec, ops, ops_off, mode=ffi.SETTLE_BY_CHUNK_POS, device=device)
+        if out["rc"] != 0:
+            raise ValueError("correct_deletion: a node without ops (the reference divides 0 by 0 in remove_overlapping_encoding)")
+        for i, r in enumerate(changed):
+            reads[r]["nodes"] = [reads[r]["nodes"][int(k)] for k in out["order"][i]]
+            nodes_to_encoded_read(reads[r], raw[reads[r]["id"]])
+    return new_ids
+
+
+def correct_chunk_deletion(ds, sim_thr=None, stddev_of_error=None, device=0):
+    """correct_chunk_deletion (encode/deletion_fill.rs:136-231, 301-367) on the parsed JSON object `ds` (modified in place): up
+    to 3 x 12 rounds in which every live read gets the nodes the other reads say it lacks.  One round = jtk_lc_fill_candidates
+    on the live reads, the candidates a read has already failed taken out, the windows of try_encoding_head / _tail
+    (api.fill_trials) with sim_thr = read error + (chunk, cluster) error + 10 stddev, one jtk_lc_encode_nodes call, per (read,
+    slot, side) the accepted trial of highest score, the new nodes appended, one jtk_lc_settle_nodes call on the reads that
+    changed, and their gaps and edges rebuilt (nodes_to_encoded_read).  The consensus sequences (take_consensus_sequence) and
+    the error rates (jtk_lc_node_errors, jtk_lc_error_quantile unless sim_thr is given, jtk_lc_estimate_error_rate) are taken
+    once, before the first round.  Returns the ids of the chunks that gained a node, ascending.
+    This build's own decisions: the guided passes of encode_node and the polish behind the consensus follow DESIGN.md section 4
+    (parity with kiley is not pinned), and among trials of equal score the last in the order jtk_lc_fill_candidates returns wins,
+    where the reference takes the last in the order of its HashMap.  A read without nodes in `ds` raises ValueError: the
+    reference fails its assert_eq of :190.  A trial that jtk_lc_encode_nodes refuses (a sequence above 32,000 bases, a band row
+    above 4,096 cells) counts as a trial that failed, as encode_node's None does."""
+    reads = ds["encoded_reads"]
+    if any(not r["nodes"] for r in reads):
+        raise ValueError("correct_deletion: an encoded read without nodes (the reference's assert_eq of deletion_fill.rs:190 fails)")
+    with _Clock("take_consensus"):
+        consensi = take_consensus_sequence(ds, device=device)                                        # :139
+    node_off, nodes, _, chunks, seqs = _flat_nodes(ds)
+    with _Clock("node_errors"):
+        errs = api.node_errors(node_off, nodes, chunks, seqs, device=device)
+        fallback = float(sim_thr) if sim_thr is not None else api.error_quantile(errs["err_num"], errs["err_len"], TAKE_THR, device=device)
+    with _Clock("estimate_error_rate"):
+        fit = api.estimate_error_rate(node_off, nodes, errs["err_num"], errs["err_len"], chunks, fallback, device=device)   # :144
+    stddev = float(stddev_of_error) if stddev_of_error is not None else fit["median_of_sqrt_err"]    # :145
+    read_err = {read["id"]: float(fit["read_err"][r]) for r, read in enumerate(reads)}
+    chunk_err = {}
+    for i, c in enumerate(ds["selected_chunks"]):
+        for cl in range(int(c["cluster_num"])):
+            chunk_err[c["id"], cl] = float(fit["chunk_err"][int(fit["chunk_err_off"][i]) + cl])
+    state = [{"alive": True, "failed": set()} for _ in reads]
+    found = set()
+    for _ in range(OUTER_LOOP):
+        for st in state:                                                                             # :181
+            st["alive"] = True
+            st["failed"].clear()
+        updated = True
+        for i in range(INNER_LOOP):
+            prev = sum(len(r["nodes"]) for r in reads)
+            found.update(_fill_round(ds, state, consensi, read_err, chunk_err, stddev, device))
+            after = sum(len(r["nodes"]) for r in reads)
+            if after == prev:                                                                        # :207-211
+                updated = i != 0
+                break
+        if not updated:                                                                              # :165
+            break
+    return sorted(found)
+
+
+def _original_seq(node):
+    """Node::original_seq (definitions/src/lib.rs:737-753)"""
+    if node["is_forward"]:
+        return node["seq"]
+    try:
+        return "".join(_COMPLEMENT[b] for b in reversed(node["seq"].upper()))
+    except KeyError:
+        raise ValueError("a reverse node holds a base outside ACGT (Node::original_seq panics)") from None
+
+
+def remove_node(read, i):
+    """EncodedRead::remove (definitions/src/lib.rs:540-603): node i goes, and its bases join the gap or the edge beside it.  Not
+    nodes_to_encoded_read: nothing is taken from the raw read, and an overlap (a negative edge offset) is cut as the reference
+    cuts it."""
+    nodes, edges = read["nodes"], read["edges"]
+    if not (0 <= i < len(nodes)) or len(nodes) != len(edges) + 1:
+        raise ValueError("EncodedRead::remove: index or edge count (the reference asserts)")
+    n = len(nodes)
+    gone = nodes.pop(i)
+    if not nodes:
+        read["leading_gap"] += _original_seq(gone)
+    elif i + 1 == n:
+        edge = edges.pop(i - 1)
+        skip = -edge["offset"] if edge["offset"] < 0 else 0
+        read["trailing_gap"] = (edge["label"] + _original_seq(gone) + read["trailing_gap"])[skip:]
+    elif i == 0:
+        edge = edges.pop(0)
+        lead = read["leading_gap"] + _original_seq(gone) + edge["label"]
+        read["leading_gap"] = lead[:max(len(lead) + edge["offset"], 0)] if edge["offset"] < 0 else lead
+    else:
+        edge, before = edges.pop(i), edges[i - 1]
+        label = before["label"] + _original_seq(gone) + edge["label"]
+        if before["offset"] < 0:
+            label = label[-before["offset"]:]
+        if edge["offset"] < 0:
+            label = label[:max(len(label) + edge["offset"], 0)]
+        before["to"] = edge["to"]
+        before["label"] = label
+        before["offset"] += len(gone["seq"]) + edge["offset"]
+
+
+def _filter_indel_sizes(distr, copy_num, hap_coverage, indel_size, occupy_fraction):
+    """filter_single_copy / filter_multi_copy (purge_diverged.rs:130-187) on one key's [(read id, node index, del_size)]:
+    None where the key is dropped, else the entries that are removed.  `accept_size < size as usize` is restated: a negative
+    del_size wraps to a huge usize and passes."""
+    accept_size = int(math.ceil(indel_size * ACCEPT_RATE))
+    passes = lambda size: size < 0 or accept_size < size   # noqa: E731
+    if copy_num <= 1:
+        num = sum(indel_size < d[2] for d in distr)
+        upper_thr = int(math.ceil(len(distr) * (1.0 - occupy_fraction / 2.0)))
+        if not 1 <= num < upper_thr:
+            return None
+        return [d for d in distr if passes(d[2])]
+    lower_thr = max(int(math.floor(hap_coverage * occupy_fraction)), 0)
+    upper_thr = int(math.ceil(max(float(len(distr)) - float(lower_thr), 0.0)))
+    min_remove = sum(indel_size < d[2] for d in distr)
+    max_remove = sum(accept_size < d[2] for d in distr)
+    if not (lower_thr < min_remove and max_remove < upper_thr):
+        return None
+    # (the reference's sum / max_remove of :179 cannot divide by zero here: accept_size <= indel_size, so max_remove >= min_remove
+    # > lower_thr >= 0)
+    return [d for d in distr if passes(d[2])]
+
+
+def purge_largeindel(ds, indel_size, occupy_fraction, compress, device=0):
+    """PurgeDivergent::purge_largeindel (purge_diverged.rs:49-187) on the parsed JSON object `ds` (modified in place).  del_size
+    of every node comes from jtk_lc_settle_nodes in mode STATS_ONLY; the nodes are grouped by (chunk, cluster) -- by chunk where
+    `compress` -- the coverage is updated (misc::update_coverage), filter_single_copy / filter_multi_copy decide per group by the
+    chunk's copy number, the nodes they name are taken out with EncodedRead::remove (remove_node) from the highest index of a read
+    down, and reads left without nodes are dropped.  Returns the chunk ids of the groups that passed, ascending."""
+    reads = ds["encoded_reads"]
+    copy_num = {c["id"]: int(c["copy_num"]) for c in ds["selected_chunks"]}
+    node_off, rec, ops, ops_off = _settle_arrays([r["nodes"] for r in reads])
+    with _Clock("settle_nodes"):
+        out = api.settle_nodes(node_off, rec, ops, ops_off, mode=ffi.SETTLE_STATS_ONLY, device=device)
+    distr = {}
+    e = 0
+    for r, read in enumerate(reads):
+        for idx, node in enumerate(read["nodes"]):
+            if not node["cigar"]:
+                raise ValueError("purge_largeindel: a node without ops (max_region of nothing is i64::MIN)")
+            key = (node["chunk"], 0 if compress else node["cluster"])
+            distr.setdefault(key, []).append((r, idx, int(out["stats"]["del_size"][e])))
+            e += 1
+    update_coverage(ds)                                                                              # :91
+    hap_coverage = coverage_of(ds)[1]
+    buckets, purged = {}, set()
+    for (chunk, cluster), entries in distr.items():
+        if chunk not in copy_num:
+            raise ValueError(f"purge_largeindel: a node of chunk {chunk}, which is not selected (copy_num[&chunk] panics)")
+        removed = _filter_indel_sizes(entries, copy_num[chunk], hap_coverage, indel_size, occupy_fraction)
+        if removed is None:
+            continue
+        purged.add(chunk)
+        for r, idx, _ in removed:
+            buckets.setdefault(r, []).append(idx)
+    for r, idxs in buckets.items():
+        for idx in sorted(idxs, reverse=True):                                                       # :111
+            remove_node(reads[r], idx)
+    ds["encoded_reads"] = [r for r in reads if r["nodes"]]                                           # :52
+    return sorted(purged)
+
+
+def correct_deletion(ds, re_clustering=False, sim_thr=None, stddev_of_error=None, device=0):
+    """CorrectDeletion::correct_deletion (encode/deletion_fill.rs:36-90) on the parsed JSON object `ds` (modified in place):
+    correct_chunk_deletion, then purge_largeindel(MAX_ALLOWED_GAP, 0.5) by (chunk, cluster) and once more by chunk.  Returns the
+    ids of the chunks that gained a node or had a group purged, ascending -- the reference's find_new_chunks."""
+    if re_clustering:
+        raise NotImplementedError("re_clustering=True needs estimate_multiplicity, which is another subsystem")
+    found = set(correct_chunk_deletion(ds, sim_thr=sim_thr, stddev_of_error=stddev_of_error, device=device))
+    found.update(purge_largeindel(ds, MAX_ALLOWED_GAP, OCCUPY_FRACTION, False, device=device))
+    found.update(purge_largeindel(ds, MAX_ALLOWED_GAP, OCCUPY_FRACTION, True, device=device))
+    return sorted(found)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--stage", default="local_clustering", choices=("local_clustering", "correct_clustering", "squish_erroneous_clusters", "corrected", "realign", "purge_diverged_nodes", "fill_candidates", "consensus_sequences"),
+    ap.add_argument("--stage", default="local_clustering", choices=("local_clustering", "correct_clustering", "squish_erroneous_clusters", "corrected", "realign", "purge_diverged_nodes", "fill_candidates", "consensus_sequences", "correct_deletion"),
                     help="which JTK stage to run on the file (jtk local_clustering / jtk correct_clustering); "
                          "squish_erroneous_clusters: the step JTK runs in front of the correction, with its default "
                          "configuration; corrected: that step, then correct_clustering (cli/src/pipeline.rs:174-175); realign: "
@@ -606,7 +926,9 @@ def main(argv=None):
                          "keyed by read id with coverage, ins_thr and the head / tail candidates, not a DataSet: testing a "
                          "candidate against the sequence (encode_node, kiley's infix_guided) is JTK's; consensus_sequences: "
                          "take_consensus_sequence (deletion_fill.rs:260-285) -- also a REPORT, {\"chunk,cluster\": \"ACGT...\"}, made with "
-                         "this build's guided polish (parity with kiley's polish_until_converge is not pinned)")
+                         "this build's guided polish (parity with kiley's polish_until_converge is not pinned); correct_deletion: "
+                         "`ds.correct_deletion` without re-clustering (deletion_fill.rs:36-44: the filling rounds, then purge_largeindel "
+                         "twice), the chunk ids that changed go to stderr; the guided passes and the polish are this build's own")
     ap.add_argument("input", help="DataSet JSON ('-' = stdin)")
     ap.add_argument("output", help="DataSet JSON ('-' = stdout)")
     ap.add_argument("--chunks", default="", help="comma-separated chunk ids (local_clustering_selected); default: all")
@@ -640,6 +962,10 @@ def main(argv=None):
         sys.stderr.write("PD\tPurged\t%s\n" % ",".join(str(x) for x in purged))
         if args.recluster and purged:
             local_clustering_selected(ds, purged, device=args.device, failed=failed, refit=not args.no_refit, record=record, trace=trace)
+    elif args.stage == "correct_deletion":
+        validate(ds)
+        changed = correct_deletion(ds, device=args.device)
+        sys.stderr.write("CD\tChanged\t%s\n" % ",".join(str(x) for x in changed))
     elif args.stage == "fill_candidates":
         ds = fill_candidates(ds, device=args.device)   # the report takes the data set's place in the output
     elif args.stage == "consensus_sequences":

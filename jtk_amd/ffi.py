@@ -137,11 +137,17 @@ EDGE_NODE_DT = np.dtype([("verdict", "<u4"), ("mat_num", "<u4"), ("ops_len", "<u
 EDGE_ACCEPTED, EDGE_REJECTED, EDGE_NOT_REACHED = 0, 2, 3   # enum jtk_edge_verdict
 GUIDED_MAX_WIDTH = 4096    # JTK_GUIDED_MAX_WIDTH
 ENCODE_ACCEPTED, ENCODE_LOWER_BOUND, ENCODE_REJECTED = 0, 1, 2   # enum jtk_encode_verdict
+# jtk_settle_node_t / jtk_node_stats_t (jtk_lc_settle_nodes); the C struct pads del_size to offset 16
+SETTLE_NODE_DT = np.dtype([("chunk", "<u8"), ("position_from_start", "<u8"), ("is_forward", "<u4"), ("query_len", "<u4")])
+NODE_STATS_DT = np.dtype({"names": ["score", "total", "indel", "del_size"], "formats": ["<i4", "<u4", "<u4", "<i8"],
+                          "offsets": [0, 4, 8, 16], "itemsize": 24})
+SETTLE_STATS_ONLY, SETTLE_BY_CHUNK_POS, SETTLE_BY_CHUNK = 0, 1, 2   # enum jtk_settle_mode
+SETTLE_DROPPED = 0xffffffff   # order[] behind a read's survivors
 
 # every symbol declared in include/jtk_lc.h (tests check the library exports them)
 EXPORTED_SYMBOLS = (
     "jtk_lc_cluster_chunks", "jtk_lc_cluster_chunks_multi", "jtk_lc_cluster_polished", "jtk_lc_polish_chunks", "jtk_lc_align_reads", "jtk_lc_align_reads_mode", "jtk_lc_modification_table",
-    "jtk_lc_cluster_features", "jtk_lc_estimate_gains", "jtk_lc_estimate_minimum_gain", "jtk_lc_fit_model", "jtk_lc_correct_clustering", "jtk_lc_squish_clusters", "jtk_lc_squish_classify", "jtk_lc_node_errors", "jtk_lc_error_quantile", "jtk_lc_estimate_error_rate", "jtk_lc_purge_diverged", "jtk_lc_fill_candidates", "jtk_lc_align_guided", "jtk_lc_polish_guided", "jtk_lc_encode_nodes", "jtk_lc_encode_edges", "jtk_lc_trim_cache", "jtk_lc_pileup_sort_key", "jtk_lc_normalize_pileup", "jtk_lc_strerror",
+    "jtk_lc_cluster_features", "jtk_lc_estimate_gains", "jtk_lc_estimate_minimum_gain", "jtk_lc_fit_model", "jtk_lc_correct_clustering", "jtk_lc_squish_clusters", "jtk_lc_squish_classify", "jtk_lc_node_errors", "jtk_lc_error_quantile", "jtk_lc_estimate_error_rate", "jtk_lc_purge_diverged", "jtk_lc_settle_nodes", "jtk_lc_fill_candidates", "jtk_lc_align_guided", "jtk_lc_polish_guided", "jtk_lc_encode_nodes", "jtk_lc_encode_edges", "jtk_lc_trim_cache", "jtk_lc_pileup_sort_key", "jtk_lc_normalize_pileup", "jtk_lc_strerror",
     "jtk_lc_last_error", "jtk_lc_version", "jtk_lc_device_ok", "jtk_lc_last_timing",
     "jtk_lc_session_create", "jtk_lc_session_run", "jtk_lc_session_fetch", "jtk_lc_session_destroy", "jtk_lc_session_trace",
 )
@@ -153,7 +159,7 @@ DEBUG_SYMBOLS = (
     "jtk_lc_debug_guided_scratch_cap", "jtk_lc_debug_guided_timing", "jtk_lc_debug_encode_timing",
     "jtk_lc_debug_guided_table", "jtk_lc_debug_gpolish_timing", "jtk_lc_debug_edges_timing",
     "jtk_lc_debug_session_lane", "jtk_lc_debug_lane_hold", "jtk_lc_debug_lane_state", "jtk_lc_debug_filter",
-    "jtk_lc_debug_round_hold", "jtk_lc_debug_round_state",
+    "jtk_lc_debug_round_hold", "jtk_lc_debug_round_state", "jtk_lc_debug_settle_timing",
 )
 DEBUG_FILTER_TABLE, DEBUG_FILTER_ROWS_FUSED, DEBUG_FILTER_ROWS_TABLE = 0, 1, 2   # modes of jtk_lc_debug_filter
 DEBUG_FILTER_TRACE_WORDS = 66   # JTK_LC_DEBUG_FILTER_TRACE_WORDS
@@ -225,6 +231,8 @@ def lib():
     sig("jtk_lc_estimate_error_rate", i32, sz, PU64, vp, PU32, PU32, sz, vp, C.c_double, PD, PD, PU64, sz, PD, PU32, i32)
     sig("jtk_lc_purge_diverged", i32, sz, PU64, vp, sz, sz, vp, PU8, PU64, PU8, PU64, PU8, PU64, C.c_double, PU8, PU64, sz, PU8, PU64,
         PU8, PU8, PU64, sz, PSZ, PD, PD, PD, i32)
+    sig("jtk_lc_settle_nodes", i32, sz, PU64, vp, PU8, PU64, i32, vp, PU32, PU32, PU8, PI32, i32)
+    sig("jtk_lc_debug_settle_timing", None, PD)
     sig("jtk_lc_fill_candidates", i32, sz, PU64, vp, PU8, PU32, PU32, PU64, vp, sz, PSZ, i32)
     sig("jtk_lc_debug_fill_pairs", i32, sz, PU64, vp, sz, PU32, PU32, PI32, PI32, PU8, PU64, PU32, sz, PSZ, i32)
     sig("jtk_lc_debug_fill_timing", None, PD)

@@ -59,6 +59,19 @@ pub struct JtkFillCand {
     pub read: u32, pub slot: u32, pub side: u32, pub is_forward: u32, pub chunk: u64, pub cluster: u64,
     pub count: u32, pub reserved: u32, pub position: i64,
 }
+// what the settle step reads of a Node (encode/deletion_fill.rs:349-361, encode/mod.rs:248-313), and the numbers it and
+// purge_large_deletion_nodes (purge_diverged.rs:75-80) take from a node's cigar
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct JtkSettleNode {
+    pub chunk: u64, pub position_from_start: u64, pub is_forward: u32, pub query_len: u32,
+}
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct JtkNodeStats {
+    pub score: i32, pub total: u32, pub indel: u32, pub del_size: i64,
+}
+pub const JTK_SETTLE_STATS_ONLY: c_int = 0;
+pub const JTK_SETTLE_BY_CHUNK_POS: c_int = 1;
+pub const JTK_SETTLE_BY_CHUNK: c_int = 2;
 // one pair of jtk_lc_align_guided: offsets into two base buffers and one op buffer, so that pairs can share a sequence
 #[repr(C)] #[derive(Clone, Copy, Default)]
 pub struct JtkGuidedPair {
@@ -178,6 +191,13 @@ extern "C" {
         thr: f64, diverged: *mut u8, chunk_err_off: *mut u64, slot_cap: usize, keep: *mut u8, cluster_out: *mut u64,
         touched: *mut u8, post_keep: *mut u8, purged: *mut u64, purged_cap: usize, n_purged: *mut usize,
         read_err: *mut f64, chunk_err: *mut f64, median_of_sqrt_err: *mut f64, device: c_int) -> c_int;
+    // the node statistics (remove_slippy_alignment::score, the identity of remove_overlapping_encoding, del_size of
+    // purge_diverged.rs:75-80) and, unless mode is JTK_SETTLE_STATS_ONLY, the list surgery of encode/deletion_fill.rs:349-361 per read;
+    // order[node_off[r] ..][.. n_kept[r]] = the surviving nodes' indices inside read r in their final order
+    pub fn jtk_lc_settle_nodes(
+        n_reads: usize, node_off: *const u64, nodes: *const JtkSettleNode, ops: *const u8, ops_off: *const u64, mode: c_int,
+        stats: *mut JtkNodeStats, n_kept: *mut u32, order: *mut u32, keep: *mut u8, read_status: *mut i32,
+        device: c_int) -> c_int;
     // get_pileup, ins_thr and check_insertion_head / _tail of correct_deletion_error (encode/deletion_fill.rs:301-337, 642-698,
     // 883-981) for every read with target[r] == 1 (null: every read); cands sorted by (read, slot, side, chunk, cluster, is_forward)
     pub fn jtk_lc_fill_candidates(

@@ -194,6 +194,43 @@ pub(crate) fn fill_candidates_gpu(reads: &[definitions::EncodedRead], alive: &[b
         .map(|c| (c.slot as usize, c.side, (c.chunk, c.cluster, c.is_forward == 1), c.position as isize)).collect()).collect()
 }
 
+/// The list surgery at the end of `correct_deletion_error` (encode/deletion_fill.rs:349-361) for every read of a round that
+/// gained a node, in one call: `reads[k]` holds the read's nodes with the new ones appended (:344).  mode =
+/// JTK_SETTLE_BY_CHUNK_POS is that function's sort, JTK_SETTLE_BY_CHUNK the one of `re_encode_read`
+/// (determine_chunks.rs:555) and encode_read_to_nodes_by_paf (encode/mod.rs:134), JTK_SETTLE_STATS_ONLY only fills the
+/// statistics -- `del_size` is what purge_large_deletion_nodes (purge_diverged.rs:75-80) computes per node.  Returns per read
+/// the indices of the nodes that survive the sort, remove_slippy_alignment, the sort by position, remove_slippy_alignment and
+/// remove_overlapping_encoding, in their final order, and per node its statistics; the caller moves the nodes and calls
+/// nodes_to_encoded_read (:361).
+pub(crate) fn settle_gpu(reads: &[&[definitions::Node]], mode: std::os::raw::c_int) -> (Vec<Vec<usize>>, Vec<JtkNodeStats>) {
+    let (mut node_off, mut nodes, mut ops, mut ops_off) = (vec![0u64], vec![], Vec::<u8>::new(), vec![0u64]);
+    for read in reads.iter() {
+        for n in read.iter() {
+            nodes.push(JtkSettleNode { chunk: n.chunk, position_from_start: n.position_from_start as u64,
+                is_forward: n.is_forward as u32, query_len: n.query_length() as u32 });
+            for op in n.cigar.iter() {       // per base: Match 0, Ins 2, Del 3 (a cigar Match covers mismatches)
+                let (code, len) = match *op {
+                    definitions::Op::Match(l) => (0u8, l),
+                    definitions::Op::Ins(l) => (2u8, l),
+                    definitions::Op::Del(l) => (3u8, l),
+                };
+                ops.extend(std::iter::repeat(code).take(len));
+            }
+            ops_off.push(ops.len() as u64);
+        }
+        node_off.push(nodes.len() as u64);
+    }
+    let (mut stats, mut n_kept) = (vec![JtkNodeStats::default(); nodes.len()], vec![0u32; reads.len()]);
+    let (mut order, mut keep, mut status) = (vec![0u32; nodes.len()], vec![0u8; nodes.len()], vec![0i32; reads.len()]);
+    let rc = unsafe { jtk_lc_settle_nodes(reads.len(), node_off.as_ptr(), nodes.as_ptr(), ops.as_ptr(), ops_off.as_ptr(), mode,
+        stats.as_mut_ptr(), n_kept.as_mut_ptr(), order.as_mut_ptr(), keep.as_mut_ptr(), status.as_mut_ptr(), /*device*/ 0) };
+    // -6: a node without ops -- remove_overlapping_encoding would divide 0 by 0 there
+    assert!(rc == 0, "{}", unsafe { std::ffi::CStr::from_ptr(jtk_lc_last_error()) }.to_string_lossy());
+    let kept = (0..reads.len()).map(|r| { let b = node_off[r] as usize;
+        order[b..b + n_kept[r] as usize].iter().map(|&i| i as usize).collect() }).collect();
+    (kept, stats)
+}
+
 /// `take_consensus_sequence` (encode/deletion_fill.rs:260-285) in one call: the nodes are bucketed by (chunk, cluster) in
 /// encoded_reads order, cluster 0 stands for the chunk's own sequence, and every other bucket is polished from the chunk's
 /// sequence: the global ops of jtk_lc_align_reads, then jtk_lc_polish_guided with radius = read_type.band_width(len) (:277).
