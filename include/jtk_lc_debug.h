@@ -143,10 +143,10 @@ JTK_LC_API int jtk_lc_debug_lane_state(int device, int lane, jtk_lc_debug_lane_s
  * stall chains of sessions that have left their polish phase.
  *
  * jtk_lc_debug_round_state: in_rounds = sessions in their polish phase, parked = those waiting for a launch, holds, launch_calls
- * = round launches the lane has made (a single-session one counts), and the n_records most recent, oldest first.  A record is
- * read back from the segment table the kernels were given: members = its segments (1 and merged = 0: the single-session
- * kernels ran), and per member round[i] (JTK_LC_DEBUG_ROUND_OPEN: the opening), chunks[i], and phmm_items[i], its reads in
- * phmm_kernel's merged item space (0 at the opening). */
+ * = round launches the lane has made (one that carried a single session counts), and the n_records most recent, oldest first.  A record is
+ * read back from the segment table the kernels were given: members = its segments (1 and merged = 0: a session on its own,
+ * a table of one), and per member round[i] (JTK_LC_DEBUG_ROUND_OPEN: the opening), chunks[i], and phmm_items[i], its reads in
+ * phmm_kernel's item space (0 at the opening). */
 #define JTK_LC_DEBUG_ROUND_RECORDS 64
 #define JTK_LC_DEBUG_ROUND_OPEN 0xffffffffu
 typedef struct jtk_lc_debug_round_launch {

@@ -89,7 +89,6 @@ def build_experiment(name, extra_flags):
 PROFILED_SOURCES = ["phmm_kernels.hip", "phmm_sweep.hip", "phmm_pair.hip", "phmm_wide.hip", "polish_kernels.hip", "filter_kernels.hip", "mcmc_kernels.hip",
                     "session.hip", "session_split.hip", "session_stages.hip", "session_refit.hip", "session_features.hip", "session_trace.hip",
                     "io_kernels.hip", "device_common.h", "batch_types.h", "host_common.h", "session_internal.h", "session_plan.h", "session_lanes.h", "finalize_common.h",
-                    "band_prep_body.h", "sum_final_body.h", "rethread_body.h", "phmm_item_body.h",
                     # the parts of mcmc_kernels.hip
                     "chain_stats.h", "chain_layout.h", "chain_rng.h", "chain_lds.h", "chain_common.h", "chain_producer.h",
                     "chain_jump_table.h", "chain_generic.h", "chain_tab.h", "chain_k2.h"]

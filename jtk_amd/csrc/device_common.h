@@ -9,11 +9,9 @@
 
 // ---- kernel launchers (definitions in the .hip files) ----
 size_t phmm_lds_bytes(uint32_t max_tmpl, uint32_t max_read);
-void launch_band_prep(hipStream_t s, uint32_t n_reads, const ReadMeta *reads, const ChunkMeta *chunks,
-                      ChunkState *state, DevBufs bufs, uint64_t *delta, int only_active, uint32_t max_tmpl, uint32_t max_read);
-// Work queues: `work_counter` is a device ticket counter that is never reset (no fill blit in front of a launch).  A wave
-// takes tickets until one is past the launch's last item, so a launch advances the counter by exactly n_items + n_waves;
-// `ticket_base` (host, owned by the session) is the counter's value when the launch starts and is advanced by the launcher.
+// Work queues (phmm, phmm_pair, phmm_wide, phmm_counts): `work_counter` is a device ticket counter that is never reset (no fill
+// blit in front of a launch).  A wave takes tickets until one is past the launch's last item, so a launch advances the counter
+// by exactly n_items + n_waves; `ticket_base` (host) is the counter's value when the launch starts and is advanced by the launcher.
 // The forward scratch of the lane-ring pair-HMM kernels: stripes of (template + read + guard) x 1 KiB, one per RESIDENT wave.
 // The set is shared by every session of a device (session_internal.h: StripePool): however many batches are in flight, no more
 // waves than the device holds are ever inside a sweep, so a wave takes a free stripe when it starts and gives it back when it
@@ -51,11 +49,6 @@ __device__ __forceinline__ void jtk_stripe_release(const StripeSet &ss, uint32_t
     if (threadIdx.x == 0) __hip_atomic_store(&ss.owner[stripe], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 #endif
-void launch_phmm(hipStream_t s, uint32_t n_reads, const ReadMeta *reads, const ChunkMeta *chunks,
-                 const ChunkState *state, DevBufs bufs, const uint8_t *ey, const uint64_t *delta,
-                 const HmmDev *hmm2, StripeSet stripes, uint32_t n_waves,
-                 uint32_t *work_counter, uint32_t *ticket_base, double *raw, int *rawG, double *lk, uint32_t max_tmpl,
-                 uint32_t max_read, int only_active, uint32_t skip_le_radius = 0);
 // phmm_pair.hip: the same sweep for band radius <= JTK_PAIR_MAX_RADIUS, two reads of a chunk per wave.  items[q] = index of
 // the first read of the pair, bit 31 set when the item is a single read; phmm_kernel is then told to skip those chunks.
 size_t phmm_pair_lds_bytes(uint32_t max_tmpl, uint32_t max_read);
@@ -68,9 +61,6 @@ void launch_finalize(hipStream_t s, uint32_t n_reads, const ReadMeta *reads, con
                      uint32_t max_tmpl, int only_active, int converged_in = -1);  // in place: a read's table takes the place of
                                                                                    // its row sums; converged_in >= 0: only the
                                                                                    // chunks that converged in that polish round
-// the column totals of a polish round straight from the row sums (finalize's arithmetic + sum_tables' sum, no table written)
-void launch_sum_final(hipStream_t s, uint32_t n_chunks, const ReadMeta *reads, const ChunkMeta *chunks, const ChunkState *state,
-                      const HmmDev *hmm2, const double *raw, const int *rawG, const double *lk, double *total, uint32_t max_tmpl);
 // phmm_wide.hip: the reads of chunks whose band radius exceeds JTK_MAX_RADIUS (phmm_kernel skips them)
 size_t phmm_wide_lds_bytes(uint32_t max_tmpl, uint32_t max_read, uint32_t max_radius);
 uint64_t phmm_wide_scratch_doubles(uint32_t max_tmpl, uint32_t max_read, uint32_t max_radius);
@@ -98,20 +88,14 @@ void launch_gather(hipStream_t s, uint32_t n_reads, uint32_t n_chunks, const Rea
                    uint8_t *ops_out, uint8_t *cons_out);
 // polish_kernels.hip
 #define JTK_NACTIVE_SLOTS (JTK_POLISH_MAX_ROUNDS + 3)  // one "chunks still active" counter per polish round of a pass
-void launch_reset_pass(hipStream_t s, uint32_t n_chunks, ChunkState *state, const ChunkState *state0, uint32_t *n_active,
-                       uint32_t n_counters);
-void launch_polish_round(hipStream_t s, uint32_t n_chunks, uint32_t n_reads, const ReadMeta *reads,
-                         const ChunkMeta *chunks, ChunkState *state, DevBufs bufs, const uint8_t *ey,
-                         const double *table, double *total, Edit *edits, uint32_t *new_len, uint32_t max_tmpl,
-                         uint32_t ignore_edge, int final_pass, uint32_t *n_active_out, uint32_t *n_active_host);
-                         // (`total` holds the round's column totals: launch_sum_final)
-// The polish rounds of several sessions in one launch per kernel (the sessions of a lane, session_lanes.h: RoundGather).  A
+// The kernels of a polish round take the rounds of up to JTK_ROUND_MAX_SEGMENTS sessions in one launch (the sessions of a
+// lane, session_lanes.h: RoundGather); a session on its own is a table of one segment -- there is one kernel per step.  A
 // segment is one session's round: its pointers, its own flags, and which step of its pass it is at -- the opening (`open`:
 // reset_pass + band_prep of every read) or polish round `round` (phmm, sum_final, select_edits, rethread, commit, band_prep
-// of the active chunks; a final pass ends after select_edits).  Lane-mates need not be at the same step.  Every merged kernel
-// takes the table by value plus its own prefix of first blocks / items (a segment that has no part in the kernel has no
-// width), finds its segment by a scalar scan of the prefix and runs the single-session kernel's body on that segment's
-// pointers with a rebased index: the same arithmetic on the same buffers in the same order.  Nothing waits for anything.
+// of the active chunks; a final pass ends after select_edits).  Lane-mates need not be at the same step.  Every kernel takes
+// the table by value plus its own prefix of first blocks / items (a segment that has no part in the kernel has no width),
+// finds its segment by a scalar scan of the prefix and works on that segment's pointers with a rebased index: for every
+// session the same arithmetic on the same buffers in the same order, whoever shares the launch.  Nothing waits for anything.
 #define JTK_ROUND_MAX_SEGMENTS 8
 struct RoundSegment {
     uint32_t n_chunks, n_reads;
@@ -140,14 +124,14 @@ struct RoundSegTable {
     RoundSegment seg[JTK_ROUND_MAX_SEGMENTS];
     uint32_t n;
 };
-// what a merged launch carried, read back from the tables the kernels were given (the lane's round ledger)
+// what a launch carried, read back from the table the kernels were given (the lane's round ledger)
 struct RoundLaunchInfo {
     uint32_t segments;                           // of the table
     uint32_t round[JTK_ROUND_MAX_SEGMENTS];      // 0xffffffff: the opening
     uint32_t chunks[JTK_ROUND_MAX_SEGMENTS];
     uint32_t phmm_items[JTK_ROUND_MAX_SEGMENTS]; // the segment's width in phmm_kernel's item space
 };
-// a merged kernel's own prefix: first[i] = the first block (or item) of segment i, first[JTK_ROUND_MAX_SEGMENTS] = their number;
+// a kernel's own prefix: first[i] = the first block (or item) of segment i, first[JTK_ROUND_MAX_SEGMENTS] = their number;
 // entries past the table's last segment hold that number too, so the scan needs no segment count
 struct RoundFirst {
     uint32_t first[JTK_ROUND_MAX_SEGMENTS + 1];
@@ -173,14 +157,16 @@ __device__ __forceinline__ uint32_t round_segment_of(const RoundFirst &f, uint32
 }
 #endif
 void round_table_info(const RoundSegTable &t, RoundLaunchInfo *info);
-void launch_reset_pass_merged(hipStream_t s, const RoundSegTable &t);
-void launch_band_prep_merged(hipStream_t s, const RoundSegTable &t);
-// `work_counter` / `ticket_base`: the LANE's never-reset ticket counter and its host mirror; `stripes`: a set whose stripes are
-// long enough for every segment; n_waves: of the largest segment (at most the set's stripes)
-void launch_phmm_merged(hipStream_t s, const RoundSegTable &t, StripeSet stripes, uint32_t n_waves, uint32_t *work_counter,
-                        uint32_t *ticket_base, RoundLaunchInfo *info);
-void launch_sum_final_merged(hipStream_t s, const RoundSegTable &t);
-void launch_polish_round_merged(hipStream_t s, const RoundSegTable &t);
+void launch_reset_pass(hipStream_t s, const RoundSegTable &t);
+void launch_band_prep(hipStream_t s, const RoundSegTable &t);
+// `work_counter` / `ticket_base`: a never-reset ticket counter and its host mirror (above) -- the lane's for a launch through
+// the lane's gather, the session's own otherwise; `stripes`: a set whose stripes are long enough for every segment; n_waves: of
+// the largest segment (at most the set's stripes)
+void launch_phmm(hipStream_t s, const RoundSegTable &t, StripeSet stripes, uint32_t n_waves, uint32_t *work_counter,
+                 uint32_t *ticket_base);
+// the column totals of a polish round straight from the row sums (finalize's arithmetic + the ordered sum, no table written)
+void launch_sum_final(hipStream_t s, const RoundSegTable &t);
+void launch_polish_round(hipStream_t s, const RoundSegTable &t);  // select_edits, rethread, commit (after launch_sum_final)
 // filter_kernels.hip: the variant search of a clustering pass, and one chunk's pick once more with its trace arrays
 void launch_filter(hipStream_t s, uint32_t n_chunks, const ReadMeta *reads, const ChunkMeta *chunks,
                    ChunkState *state, DevBufs bufs, const jtk_lc_params_t *params, const double *table,

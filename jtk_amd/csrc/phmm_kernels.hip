@@ -76,30 +76,89 @@ __device__ __forceinline__ int delta_bit(const uint64_t *delta, int t) {  // c[t
 // satisfies the condition (the set is one interval, see below), a min / max over the lanes.
 // ------------------------------------------------------------------------------------------------------
 #define BP_WAVES 4
-__global__ __launch_bounds__(64 * BP_WAVES) void band_prep_kernel(uint32_t n_reads, const ReadMeta *reads, const ChunkMeta *chunks,
-                                                                 ChunkState *state, DevBufs bufs, uint64_t *delta, int only_active,
-                                                                 uint32_t max_words) {
-#define JTK_BODY_BLOCK blockIdx.x
-#include "band_prep_body.h"
-#undef JTK_BODY_BLOCK
-}
+// A launch carries up to JTK_ROUND_MAX_SEGMENTS sessions (device_common.h: RoundSegTable; a lone session is a table of one):
 // the opening's band_prep (every read) of the segments at their opening, a round's (the active chunks' reads) of the others;
 // max_words: the LDS words per wave, of the longest read of any segment
-__global__ __launch_bounds__(64 * BP_WAVES) void band_prep_merged_kernel(const RoundSegTable t, const RoundFirst f, uint32_t max_words) {
+__global__ __launch_bounds__(64 * BP_WAVES) void band_prep_kernel(const RoundSegTable t, const RoundFirst f, uint32_t max_words) {
     const uint32_t i = round_segment_of(f, blockIdx.x);
     const RoundSegment &g = t.seg[i];
-    const uint32_t bid = blockIdx.x - f.first[i], n_reads = g.n_reads;
+    const uint32_t bid = blockIdx.x - f.first[i], n_reads = g.n_reads;  // bid: the workgroup's index among the session's
     const ReadMeta *reads = g.reads;
     const ChunkMeta *chunks = g.chunks;
     ChunkState *state = g.state;
     const DevBufs &bufs = g.bufs;
     uint64_t *delta = g.delta;
     const int only_active = g.open ? 0 : 1;
-#define JTK_BODY_BLOCK bid
-#include "band_prep_body.h"
-#undef JTK_BODY_BLOCK
+    extern __shared__ __align__(8) unsigned char bp_smem[];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t r = bid * BP_WAVES + wave;
+    if (r >= n_reads) return;
+    const ReadMeta rm = reads[r];
+    ChunkState *st = &state[rm.chunk];
+    if (st->status != 0) return;
+    if (only_active && !st->active) return;
+    unsigned long long *sd = reinterpret_cast<unsigned long long *>(bp_smem) + (size_t)wave * max_words;
+    const uint32_t L = st->tmpl_len, n = rm.read_len, T = L + n;
+    const uint8_t *ops = bufs.ops[st->buf] + rm.ops_off;
+    const uint32_t n_ops = bufs.ops_len[st->buf][r];
+    uint64_t *d = delta + rm.delta_off;
+    const uint32_t words = (T >> 6) + 2;
+    for (uint32_t w = lane; w < words; w += 64) sd[w] = 0ull;
+    // the interval [f_lo, f_hi] of diagonals whose WHOLE band lies inside the DP matrix (0 <= i <= L, 0 <= j <= n for every
+    // band cell): c - r >= 0, c + r <= L, c + r <= t, c - r >= t - n.  c and t - c are non-decreasing in t, so the set is one
+    // interval; phmm_kernel runs it under an EXEC mask that is the band and takes per-lane predicates outside of it.
+    const int32_t rad = (int32_t)chunks[rm.chunk].radius;
+    uint32_t f_lo = 0xffffffffu, f_hi = 0;  // per lane: min / max of the diagonals it saw satisfy the condition
+    auto visit = [&](uint32_t tt, uint32_t cc) {  // diagonal tt has centre cc
+        const int32_t c = (int32_t)cc, td = (int32_t)tt;
+        if (c - rad >= 0 && c + rad <= (int32_t)L && c + rad <= td && c - rad >= td - (int32_t)n) {
+            f_lo = tt < f_lo ? tt : f_lo;
+            f_hi = tt > f_hi ? tt : f_hi;
+        }
+    };
+    uint32_t i0 = 0, j0 = 0;  // template / read bases consumed before this step's 64 ops (uniform)
+    bool bad = false;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (uint32_t base = 0; base < n_ops && !bad; base += 64) {
+        const uint32_t k = base + lane;
+        const bool has = k < n_ops;
+        const uint32_t op = has ? ops[k] : (uint32_t)JTK_OP_INS;
+        const bool invalid = has && op > JTK_OP_DEL;
+        const bool di = has && (op <= JTK_OP_MISMATCH || op == JTK_OP_DEL), dj = has && (op <= JTK_OP_MISMATCH || op == JTK_OP_INS);
+        const unsigned long long mi = __ballot(di), mj = __ballot(dj);
+        const uint32_t i = i0 + (uint32_t)__popcll(mi & below), j = j0 + (uint32_t)__popcll(mj & below), t = i + j;  // before the op
+        const uint32_t t_after = t + (di ? 1u : 0u) + (dj ? 1u : 0u);
+        // (the serial walk stopped at the first op that passed diagonal T: nothing behind it left a bit or a visit; the read is
+        // bad either way, and so is its chunk -- only the bounds matter here)
+        if (has && !invalid && t_after <= T + 2) {
+            if (op == JTK_OP_INS) {
+                visit(t + 1, i);
+            } else {
+                if (t + 1 <= T) atomicOr(&sd[(t + 1) >> 6], 1ull << ((t + 1) & 63u));
+                visit(t + 1, i + 1);
+                if (op != JTK_OP_DEL) visit(t + 2, i + 1);
+            }
+        }
+        if (__ballot(invalid || (has && t_after > T)) != 0ull) bad = true;
+        i0 += (uint32_t)__popcll(mi);
+        j0 += (uint32_t)__popcll(mj);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t a = __shfl_xor(f_lo, o, 64), b = __shfl_xor(f_hi, o, 64);
+        f_lo = a < f_lo ? a : f_lo;
+        f_hi = b > f_hi ? b : f_hi;
+    }
+    if (bad || i0 != L || j0 != n) {
+        bad = true;
+        if (lane == 0) atomicMin(&st->status, (int)JTK_ERR_OPS_MISMATCH);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");  // the wave's own LDS atomics are done before its lanes read the words
+    for (uint32_t w = lane; w < words; w += 64) d[w] = sd[w];
+    // the word behind the read's delta words (session.hip sizes the slot from the template CAPACITY: one word to spare)
+    if (lane == 0)
+        d[((chunks[rm.chunk].tmpl_cap + rm.read_len) >> 6) + 2] = (bad || f_hi < f_lo) ? 1ull : ((uint64_t)f_hi << 32 | f_lo);
 }
-
 
 // ------------------------------------------------------------------------------------------------------
 // finalize: the 14 table entries of every position p of a read from its raw row sums, MINUS the read's lk
@@ -174,16 +233,9 @@ __global__ __launch_bounds__(FIN_TILE) void finalize_kernel(uint32_t n_reads, co
 // a chunk that turns out to have converged gets its table from finalize_kernel afterwards (converged_in).  Bit for bit the
 // totals of the two-kernel path: the same values are added in the same order.
 // ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(FIN_TILE) void sum_final_kernel(const ReadMeta *reads, const ChunkMeta *chunks, const ChunkState *state,
-                                                           const HmmDev *hmm2, const double *raw_all, const int *rawG_all,
-                                                           const double *lk_all, double *total_all) {
-#define JTK_BODY_BLOCK blockIdx.y
-#include "sum_final_body.h"
-#undef JTK_BODY_BLOCK
-}
 // blockIdx.y runs over the chunks of every segment that sums (a round that is not a final pass); blockIdx.x over the tiles of
-// the longest template of any of them (a tile past a chunk's template returns at once, as in a single launch)
-__global__ __launch_bounds__(FIN_TILE) void sum_final_merged_kernel(const RoundSegTable t, const RoundFirst f) {
+// the longest template of any of them (a tile past a chunk's template returns at once)
+__global__ __launch_bounds__(FIN_TILE) void sum_final_kernel(const RoundSegTable t, const RoundFirst f) {
     const uint32_t i = round_segment_of(f, blockIdx.y);
     const RoundSegment &g = t.seg[i];
     const uint32_t chunk = blockIdx.y - f.first[i];
@@ -194,21 +246,54 @@ __global__ __launch_bounds__(FIN_TILE) void sum_final_merged_kernel(const RoundS
     const double *raw_all = g.raw, *lk_all = g.lk;
     const int *rawG_all = g.rawG;
     double *total_all = g.total;
-#define JTK_BODY_BLOCK chunk
-#include "sum_final_body.h"
-#undef JTK_BODY_BLOCK
+    __shared__ __align__(16) double s_raw[FIN_ROWS * FIN_PITCH];
+    __shared__ int s_G[FIN_ROWS];
+    const uint32_t ci = chunk;
+    const ChunkState st = state[ci];
+    if (st.status != 0 || !st.active) return;
+    const ChunkMeta cm = chunks[ci];
+    const int L = (int)st.tmpl_len;
+    const int p0 = (int)blockIdx.x * FIN_TILE;
+    if (p0 > L) return;
+    const int tid = threadIdx.x, p = p0 + tid;
+    const int n_rows = min(FIN_ROWS, L + 1 - p0);
+    double eMf[16], eMr[16];  // strand 1 -> hmm2[0], strand 0 -> hmm2[1] (as finalize_kernel)
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+        eMf[k] = hmm2[0].eM[k];
+        eMr[k] = hmm2[1].eM[k];
+    }
+    double tot[JTK_NUM_ROW];
+#pragma unroll
+    for (int k = 0; k < JTK_NUM_ROW; k++) tot[k] = 0.0;
+    const uint32_t voters = (cm.take_num && cm.take_num < cm.n_reads) ? cm.take_num : cm.n_reads;
+    for (uint32_t r = 0; r < voters; r++) {
+        const uint32_t item = cm.read_first + r;
+        const ReadMeta rm = reads[item];
+        const double lk = lk_all[item];
+        const bool dead = !(lk > JTK_LOG_ZERO);
+        fin_stage(s_raw, s_G, raw_all + rm.raw_off, rawG_all + rm.row_off, p0, n_rows, tid, dead);
+        __syncthreads();
+        double res[JTK_NUM_ROW];
+        if (rm.strand)
+            fin_position(s_raw, s_G, eMf, tid, p, L, lk, dead, res);
+        else
+            fin_position(s_raw, s_G, eMr, tid, p, L, lk, dead, res);
+#pragma unroll
+        for (int k = 0; k < JTK_NUM_ROW; k++) tot[k] += res[k];
+        __syncthreads();  // before the next read's rows are staged
+    }
+    if (p <= L) {
+        double *total = total_all + cm.total_off + (uint64_t)p * JTK_NUM_ROW;
+#pragma unroll
+        for (int k = 0; k < JTK_NUM_ROW; k++) total[k] = tot[k];
+    }
 }
 
 }  // namespace
 
-void launch_band_prep(hipStream_t s, uint32_t n_reads, const ReadMeta *reads, const ChunkMeta *chunks,
-                      ChunkState *state, DevBufs bufs, uint64_t *delta, int only_active, uint32_t max_tmpl, uint32_t max_read) {
-    if (n_reads == 0) return;
-    const uint32_t max_words = ((max_tmpl + max_read) >> 6) + 3;   // (T >> 6) + 2 words of the longest read, T <= max_tmpl + max_read
-    band_prep_kernel<<<(n_reads + BP_WAVES - 1) / BP_WAVES, 64 * BP_WAVES, (size_t)BP_WAVES * max_words * 8, s>>>(
-        n_reads, reads, chunks, state, bufs, delta, only_active, max_words);
-}
-void launch_band_prep_merged(hipStream_t s, const RoundSegTable &t) {
+// the opening of the segments that are at it, the active chunks of those in a round that goes on
+void launch_band_prep(hipStream_t s, const RoundSegTable &t) {
     RoundFirst f;
     uint32_t max_words = 0;
     const uint32_t grid = round_prefix(t, f, [&](const RoundSegment &g) {
@@ -216,10 +301,11 @@ void launch_band_prep_merged(hipStream_t s, const RoundSegTable &t) {
         max_words = std::max(max_words, ((g.max_tmpl + g.max_read) >> 6) + 3);
         return (g.n_reads + BP_WAVES - 1) / BP_WAVES;
     });
-    if (grid) band_prep_merged_kernel<<<grid, 64 * BP_WAVES, (size_t)BP_WAVES * max_words * 8, s>>>(t, f, max_words);
+    if (grid) band_prep_kernel<<<grid, 64 * BP_WAVES, (size_t)BP_WAVES * max_words * 8, s>>>(t, f, max_words);
 }
 
-void launch_sum_final_merged(hipStream_t s, const RoundSegTable &t) {
+// the column totals of a polish round straight from the row sums: total[chunk][p][row] of every segment that sums
+void launch_sum_final(hipStream_t s, const RoundSegTable &t) {
     RoundFirst f;
     uint32_t max_tmpl = 0;
     const uint32_t n = round_prefix(t, f, [&](const RoundSegment &g) {
@@ -229,7 +315,7 @@ void launch_sum_final_merged(hipStream_t s, const RoundSegTable &t) {
     });
     if (!n) return;
     dim3 grid((max_tmpl + 1 + FIN_TILE - 1) / FIN_TILE, n);
-    sum_final_merged_kernel<<<grid, FIN_TILE, 0, s>>>(t, f);
+    sum_final_kernel<<<grid, FIN_TILE, 0, s>>>(t, f);
 }
 
 void launch_finalize(hipStream_t s, uint32_t n_reads, const ReadMeta *reads, const ChunkMeta *chunks,
@@ -238,12 +324,4 @@ void launch_finalize(hipStream_t s, uint32_t n_reads, const ReadMeta *reads, con
     if (n_reads == 0) return;
     (void)max_tmpl;
     finalize_kernel<<<n_reads, FIN_TILE, 0, s>>>(n_reads, reads, chunks, state, hmm2, raw, rawG, lk, only_active, converged_in);
-}
-
-// the column totals of a polish round straight from the row sums (sum_final_kernel): total[chunk][p][row]
-void launch_sum_final(hipStream_t s, uint32_t n_chunks, const ReadMeta *reads, const ChunkMeta *chunks, const ChunkState *state,
-                      const HmmDev *hmm2, const double *raw, const int *rawG, const double *lk, double *total, uint32_t max_tmpl) {
-    if (n_chunks == 0) return;
-    dim3 grid((max_tmpl + 1 + FIN_TILE - 1) / FIN_TILE, n_chunks);
-    sum_final_kernel<<<grid, FIN_TILE, 0, s>>>(reads, chunks, state, hmm2, raw, rawG, lk, total);
 }

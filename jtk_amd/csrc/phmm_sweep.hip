@@ -869,11 +869,14 @@ __device__ __forceinline__ void sweep_read(const int L, const int n, const int r
 
 }  // namespace
 
+// A launch carries the rounds of up to JTK_ROUND_MAX_SEGMENTS sessions (a lone session: a table of one).  The items are the
+// segments' reads back to back (f.first[i] = segment i's first item, f.first[JTK_ROUND_MAX_SEGMENTS] = their number); the tickets
+// come from a never-reset counter of whoever launches (the lane, or the session).  A wave resolves the segment of every item it
+// takes; the item index is wave-uniform (readfirstlane), so the scan, the segment's pointers and its flags are scalar loads
+// from the kernel-argument segment and live in SGPRs.
 __global__ __launch_bounds__(64, 3) __attribute__((amdgpu_num_vgpr(JTK_PHMM_NUM_VGPR))) void phmm_kernel(
-    uint32_t n_reads, const ReadMeta *reads, const ChunkMeta *chunks, const ChunkState *state, DevBufs bufs,
-    const uint8_t *ey_all, const uint64_t *delta_all, const HmmDev *hmm2, StripeSet stripes,
-    uint32_t *work_counter, uint32_t ticket_base, double *raw_all, int *rawG_all, double *lk_all, uint32_t lds_tmpl,
-    uint32_t lds_read, int only_active, uint32_t skip_le_radius) {
+    const RoundSegTable t, const RoundFirst f, StripeSet stripes, uint32_t *work_counter, uint32_t ticket_base, uint32_t lds_tmpl,
+    uint32_t lds_read) {
     const int lane = threadIdx.x;
     // this wave's stripe of the device's forward scratch, for as long as the wave lives (device_common.h: StripeSet);
     // the stripe starts with JTK_SCRATCH_GUARD rows of zeros: "the pair of a diagonal below 0" is an ordinary load
@@ -881,37 +884,15 @@ __global__ __launch_bounds__(64, 3) __attribute__((amdgpu_num_vgpr(JTK_PHMM_NUM_
     double2 *scratch = reinterpret_cast<double2 *>(stripes.mem + (uint64_t)stripe * stripes.stride) + JTK_SCRATCH_GUARD * 64;
 #pragma unroll
     for (int g = 1; g <= JTK_SCRATCH_GUARD; g++) scratch[-g * 64 + lane] = make_double2(0.0, 0.0);
+    const uint32_t n_items = f.first[JTK_ROUND_MAX_SEGMENTS];
     for (;;) {
         uint32_t item = 0;
         if (lane == 0) item = atomicAdd(work_counter, 1u) - ticket_base;  // tickets: the counter is never reset
         item = __builtin_amdgcn_readfirstlane(item);
-        if (item >= n_reads) break;
-#include "phmm_item_body.h"
-    }
-    jtk_stripe_release(stripes, stripe);
-}
-
-// The rounds of several sessions: the items are the segments' reads back to back (f.first[i] = segment i's first item,
-// f.first[JTK_ROUND_MAX_SEGMENTS] = their number), the tickets come from a counter of the LANE.  A wave resolves the segment
-// of every item it takes; the item index is wave-uniform (readfirstlane), so the scan, the segment's pointers and its flags
-// are scalar loads from the kernel-argument segment and live in SGPRs: the sweep's register budget is phmm_kernel's.
-__global__ __launch_bounds__(64, 3) __attribute__((amdgpu_num_vgpr(JTK_PHMM_NUM_VGPR))) void phmm_merged_kernel(
-    const RoundSegTable t, const RoundFirst f, StripeSet stripes, uint32_t *work_counter, uint32_t ticket_base, uint32_t lds_tmpl,
-    uint32_t lds_read) {
-    const int lane = threadIdx.x;
-    const uint32_t stripe = jtk_stripe_acquire(stripes);
-    double2 *scratch = reinterpret_cast<double2 *>(stripes.mem + (uint64_t)stripe * stripes.stride) + JTK_SCRATCH_GUARD * 64;
-#pragma unroll
-    for (int g = 1; g <= JTK_SCRATCH_GUARD; g++) scratch[-g * 64 + lane] = make_double2(0.0, 0.0);
-    const uint32_t n_items = f.first[JTK_ROUND_MAX_SEGMENTS];
-    for (;;) {
-        uint32_t item = 0;
-        if (lane == 0) item = atomicAdd(work_counter, 1u) - ticket_base;
-        item = __builtin_amdgcn_readfirstlane(item);
         if (item >= n_items) break;
         const uint32_t i = round_segment_of(f, item);
         const RoundSegment &g = t.seg[i];
-        item -= f.first[i];
+        item -= f.first[i];  // read `item` of the segment's session: both sweeps, unless the read has no part in this launch
         const ReadMeta *reads = g.reads;
         const ChunkMeta *chunks = g.chunks;
         const ChunkState *state = g.state;
@@ -923,7 +904,24 @@ __global__ __launch_bounds__(64, 3) __attribute__((amdgpu_num_vgpr(JTK_PHMM_NUM_
         int *rawG_all = g.rawG;
         const int only_active = g.only_active;
         const uint32_t skip_le_radius = g.skip_le_radius;
-#include "phmm_item_body.h"
+        const ReadMeta rm = reads[item];
+        const ChunkMeta cm = chunks[rm.chunk];
+        const ChunkState st = state[rm.chunk];
+        if (st.status != 0) continue;
+        if (only_active && !st.active) continue;
+        if (cm.take_num && item - cm.read_first >= cm.take_num) continue;  // this read does not vote
+        if (cm.radius > JTK_MAX_RADIUS) continue;                          // phmm_wide_kernel's read
+        if (cm.radius <= skip_le_radius) continue;                         // phmm_pair_kernel's read
+        const uint64_t *delta = delta_all + rm.delta_off;
+        // the interval of diagonals whose whole band lies inside the DP matrix (band_prep_kernel)
+        const uint64_t fastw = delta[((cm.tmpl_cap + rm.read_len) >> 6) + 2];
+        // everything below was loaded through the vector memory path: make it scalar again (it is the same in every lane),
+        // or the sweeps' control flow and addressing would be per-lane
+        const int strand = uni((int)rm.strand), buf = uni((int)st.buf);
+        sweep_read(uni((int)st.tmpl_len), uni((int)rm.read_len), uni((int)cm.radius), uni((int)(uint32_t)fastw),
+                   uni((int)(uint32_t)(fastw >> 32)), hmm2 + (strand ? 0 : 1), bufs.tmpl[buf] + uni64(cm.tmpl_off),
+                   ey_all + uni64(rm.ey_off), delta_all + uni64(rm.delta_off), scratch, raw_all + uni64(rm.raw_off),
+                   rawG_all + uni64(rm.row_off), lk_all + item, lds_tmpl, lds_read);
     }
     jtk_stripe_release(stripes, stripe);
 }
@@ -936,22 +934,7 @@ size_t phmm_lds_bytes(uint32_t max_tmpl, uint32_t max_read) {
     return (b + 15) & ~(size_t)15;
 }
 
-void launch_phmm(hipStream_t s, uint32_t n_reads, const ReadMeta *reads, const ChunkMeta *chunks,
-                 const ChunkState *state, DevBufs bufs, const uint8_t *ey, const uint64_t *delta,
-                 const HmmDev *hmm2, StripeSet stripes, uint32_t n_waves,
-                 uint32_t *work_counter, uint32_t *ticket_base, double *raw, int *rawG, double *lk, uint32_t max_tmpl,
-                 uint32_t max_read, int only_active, uint32_t skip_le_radius) {
-    if (n_reads == 0) return;
-    const size_t lds = phmm_lds_bytes(max_tmpl, max_read);
-    const uint32_t base = *ticket_base;
-    phmm_kernel<<<n_waves, 64, lds, s>>>(n_reads, reads, chunks, state, bufs, ey, delta, hmm2, stripes, work_counter, base, raw,
-                                         rawG, lk, max_tmpl, max_read, only_active, skip_le_radius);
-    // the host mirror of the never-reset ticket counter moves only when the launch was accepted: a rejected launch (LDS, grid
-    // or an earlier sticky error) takes no tickets, and a mirror that ran ahead would make every later launch exit at once
-    if (hipPeekAtLastError() == hipSuccess) *ticket_base = base + n_reads + n_waves;
-}
-
-// what a merged launch carries, from its table (and phmm_merged_kernel's own prefix)
+// what a launch carries, from its table (and phmm_kernel's own prefix)
 static uint32_t phmm_prefix(const RoundSegTable &t, RoundFirst &f) {
     return round_prefix(t, f, [](const RoundSegment &g) { return g.open ? 0u : g.n_reads; });
 }
@@ -967,11 +950,10 @@ void round_table_info(const RoundSegTable &t, RoundLaunchInfo *info) {
     }
 }
 
-void launch_phmm_merged(hipStream_t s, const RoundSegTable &t, StripeSet stripes, uint32_t n_waves, uint32_t *work_counter,
-                        uint32_t *ticket_base, RoundLaunchInfo *info) {
+void launch_phmm(hipStream_t s, const RoundSegTable &t, StripeSet stripes, uint32_t n_waves, uint32_t *work_counter,
+                 uint32_t *ticket_base) {
     RoundFirst f;
     const uint32_t n_items = phmm_prefix(t, f);
-    if (info) round_table_info(t, info);
     if (n_items == 0 || n_waves == 0) return;
     uint32_t max_tmpl = 0, max_read = 0;
     for (uint32_t i = 0; i < t.n; i++) {
@@ -981,6 +963,8 @@ void launch_phmm_merged(hipStream_t s, const RoundSegTable &t, StripeSet stripes
     }
     const size_t lds = phmm_lds_bytes(max_tmpl, max_read);
     const uint32_t base = *ticket_base;
-    phmm_merged_kernel<<<n_waves, 64, lds, s>>>(t, f, stripes, work_counter, base, max_tmpl, max_read);
-    if (hipPeekAtLastError() == hipSuccess) *ticket_base = base + n_items + n_waves;  // (as launch_phmm)
+    phmm_kernel<<<n_waves, 64, lds, s>>>(t, f, stripes, work_counter, base, max_tmpl, max_read);
+    // the host mirror of the never-reset ticket counter moves only when the launch was accepted: a rejected launch (LDS, grid
+    // or an earlier sticky error) takes no tickets, and a mirror that ran ahead would make every later launch exit at once
+    if (hipPeekAtLastError() == hipSuccess) *ticket_base = base + n_items + n_waves;
 }

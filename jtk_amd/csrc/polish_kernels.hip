@@ -21,7 +21,9 @@ __device__ __forceinline__ uint32_t edit_inserted(uint32_t row, uint32_t pos, ui
 
 // one wave per chunk: lanes reduce the 14 rows of each position in parallel; lane 0 does the (inherently
 // sequential) left-to-right scan and writes the edited template.
-// (chunk(): the chunk == the workgroup's index among the session's; the merged kernel gives it rebased)
+// (chunk(): the chunk == the workgroup's index among its session's.  select_edits, commit and reset_pass keep their bodies as
+// inlined functions under their kernels: written out inside the kernel they compile to the same instructions in another
+// schedule, and the kernels are to stay the machine code they were -- profiles/round_kernels_isa_same.txt)
 template <class Chunk>
 __device__ __forceinline__ void select_edits_body(Chunk &&chunk, const ChunkMeta *chunks, ChunkState *state, const DevBufs &bufs,
                                                   const double *total_all, Edit *edits_all, uint32_t *new_len,
@@ -108,15 +110,11 @@ __device__ __forceinline__ void select_edits_body(Chunk &&chunk, const ChunkMeta
     }
     new_len[ci] = w;
 }
-__global__ __launch_bounds__(64) void select_edits_kernel(const ChunkMeta *chunks, ChunkState *state, DevBufs bufs,
-                                                          const double *total_all, Edit *edits_all,
-                                                          uint32_t *new_len, uint32_t ignore_edge, int final_pass) {
-    select_edits_body([] { return blockIdx.x; }, chunks, state, bufs, total_all, edits_all, new_len, ignore_edge, final_pass);
-}
-__global__ __launch_bounds__(64) void select_edits_merged_kernel(const RoundSegTable t, const RoundFirst f) {
+__global__ __launch_bounds__(64) void select_edits_kernel(const RoundSegTable t, const RoundFirst f) {
     const uint32_t i = round_segment_of(f, blockIdx.x);
     const RoundSegment &g = t.seg[i];
     const uint32_t ci = blockIdx.x - f.first[i];
+    // (the body stays a function that takes the chunk as a callable for the sake of the instruction schedule alone: see above it)
     select_edits_body([=] { return ci; }, g.chunks, g.state, g.bufs, g.total, g.edits, g.new_len, g.ignore_edge, g.final_pass);
 }
 
@@ -134,26 +132,102 @@ __global__ __launch_bounds__(64) void select_edits_merged_kernel(const RoundSegT
 // per step: ballot / mbcnt for ti, one packed prefix sum for the output position and the new (template, read) coordinates of
 // every emitted op.  Byte for byte the serial result (every full-path parity test compares the ops).
 #define RT_WAVES 4
-__global__ __launch_bounds__(64 * RT_WAVES) void rethread_kernel(uint32_t n_reads, const ReadMeta *reads, const ChunkMeta *chunks,
-                                                                ChunkState *state, DevBufs bufs, const uint8_t *ey_all,
-                                                                const Edit *edits_all) {
-#define JTK_BODY_BLOCK blockIdx.x
-#include "rethread_body.h"
-#undef JTK_BODY_BLOCK
-}
-__global__ __launch_bounds__(64 * RT_WAVES) void rethread_merged_kernel(const RoundSegTable t, const RoundFirst f) {
+__global__ __launch_bounds__(64 * RT_WAVES) void rethread_kernel(const RoundSegTable t, const RoundFirst f) {
     const uint32_t i = round_segment_of(f, blockIdx.x);
     const RoundSegment &g = t.seg[i];
-    const uint32_t bid = blockIdx.x - f.first[i], n_reads = g.n_reads;
+    const uint32_t bid = blockIdx.x - f.first[i], n_reads = g.n_reads;  // bid: the workgroup's index among the session's
     const ReadMeta *reads = g.reads;
     const ChunkMeta *chunks = g.chunks;
     ChunkState *state = g.state;
     const DevBufs &bufs = g.bufs;
     const uint8_t *ey_all = g.ey;
     const Edit *edits_all = g.edits;
-#define JTK_BODY_BLOCK bid
-#include "rethread_body.h"
-#undef JTK_BODY_BLOCK
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t r = bid * RT_WAVES + (threadIdx.x >> 6);
+    if (r >= n_reads) return;
+    const ReadMeta rm = reads[r];
+    ChunkState *st = &state[rm.chunk];
+    if (st->status != 0 || !st->active || st->n_edits == 0) return;
+    const ChunkMeta cm = chunks[rm.chunk];
+    const uint32_t L = st->tmpl_len, ne = st->n_edits, b = st->buf, nb = JTK_NEXT_BUF(b);
+    const Edit *edits = edits_all + cm.edit_off;
+    const uint8_t *ops = bufs.ops[b] + rm.ops_off;
+    uint8_t *out = bufs.ops[nb] + rm.ops_off;
+    const uint32_t n_ops = bufs.ops_len[b][r];
+    const uint8_t *tmpl = bufs.tmpl[nb] + cm.tmpl_off;  // the edited template
+    const uint8_t *ey = ey_all + rm.ey_off;               // read base j is ey[j+1] & 3
+    const unsigned long long below = (1ull << lane) - 1ull;
+    uint32_t w0 = 0, ti0 = 0, ni0 = 0, nj0 = 0;  // uniform: ops written, old template bases consumed, new template / read position
+    uint32_t e_cur = 0;                          // uniform: edits before it cannot touch an op from here on
+    bool overflow = false;
+    // an insertion edit at position 0 fires before the first op
+    if (edits[0].pos == 0 && edits[0].row >= 4 && edits[0].row < 11) {
+        const uint32_t k = edit_inserted(edits[0].row, 0, L);
+        if (lane < k && lane < rm.ops_cap) out[lane] = JTK_OP_DEL;
+        overflow = overflow || k > rm.ops_cap;
+        w0 = k;
+        ni0 = k;
+    }
+    for (uint32_t base = 0; base < n_ops; base += 64) {
+        const uint32_t kk = base + lane;
+        const bool has = kk < n_ops;
+        const uint32_t op = has ? ops[kk] : (uint32_t)JTK_OP_INS;
+        const bool cons = has && op != JTK_OP_INS;                   // consumes an old template base
+        const unsigned long long mc = __ballot(cons);
+        const uint32_t ti = ti0 + (uint32_t)__popcll(mc & below);    // old bases consumed before this op
+        // edits whose reach ends before this step's first consuming op are behind us (uniform cursor)
+        while (e_cur < ne) {
+            const Edit ed = edits[e_cur];
+            const uint32_t last = ed.row >= 11 ? ed.pos + (ed.row - 10) - 1 : (ed.row >= 4 ? ed.pos - 1 : ed.pos);  // last ti it touches
+            if ((ed.row >= 4 && ed.row < 11 && ed.pos == 0) || last < ti0)
+                e_cur++;
+            else
+                break;
+        }
+        uint32_t first = has ? op : 4u;   // what the op becomes: an op code, or 4 = nothing
+        uint32_t k_del = 0;               // Del ops that follow it
+        if (cons) {
+            for (uint32_t e = e_cur; e < ne; e++) {
+                const Edit ed = edits[e];
+                if (ed.pos > ti + 1) break;
+                if (ed.row >= 11) {
+                    if (ed.pos <= ti && ti < ed.pos + (ed.row - 10)) first = op != JTK_OP_DEL ? (uint32_t)JTK_OP_INS : 4u;
+                } else if (ed.row >= 4 && ed.pos == ti + 1) {
+                    k_del = edit_inserted(ed.row, ed.pos, L);
+                }
+            }
+        }
+        const uint32_t c_out = (first != 4u ? 1u : 0u) + k_del;
+        const uint32_t c_t = ((first <= JTK_OP_MISMATCH || first == JTK_OP_DEL) ? 1u : 0u) + k_del;     // new template bases consumed
+        const uint32_t c_r = (first <= JTK_OP_MISMATCH || first == JTK_OP_INS) ? 1u : 0u;                // read bases consumed
+        const uint32_t packed = c_out | c_t << 10 | c_r << 20;
+        uint32_t incl = packed;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t u = __shfl_up(incl, o, 64);
+            if ((int)lane >= o) incl += u;
+        }
+        const uint32_t excl = incl - packed, total = __shfl(incl, 63, 64);
+        uint32_t w = w0 + (excl & 1023u);
+        const uint32_t ni = ni0 + ((excl >> 10) & 1023u), nj = nj0 + (excl >> 20);
+        if (first != 4u) {
+            uint32_t o1 = first;
+            if (first <= JTK_OP_MISMATCH) o1 = tmpl[ni] == (ey[nj + 1] & 3) ? JTK_OP_MATCH : JTK_OP_MISMATCH;
+            if (w < rm.ops_cap) out[w] = (uint8_t)o1;
+            w++;
+        }
+        for (uint32_t q = 0; q < k_del; q++)
+            if (w + q < rm.ops_cap) out[w + q] = JTK_OP_DEL;
+        w0 += total & 1023u;
+        ni0 += (total >> 10) & 1023u;
+        nj0 += total >> 20;
+        ti0 += (uint32_t)__popcll(mc);
+        overflow = overflow || w0 > rm.ops_cap;
+    }
+    if (lane == 0) {
+        bufs.ops_len[nb][r] = overflow ? rm.ops_cap : w0;
+        if (overflow) atomicMin(&st->status, (int)JTK_ERR_CHUNK_FAILED);
+    }
 }
 
 // reads of chunks WITHOUT edits keep their ops: copy them so both buffers stay valid is unnecessary --
@@ -184,12 +258,8 @@ __device__ __forceinline__ void commit_body(uint32_t n_chunks, ChunkState *state
         if (n_active_host) __hip_atomic_store(n_active_host, s_total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
-__global__ __launch_bounds__(256) void commit_kernel(uint32_t n_chunks, ChunkState *state, const uint32_t *new_len,
-                                                     uint32_t *n_active, uint32_t *n_active_host) {
-    commit_body(n_chunks, state, new_len, n_active, n_active_host);
-}
 // one workgroup per segment that commits (f.first[i] == its workgroup): each stores ITS round's counter and mirror
-__global__ __launch_bounds__(256) void commit_merged_kernel(const RoundSegTable t, const RoundFirst f) {
+__global__ __launch_bounds__(256) void commit_kernel(const RoundSegTable t, const RoundFirst f) {
     const RoundSegment &g = t.seg[round_segment_of(f, blockIdx.x)];
     commit_body(g.n_chunks, g.state, g.new_len, g.n_active + g.round, g.n_active_host ? g.n_active_host + g.round : nullptr);
 }
@@ -203,11 +273,7 @@ __device__ __forceinline__ void reset_pass_body(const uint32_t bid, uint32_t n_c
     if (ci < n_counters) n_active[ci] = 0;
     if (ci < n_chunks) state[ci] = state0[ci];
 }
-__global__ void reset_pass_kernel(uint32_t n_chunks, ChunkState *state, const ChunkState *state0, uint32_t *n_active,
-                                  uint32_t n_counters) {
-    reset_pass_body(blockIdx.x, n_chunks, state, state0, n_active, n_counters);
-}
-__global__ void reset_pass_merged_kernel(const RoundSegTable t, const RoundFirst f) {
+__global__ void reset_pass_kernel(const RoundSegTable t, const RoundFirst f) {
     const uint32_t i = round_segment_of(f, blockIdx.x);
     const RoundSegment &g = t.seg[i];
     reset_pass_body(blockIdx.x - f.first[i], g.n_chunks, g.state, g.state0, g.n_active, JTK_NACTIVE_SLOTS);
@@ -215,49 +281,28 @@ __global__ void reset_pass_merged_kernel(const RoundSegTable t, const RoundFirst
 
 }  // namespace
 
-void launch_reset_pass(hipStream_t s, uint32_t n_chunks, ChunkState *state, const ChunkState *state0, uint32_t *n_active,
-                       uint32_t n_counters) {
-    const uint32_t n = n_chunks > n_counters ? n_chunks : n_counters;
-    reset_pass_kernel<<<(n + 127) / 128, 128, 0, s>>>(n_chunks, state, state0, n_active, n_counters);
-}
-
 // the opening of the segments that are at it
-void launch_reset_pass_merged(hipStream_t s, const RoundSegTable &t) {
+void launch_reset_pass(hipStream_t s, const RoundSegTable &t) {
     RoundFirst f;
     const uint32_t grid = round_prefix(t, f, [](const RoundSegment &g) {
         const uint32_t n = g.n_chunks > JTK_NACTIVE_SLOTS ? g.n_chunks : JTK_NACTIVE_SLOTS;
         return g.open ? (n + 127) / 128 : 0u;
     });
-    if (grid) reset_pass_merged_kernel<<<grid, 128, 0, s>>>(t, f);
+    if (grid) reset_pass_kernel<<<grid, 128, 0, s>>>(t, f);
 }
 
-// launch_polish_round of every segment that is in a round (its own final_pass, ignore_edge, round counter)
-void launch_polish_round_merged(hipStream_t s, const RoundSegTable &t) {
+// select_edits of every segment that is in a round (its own final_pass, ignore_edge), rethread and commit of those whose
+// round goes on.  commit_kernel stores the round's "chunks still active" count in the segment's own counter n_active[round]
+// (no fill blit) and, if the segment has one, in its device-visible mirror in pinned host memory.
+void launch_polish_round(hipStream_t s, const RoundSegTable &t) {
     RoundFirst f;
     uint32_t max_tmpl = 0;
     for (uint32_t i = 0; i < t.n; i++)
         if (!t.seg[i].open && t.seg[i].max_tmpl > max_tmpl) max_tmpl = t.seg[i].max_tmpl;
     uint32_t grid = round_prefix(t, f, [](const RoundSegment &g) { return g.open ? 0u : g.n_chunks; });
-    if (grid) select_edits_merged_kernel<<<grid, 64, max_tmpl + 64, s>>>(t, f);
+    if (grid) select_edits_kernel<<<grid, 64, max_tmpl + 64, s>>>(t, f);
     grid = round_prefix(t, f, [](const RoundSegment &g) { return (g.open || g.final_pass || !g.n_chunks) ? 0u : (g.n_reads + RT_WAVES - 1) / RT_WAVES; });
-    if (grid) rethread_merged_kernel<<<grid, 64 * RT_WAVES, 0, s>>>(t, f);
+    if (grid) rethread_kernel<<<grid, 64 * RT_WAVES, 0, s>>>(t, f);
     grid = round_prefix(t, f, [](const RoundSegment &g) { return (g.open || g.final_pass || !g.n_chunks) ? 0u : 1u; });
-    if (grid) commit_merged_kernel<<<grid, 256, 0, s>>>(t, f);
-}
-
-void launch_polish_round(hipStream_t s, uint32_t n_chunks, uint32_t n_reads, const ReadMeta *reads,
-                         const ChunkMeta *chunks, ChunkState *state, DevBufs bufs, const uint8_t *ey,
-                         const double *table, double *total, Edit *edits, uint32_t *new_len, uint32_t max_tmpl,
-                         uint32_t ignore_edge, int final_pass, uint32_t *n_active_out, uint32_t *n_active_host) {
-    if (n_chunks == 0) return;
-    // n_active_out is this round's own counter (commit_kernel stores it; no fill blit here); n_active_host, if given, is a
-    // device-visible pointer into pinned host memory that receives the same number
-    // (`total` holds the round's column totals: launch_sum_final, phmm_kernels.hip)
-    (void)table;
-    select_edits_kernel<<<n_chunks, 64, max_tmpl + 64, s>>>(chunks, state, bufs, total, edits, new_len,
-                                                            ignore_edge, final_pass);
-    if (!final_pass) {
-        rethread_kernel<<<(n_reads + RT_WAVES - 1) / RT_WAVES, 64 * RT_WAVES, 0, s>>>(n_reads, reads, chunks, state, bufs, ey, edits);
-        commit_kernel<<<1, 256, 0, s>>>(n_chunks, state, new_len, n_active_out, n_active_host);
-    }
+    if (grid) commit_kernel<<<grid, 256, 0, s>>>(t, f);
 }

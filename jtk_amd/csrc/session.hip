@@ -148,8 +148,8 @@ struct LaneStreams {
     hipStream_t stream = nullptr, side = nullptr;
     hipEvent_t ev_chain[2] = {nullptr, nullptr};
     LaneLedger ledger;
-    // merged polish rounds: phmm_merged_kernel's never-reset ticket counter (device, zeroed once on the lane's stream) and its
-    // host mirror, both touched only by launch_lane_rounds, which runs under the round gather's mutex
+    // the round launches that come through the lane's gather: phmm_kernel's never-reset ticket counter (device, zeroed once on
+    // the lane's stream) and its host mirror, both touched only by launch_lane_rounds, which runs under the round gather's mutex
     uint32_t *d_round_counter = nullptr;
     uint32_t tk_round = 0;
     RoundLedger round_ledger;
@@ -712,89 +712,45 @@ int jtk_lc_debug_round_state(int device, int lane, jtk_lc_debug_round_state_t *o
     return JTK_OK;
 }
 
-// ---- the polish rounds of a pass: alone on the stream, or with the lane-mates' in one launch per kernel
+// ---- the polish rounds of a pass: one table of segments per launch, a lone session's included
 
-// the opening of a pass: every chunk back to the batch as uploaded (buffer set 0 is never written, so there is nothing to
-// copy) and the per-round counters to zero -- one small kernel, no blits -- then the bands of every read
-static int queue_open_alone(jtk_lc_session *s) {
-    hipStream_t st = s->stream;
-    launch_reset_pass(st, s->n_chunks, s->d_state.as<ChunkState>(), s->d_state0.as<ChunkState>(), s->d_nactive.as<uint32_t>(), JTK_NACTIVE_SLOTS);
-    tstart(s, JTK_K_POLISH);
-    launch_band_prep(st, s->n_reads, s->d_reads.as<ReadMeta>(), s->d_chunks.as<ChunkMeta>(), s->d_state.as<ChunkState>(), s->bufs,
-                     s->d_delta.as<uint64_t>(), 0, s->max_tmpl, s->max_read);
-    tstop(s);
-    return 0;
+// A session's step as a segment of the round kernels' table (device_common.h: RoundSegment) -- the opening of its pass (every
+// chunk back to the batch as uploaded: buffer set 0 is never written, so there is nothing to copy; the per-round counters to
+// zero; then the bands of every read) or polish round rq.round.
+RoundSegment round_segment(const jtk_lc_session *s, const jtk_lc_session::RoundRequest &rq) {
+    RoundSegment g;
+    memset(&g, 0, sizeof g);
+    g.n_chunks = s->n_chunks;
+    g.n_reads = s->n_reads;
+    g.reads = s->d_reads.as<ReadMeta>();
+    g.chunks = s->d_chunks.as<ChunkMeta>();
+    g.state = s->d_state.as<ChunkState>();
+    g.state0 = s->d_state0.as<ChunkState>();
+    g.bufs = s->bufs;
+    g.ey = s->d_ey.as<uint8_t>();
+    g.delta = s->d_delta.as<uint64_t>();
+    g.hmm2 = s->d_hmm2.as<HmmDev>();
+    g.raw = s->d_raw.as<double>();
+    g.rawG = s->d_rawG.as<int>();
+    g.lk = s->d_lk.as<double>();
+    g.total = s->d_total.as<double>();
+    g.edits = s->d_edits.as<Edit>();
+    g.new_len = s->d_newlen.as<uint32_t>();
+    g.n_active = s->d_nactive.as<uint32_t>();
+    g.n_active_host = s->h_nactive_dev;  // commit_kernel stores the round's count there itself (mapped pinned memory)
+    g.max_tmpl = s->max_tmpl;
+    g.max_read = s->max_read;
+    g.n_waves = s->n_waves;
+    g.open = rq.open ? 1u : 0u;
+    g.round = (uint32_t)rq.round;
+    g.ignore_edge = s->ignore_edge;
+    g.skip_le_radius = s->n_pair_items ? JTK_PAIR_MAX_RADIUS : 0;  // phmm_pair_kernel's chunks (such a session never shares a table)
+    g.only_active = rq.only_active;
+    g.final_pass = rq.final_pass;
+    return g;
 }
 
-// one polish round of one session, as a pass has always queued it; the round's event is recorded behind it
-static int queue_round_alone(jtk_lc_session *s, int round, int only_active, int final_pass) {
-    hipStream_t st = s->stream;
-    const ReadMeta *reads = s->d_reads.as<ReadMeta>();
-    const ChunkMeta *chunks = s->d_chunks.as<ChunkMeta>();
-    ChunkState *state = s->d_state.as<ChunkState>();
-    const HmmDev *hmm2 = s->d_hmm2.as<HmmDev>();
-    // Round 6: the variant filter takes its column statistics and the picked columns' entries straight from the row sums
-    // (column_filter_fused_kernel, filter_kernels.hip), so a clustering pass never materialises the N x 14(L+1) table --
-    // finalize_kernel runs only where the table itself is the product (window polishing keeps its final-pass call; the
-    // modification-table entry point has its own) or where a pile-up is too deep for the fused filter.
-    const bool need_tables = batch_needs_tables(s->polish_only, s->max_n);
-    tstart(s, JTK_K_PHMM);
-    launch_phmm(st, s->n_reads, reads, chunks, state, s->bufs, s->d_ey.as<uint8_t>(), s->d_delta.as<uint64_t>(),
-                hmm2, s->stripes->set(), s->n_waves, s->d_counter.as<uint32_t>(), &s->tk_phmm,
-                s->d_raw.as<double>(), s->d_rawG.as<int>(), s->d_lk.as<double>(), s->max_tmpl, s->max_read,
-                only_active, s->n_pair_items ? JTK_PAIR_MAX_RADIUS : 0);
-    if (s->n_pair_items)
-        launch_phmm_pair(st, s->n_pair_items, s->d_pair_items.as<uint32_t>(), reads, chunks, state, s->bufs,
-                         s->d_ey.as<uint8_t>(), s->d_delta.as<uint64_t>(), hmm2, s->stripes->set(),
-                         s->n_pair_waves, s->d_counter.as<uint32_t>() + 1, &s->tk_pair, s->d_raw.as<double>(), s->d_rawG.as<int>(),
-                         s->d_lk.as<double>(), s->max_tmpl, s->max_read, only_active);
-    if (s->n_wide_reads)
-        launch_phmm_wide(st, s->n_reads, reads, chunks, state, s->bufs, s->d_ey.as<uint8_t>(), s->d_delta.as<uint64_t>(),
-                         hmm2, s->d_wide_scratch.as<double>(), s->wide_stride, s->n_wide_waves,
-                         s->d_wide_counter.as<uint32_t>(), &s->tk_wide, s->d_raw.as<double>(), s->d_rawG.as<int>(),
-                         s->d_lk.as<double>(), s->max_tmpl, s->max_read, only_active, s->max_wide_radius);
-    // A polish round needs the column totals of the active chunks, not their per-read tables: the totals come straight from
-    // the row sums (sum_final_kernel), and only a chunk that turns out to have converged -- no edit selected -- gets its
-    // table, once, from the row sums it still holds.  The last pass materialises the tables of whatever is still active.
-    if (final_pass) {
-        if (need_tables)
-            launch_finalize(st, s->n_reads, reads, chunks, state, hmm2, s->d_raw.as<double>(), s->d_rawG.as<int>(),
-                            s->d_lk.as<double>(), s->max_tmpl, only_active);
-    } else
-        launch_sum_final(st, s->n_chunks, reads, chunks, state, hmm2, s->d_raw.as<double>(), s->d_rawG.as<int>(),
-                         s->d_lk.as<double>(), s->d_total.as<double>(), s->max_tmpl);
-    tstop(s);
-    tstart(s, JTK_K_POLISH);
-    launch_polish_round(st, s->n_chunks, s->n_reads, reads, chunks, state, s->bufs, s->d_ey.as<uint8_t>(),
-                        s->d_raw.as<double>(), s->d_total.as<double>(), s->d_edits.as<Edit>(),
-                        s->d_newlen.as<uint32_t>(), s->max_tmpl, s->ignore_edge, final_pass,
-                        s->d_nactive.as<uint32_t>() + round, s->h_nactive_dev + round);
-    if (!final_pass)
-        launch_band_prep(st, s->n_reads, reads, chunks, state, s->bufs, s->d_delta.as<uint64_t>(), 1, s->max_tmpl, s->max_read);
-    tstop(s);
-    if (!final_pass && !s->polish_only && need_tables) {  // the chunks that converged in this round: their tables, for the variant search
-        tstart(s, JTK_K_PHMM);
-        launch_finalize(st, s->n_reads, reads, chunks, state, hmm2, s->d_raw.as<double>(), s->d_rawG.as<int>(),
-                        s->d_lk.as<double>(), s->max_tmpl, 0, round);
-        tstop(s);
-    }
-    // commit_kernel has stored the round's count in h_nactive[round] itself (mapped pinned memory): no read-back copy
-    if (!final_pass) JTK_HIP_TRY(hipEventRecord(s->ev_round[round & 1], st));
-    return 0;
-}
-
-static int queue_request_alone(jtk_lc_session *s) {
-    const jtk_lc_session::RoundRequest &rq = s->round_request;
-    return rq.open ? queue_open_alone(s) : queue_round_alone(s, rq.round, rq.only_active, rq.final_pass);
-}
-
-static void round_ledger_add(jtk_lc_session *s, const jtk_lc_debug_round_launch_t &rec) {
-    RoundLedger &lg = device_lanes(s->device).lane(s->lane).streams.round_ledger;
-    std::lock_guard<std::mutex> lock(lg.m);
-    lg.ring[lg.calls++ % JTK_LC_DEBUG_ROUND_RECORDS] = rec;
-}
-
-// a timed stretch of a merged launch: one event pair on the lane's stream, shared by the members it is booked to
+// a timed stretch of a round launch: one event pair on the stream, shared by the members it is booked to
 struct SharedPair {
     hipEvent_t a = nullptr, b = nullptr;
     ~SharedPair() {
@@ -816,38 +772,18 @@ static void pair_book(jtk_lc_session *s, int kind, const std::shared_ptr<SharedP
     s->timers.push_back(t);
 }
 
-// The round launch of `n` sessions of one lane (RoundGather::arrive calls it, under the gather's mutex, from the thread of
-// the member that found the lane's rounds gathered).  One member: exactly what it queues without a gather.  Several: one
-// segment per member, whatever step each is at, and one launch per kernel; the phmm / polish event pairs are the launch's,
-// booked to every member they cover (kernel_launches counts a merged launch once per member it carried), and every member's
-// own round event is recorded behind the sequence.  What was launched goes into the lane's round ledger, from the table.
-static int launch_lane_rounds_on_this_thread(jtk_lc_session *const *members, int n);
-static int launch_lane_rounds(jtk_lc_session *const *members, int n) {
-    // the launch runs on ONE member's thread and g_last_error is per thread: a failure's text is left with every member it
-    // carried, and each puts it into its own thread's g_last_error when arrive() returns (run_batch)
-    const int rc = launch_lane_rounds_on_this_thread(members, n);
-    for (int i = 0; i < n; i++) members[i]->round_error = rc ? g_last_error : std::string();
-    return rc;
-}
-static int launch_lane_rounds_on_this_thread(jtk_lc_session *const *members, int n) {
-    uint64_t chunk_rows = 0;
-    for (int i = 0; i < n; i++) chunk_rows += members[i]->n_chunks;
-    if (n == 1 || chunk_rows > 65535u) {  // (sum_final's merged grid has the chunks of all members in one dimension)
-        for (int i = 0; i < n; i++) {
-            jtk_lc_session *s = members[i];
-            jtk_lc_debug_round_launch_t rec;
-            memset(&rec, 0, sizeof rec);
-            rec.members = 1;
-            rec.round[0] = s->round_request.open ? JTK_LC_DEBUG_ROUND_OPEN : (uint32_t)s->round_request.round;
-            rec.chunks[0] = s->n_chunks;
-            rec.phmm_items[0] = s->round_request.open ? 0 : s->n_reads;
-            round_ledger_add(s, rec);
-            if (int rc = queue_request_alone(s)) return rc;
-        }
-        return 0;
-    }
-    LaneStreams &ls = device_lanes(members[0]->device).lane(members[0]->lane).streams;
-    hipStream_t st = members[0]->stream;
+// The round_request of `n` >= 1 sessions that share a stream, as one table and one launch per kernel: one segment per member,
+// whatever step each is at.  The phmm / polish event pairs are the launch's, booked to every member they cover
+// (kernel_launches counts a launch once per member it carried), and every member's own round event is recorded behind the
+// sequence.  `lane`: the launch comes through the lane's round gather (under its mutex) -- the tickets are the lane's and what
+// was launched goes into the lane's round ledger, read back from the table; otherwise the one member's own tickets, no record.
+// Three kernels are outside the table and are queued for a table of ONE only, the sessions that need them never gather
+// (run_batch): phmm_pair_kernel (its chunks are the segment's skip_le_radius), phmm_wide_kernel, and finalize_kernel where the
+// per-read tables are the product (batch_needs_tables) -- the final pass's instead of sum_final, a clustering pass's after the
+// round for the chunks that converged in it.
+static int launch_round_table(jtk_lc_session *const *members, int n, LaneStreams *lane) {
+    jtk_lc_session *m0 = members[0];  // the stream is every member's; for n == 1 the lone member, whose extras are queued below
+    hipStream_t st = m0->stream;
     RoundSegTable t;
     memset(&t, 0, sizeof t);
     t.n = (uint32_t)n;
@@ -855,81 +791,107 @@ static int launch_lane_rounds_on_this_thread(jtk_lc_session *const *members, int
     uint32_t n_waves = 0;
     const StripePool *stripes = nullptr;
     for (int i = 0; i < n; i++) {
-        jtk_lc_session *s = members[i];
-        const jtk_lc_session::RoundRequest &rq = s->round_request;
-        RoundSegment &g = t.seg[i];
-        g.n_chunks = s->n_chunks;
-        g.n_reads = s->n_reads;
-        g.reads = s->d_reads.as<ReadMeta>();
-        g.chunks = s->d_chunks.as<ChunkMeta>();
-        g.state = s->d_state.as<ChunkState>();
-        g.state0 = s->d_state0.as<ChunkState>();
-        g.bufs = s->bufs;
-        g.ey = s->d_ey.as<uint8_t>();
-        g.delta = s->d_delta.as<uint64_t>();
-        g.hmm2 = s->d_hmm2.as<HmmDev>();
-        g.raw = s->d_raw.as<double>();
-        g.rawG = s->d_rawG.as<int>();
-        g.lk = s->d_lk.as<double>();
-        g.total = s->d_total.as<double>();
-        g.edits = s->d_edits.as<Edit>();
-        g.new_len = s->d_newlen.as<uint32_t>();
-        g.n_active = s->d_nactive.as<uint32_t>();
-        g.n_active_host = s->h_nactive_dev;
-        g.max_tmpl = s->max_tmpl;
-        g.max_read = s->max_read;
-        g.n_waves = s->n_waves;
-        g.open = rq.open ? 1u : 0u;
-        g.round = (uint32_t)rq.round;
-        g.ignore_edge = s->ignore_edge;
-        g.skip_le_radius = 0;  // (a session with pair items does not merge)
-        g.only_active = rq.only_active;
-        g.final_pass = rq.final_pass;
-        if (rq.open) {
+        const jtk_lc_session *m = members[i];
+        t.seg[i] = round_segment(m, m->round_request);
+        if (t.seg[i].open) {
             any_open = true;
             continue;
         }
         any_round = true;
-        n_waves = std::max(n_waves, s->n_waves);
+        n_waves = std::max(n_waves, m->n_waves);
         // the forward scratch: the members' set with the longest stripes serves every segment
-        const StripePool *sp = s->stripes.get();
+        const StripePool *sp = m->stripes.get();
         if (!stripes || sp->stride > stripes->stride || (sp->stride == stripes->stride && sp->n > stripes->n)) stripes = sp;
     }
-    jtk_lc_debug_round_launch_t rec;
-    memset(&rec, 0, sizeof rec);
-    RoundLaunchInfo info;
-    round_table_info(t, &info);
-    if (any_open) launch_reset_pass_merged(st, t);
-    if (any_round) {
+    if (lane) {
+        RoundLaunchInfo info;
+        round_table_info(t, &info);
+        jtk_lc_debug_round_launch_t rec;
+        memset(&rec, 0, sizeof rec);
+        rec.members = info.segments;
+        rec.merged = n > 1;
+        for (int i = 0; i < JTK_ROUND_MAX_SEGMENTS; i++) {
+            rec.round[i] = info.round[i];
+            rec.chunks[i] = info.chunks[i];
+            rec.phmm_items[i] = info.phmm_items[i];
+        }
+        std::lock_guard<std::mutex> lock(lane->round_ledger.m);
+        lane->round_ledger.ring[lane->round_ledger.calls++ % JTK_LC_DEBUG_ROUND_RECORDS] = rec;
+    }
+    const jtk_lc_session::RoundRequest &rq0 = m0->round_request;  // read only where lone_round holds: the lone member's step
+    const bool lone_round = n == 1 && any_round, need_tables = batch_needs_tables(m0->polish_only, m0->max_n);
+    const ReadMeta *reads = m0->d_reads.as<ReadMeta>();
+    const ChunkMeta *chunks = m0->d_chunks.as<ChunkMeta>();
+    const ChunkState *state = m0->d_state.as<ChunkState>();
+    const HmmDev *hmm2 = m0->d_hmm2.as<HmmDev>();
+    auto timed = [&](int kind, bool rounds_only, auto &&launches) -> int {
         auto p = pair_start(st);
-        if (!p) return jtk_fail(JTK_ERR_INTERNAL, "hipEventCreate / hipEventRecord failed for a merged round");
-        launch_phmm_merged(st, t, stripes->set(), std::min(n_waves, stripes->n), ls.d_round_counter, &ls.tk_round, &info);
-        launch_sum_final_merged(st, t);
+        if (!p) return jtk_fail(JTK_ERR_INTERNAL, "hipEventCreate / hipEventRecord failed for a round launch");
+        launches();
         JTK_HIP_TRY(hipEventRecord(p->b, st));
         for (int i = 0; i < n; i++)
-            if (!members[i]->round_request.open) pair_book(members[i], JTK_K_PHMM, p);
-    }
-    {
-        auto p = pair_start(st);
-        if (!p) return jtk_fail(JTK_ERR_INTERNAL, "hipEventCreate / hipEventRecord failed for a merged round");
-        if (any_round) launch_polish_round_merged(st, t);
-        launch_band_prep_merged(st, t);
-        JTK_HIP_TRY(hipEventRecord(p->b, st));
-        for (int i = 0; i < n; i++) pair_book(members[i], JTK_K_POLISH, p);
-    }
-    rec.members = info.segments;
-    rec.merged = 1;
-    for (int i = 0; i < JTK_ROUND_MAX_SEGMENTS; i++) {
-        rec.round[i] = info.round[i];
-        rec.chunks[i] = info.chunks[i];
-        rec.phmm_items[i] = info.phmm_items[i];
-    }
-    round_ledger_add(members[0], rec);
+            if (!rounds_only || !t.seg[i].open) pair_book(members[i], kind, p);
+        return 0;
+    };
+    // A polish round needs the column totals of the active chunks, not their per-read tables: the totals come straight from
+    // the row sums (sum_final_kernel).  Round 6: the variant filter takes its column statistics and the picked columns' entries
+    // from the row sums too (column_filter_fused_kernel, filter_kernels.hip), so a clustering pass never materialises the
+    // N x 14(L+1) table -- finalize_kernel runs only where the table itself is the product (window polishing's final pass;
+    // the modification-table entry point has its own) or where a pile-up is too deep for the fused filter.
+    auto sweeps_and_totals = [&] {
+        launch_phmm(st, t, stripes->set(), std::min(n_waves, stripes->n), lane ? lane->d_round_counter : m0->d_counter.as<uint32_t>(),
+                    lane ? &lane->tk_round : &m0->tk_phmm);  // (the cap binds only when sets differ: a lone session's waves fit its own set)
+        if (lone_round && m0->n_pair_items)
+            launch_phmm_pair(st, m0->n_pair_items, m0->d_pair_items.as<uint32_t>(), reads, chunks, state, m0->bufs,
+                             m0->d_ey.as<uint8_t>(), m0->d_delta.as<uint64_t>(), hmm2, m0->stripes->set(), m0->n_pair_waves,
+                             m0->d_counter.as<uint32_t>() + 1, &m0->tk_pair, m0->d_raw.as<double>(), m0->d_rawG.as<int>(),
+                             m0->d_lk.as<double>(), m0->max_tmpl, m0->max_read, rq0.only_active);
+        if (lone_round && m0->n_wide_reads)
+            launch_phmm_wide(st, m0->n_reads, reads, chunks, state, m0->bufs, m0->d_ey.as<uint8_t>(), m0->d_delta.as<uint64_t>(),
+                             hmm2, m0->d_wide_scratch.as<double>(), m0->wide_stride, m0->n_wide_waves,
+                             m0->d_wide_counter.as<uint32_t>(), &m0->tk_wide, m0->d_raw.as<double>(), m0->d_rawG.as<int>(),
+                             m0->d_lk.as<double>(), m0->max_tmpl, m0->max_read, rq0.only_active, m0->max_wide_radius);
+        launch_sum_final(st, t);  // (not of a final pass)
+        if (lone_round && rq0.final_pass && need_tables)  // the last pass materialises the tables of whatever is still active
+            launch_finalize(st, m0->n_reads, reads, chunks, state, hmm2, m0->d_raw.as<double>(), m0->d_rawG.as<int>(),
+                            m0->d_lk.as<double>(), m0->max_tmpl, rq0.only_active);
+    };
+    auto edits_and_bands = [&] {
+        if (any_round) launch_polish_round(st, t);
+        launch_band_prep(st, t);
+    };
+    // the chunks that converged in this round -- no edit selected -- get their tables, once, from the row sums they still hold
+    auto converged_tables = [&] {
+        launch_finalize(st, m0->n_reads, reads, chunks, state, hmm2, m0->d_raw.as<double>(), m0->d_rawG.as<int>(), m0->d_lk.as<double>(),
+                        m0->max_tmpl, 0, rq0.round);
+    };
+    int rc;
+    if (any_open) launch_reset_pass(st, t);
+    if (any_round && (rc = timed(JTK_K_PHMM, true, sweeps_and_totals))) return rc;
+    if ((rc = timed(JTK_K_POLISH, false, edits_and_bands))) return rc;
+    if (lone_round && !rq0.final_pass && !m0->polish_only && need_tables && (rc = timed(JTK_K_PHMM, true, converged_tables))) return rc;
     for (int i = 0; i < n; i++) {
-        const jtk_lc_session::RoundRequest &rq = members[i]->round_request;
-        if (!rq.open && !rq.final_pass) JTK_HIP_TRY(hipEventRecord(members[i]->ev_round[rq.round & 1], st));
+        const jtk_lc_session::RoundRequest &q = members[i]->round_request;
+        if (!q.open && !q.final_pass) JTK_HIP_TRY(hipEventRecord(members[i]->ev_round[q.round & 1], st));
     }
     return 0;
+}
+
+// The round launch of `n` sessions of one lane (RoundGather::arrive calls it, under the gather's mutex, from the thread of
+// the member that found the lane's rounds gathered).
+static int launch_lane_rounds(jtk_lc_session *const *members, int n) {
+    LaneStreams *lane = &device_lanes(members[0]->device).lane(members[0]->lane).streams;
+    uint64_t chunk_rows = 0;
+    for (int i = 0; i < n; i++) chunk_rows += members[i]->n_chunks;
+    int rc = 0;
+    if (chunk_rows > 65535u)  // (sum_final's grid has the chunks of all members in one dimension): each as its own table of one
+        for (int i = 0; i < n && !rc; i++) rc = launch_round_table(members + i, 1, lane);
+    else
+        rc = launch_round_table(members, n, lane);
+    // the launch runs on ONE member's thread and g_last_error is per thread: a failure's text is left with every member it
+    // carried, and each puts it into its own thread's g_last_error when arrive() returns (run_batch)
+    for (int i = 0; i < n; i++) members[i]->round_error = rc ? g_last_error : std::string();
+    return rc;
 }
 
 // Lane-mates' rounds go out in one launch per kernel unless JTK_LC_MERGE_ROUNDS=0 (read at every pass).
@@ -969,9 +931,9 @@ int run_batch(jtk_lc_session_t *s, int skip_polish) {
         JTK_HIP_TRY(hipEventCreateWithFlags(&s->ev_round[1], hipEventDisableTiming));
     }
     // The rounds go through the lane's round gather (session_lanes.h): lane-mates that are in their polish phase at the same
-    // time get one launch per kernel for all of them; a session that is alone there launches what it always has.  Sessions
-    // whose rounds hold kernels the segment tables do not cover queue them alone: pair items, wide reads, per-read tables,
-    // and the passes that enter no chain gather either.
+    // time get one launch per kernel for all of them; a session that is alone there goes out as a table of one.  Sessions
+    // whose rounds hold kernels the segment tables do not cover never park there and queue their own tables of one: pair
+    // items, wide reads, per-read tables, and the passes that enter no chain gather either.
     const bool gathers = pass.g && s->rounds && !skip_polish && !s->n_pair_items && !s->n_wide_reads &&
                          !batch_needs_tables(s->polish_only, s->max_n) && merge_rounds_enabled();
     RoundPass<jtk_lc_session> rounds(gathers ? s->rounds : nullptr);
@@ -980,7 +942,7 @@ int run_batch(jtk_lc_session_t *s, int skip_polish) {
         s->round_request.round = round;
         s->round_request.only_active = only_active;
         s->round_request.final_pass = final_pass;
-        if (!rounds.g) return queue_request_alone(s);
+        if (!rounds.g) return launch_round_table(&s, 1, nullptr);
         const int arc = rounds.g->arrive(s, launch_lane_rounds);
         if (arc) g_last_error = s->round_error;   // (the launch may have run on a lane-mate's thread)
         return arc;

@@ -175,6 +175,8 @@ int session_create_ex(const jtk_lc_params_t *params, size_t n_chunks, const jtk_
                       uint32_t post_stride, int device, const ChunkExtra *extra, uint32_t ignore_edge,
                       jtk_lc_session_t **out, bool polish_only = false);
 int run_batch(jtk_lc_session_t *s, int skip_polish);  // one pass of the kernel sequence over the resident batch
+// a session's step (the opening of a pass, or a polish round) as a segment of the round kernels' table
+RoundSegment round_segment(const jtk_lc_session *s, const jtk_lc_session::RoundRequest &rq);
 int fetch_begin(jtk_lc_session_t *s, FetchPlan &pl, uint32_t *label, double *log_post, jtk_lc_result_t *result, bool want_cons,
                 bool want_ops);
 int fetch_finish(jtk_lc_session_t *s, FetchPlan &pl, uint8_t *cons_out, uint64_t *cons_off, uint64_t cons_base, uint64_t cons_cap,

@@ -171,8 +171,8 @@ struct LanePass {
 // every point where it would queue a round (the pass's opening, then each round) it calls arrive() and is parked.  The launch
 // is made as soon as every member that is in its rounds is parked and nobody holds the gather: whoever completes that
 // condition (the last to arrive, or a parked member woken by a mate that left) calls `launch` for all parked members in
-// arrival order, at most JTK_LANE_MAX_SEGMENTS per call and the rest in the next call; `launch` itself takes the
-// single-session path for a call of one.  Every member returns once its own launch has been made, and goes back to its own
+// arrival order, at most JTK_LANE_MAX_SEGMENTS per call and the rest in the next call; a call of one is a table of one
+// segment.  Every member returns once its own launch has been made, and goes back to its own
 // bookkeeping (it stays exactly one round queued ahead, as without the gather).
 //
 // Invariants.  No timers: the only waits are on the condition variable.  A member leaves on every path out of its scope

@@ -30,6 +30,30 @@ void fit_mstep(const jtk_hmm_t &old, const double *cnt, jtk_hmm_t &out) {
             for (int q = 0; q < 4; q++) out.ins_emit[4 * cx + q] = e[q] / sum;
     }
 }
+
+// The opening of a pass and one sweep of every read, as two tables of one segment each (session.hip: round_segment): the
+// session at its opening, then in round 0.  The reads of wide bands take their own kernel, which is outside the table.
+void queue_open_and_sweep(jtk_lc_session *s) {
+    hipStream_t st = s->stream;
+    RoundSegTable t;
+    memset(&t, 0, sizeof t);
+    t.n = 1;
+    jtk_lc_session::RoundRequest rq;
+    rq.open = 1;
+    t.seg[0] = round_segment(s, rq);
+    launch_reset_pass(st, t);
+    launch_band_prep(st, t);
+    rq.open = 0;  // round 0, every chunk
+    t.seg[0] = round_segment(s, rq);
+    t.seg[0].skip_le_radius = 0;  // overrides round_segment: no launch_phmm_pair here, phmm_kernel takes the narrow bands too
+    launch_phmm(st, t, s->stripes->set(), s->n_waves, s->d_counter.as<uint32_t>(), &s->tk_phmm);
+    if (s->n_wide_reads)
+        launch_phmm_wide(st, s->n_reads, s->d_reads.as<ReadMeta>(), s->d_chunks.as<ChunkMeta>(), s->d_state.as<ChunkState>(), s->bufs,
+                         s->d_ey.as<uint8_t>(), s->d_delta.as<uint64_t>(), s->d_hmm2.as<HmmDev>(),
+                         s->d_wide_scratch.as<double>(), s->wide_stride, s->n_wide_waves, s->d_wide_counter.as<uint32_t>(), &s->tk_wide,
+                         s->d_raw.as<double>(), s->d_rawG.as<int>(), s->d_lk.as<double>(), s->max_tmpl, s->max_read, 0,
+                         s->max_wide_radius);
+}
 }  // namespace
 
 // `rounds` x [ polish every training pile-up with HMMPolishConfig::new(band / 2, N, 0) (model_tune.rs:137-143), then one
@@ -162,18 +186,7 @@ int jtk_lc_modification_table(const jtk_lc_params_t *params, const uint8_t *tmpl
     std::unique_ptr<jtk_lc_session> guard(s);
     hipStream_t st = s->stream;
     ChunkState *state = s->d_state.as<ChunkState>();
-    launch_reset_pass(st, s->n_chunks, state, s->d_state0.as<ChunkState>(), s->d_nactive.as<uint32_t>(), JTK_NACTIVE_SLOTS);
-    launch_band_prep(st, s->n_reads, s->d_reads.as<ReadMeta>(), s->d_chunks.as<ChunkMeta>(), state, s->bufs,
-                     s->d_delta.as<uint64_t>(), 0, s->max_tmpl, s->max_read);
-    launch_phmm(st, s->n_reads, s->d_reads.as<ReadMeta>(), s->d_chunks.as<ChunkMeta>(), state, s->bufs,
-                s->d_ey.as<uint8_t>(), s->d_delta.as<uint64_t>(), s->d_hmm2.as<HmmDev>(), s->stripes->set(), s->n_waves, s->d_counter.as<uint32_t>(), &s->tk_phmm, s->d_raw.as<double>(), s->d_rawG.as<int>(),
-                s->d_lk.as<double>(), s->max_tmpl, s->max_read, 0);
-    if (s->n_wide_reads)
-        launch_phmm_wide(st, s->n_reads, s->d_reads.as<ReadMeta>(), s->d_chunks.as<ChunkMeta>(), state, s->bufs,
-                         s->d_ey.as<uint8_t>(), s->d_delta.as<uint64_t>(), s->d_hmm2.as<HmmDev>(),
-                         s->d_wide_scratch.as<double>(), s->wide_stride, s->n_wide_waves, s->d_wide_counter.as<uint32_t>(), &s->tk_wide,
-                         s->d_raw.as<double>(), s->d_rawG.as<int>(), s->d_lk.as<double>(), s->max_tmpl, s->max_read, 0,
-                         s->max_wide_radius);
+    queue_open_and_sweep(s);
     launch_finalize(st, s->n_reads, s->d_reads.as<ReadMeta>(), s->d_chunks.as<ChunkMeta>(), state,
                     s->d_hmm2.as<HmmDev>(), s->d_raw.as<double>(), s->d_rawG.as<int>(), s->d_lk.as<double>(), s->max_tmpl, 0);
     ChunkState cs;
@@ -210,18 +223,7 @@ int jtk_internal_likelihoods(const jtk_lc_params_t *params, size_t n_chunks, con
     std::unique_ptr<jtk_lc_session> guard(s);
     hipStream_t st = s->stream;
     ChunkState *state = s->d_state.as<ChunkState>();
-    launch_reset_pass(st, s->n_chunks, state, s->d_state0.as<ChunkState>(), s->d_nactive.as<uint32_t>(), JTK_NACTIVE_SLOTS);
-    launch_band_prep(st, s->n_reads, s->d_reads.as<ReadMeta>(), s->d_chunks.as<ChunkMeta>(), state, s->bufs,
-                     s->d_delta.as<uint64_t>(), 0, s->max_tmpl, s->max_read);
-    launch_phmm(st, s->n_reads, s->d_reads.as<ReadMeta>(), s->d_chunks.as<ChunkMeta>(), state, s->bufs,
-                s->d_ey.as<uint8_t>(), s->d_delta.as<uint64_t>(), s->d_hmm2.as<HmmDev>(), s->stripes->set(), s->n_waves, s->d_counter.as<uint32_t>(), &s->tk_phmm, s->d_raw.as<double>(), s->d_rawG.as<int>(),
-                s->d_lk.as<double>(), s->max_tmpl, s->max_read, 0);
-    if (s->n_wide_reads)
-        launch_phmm_wide(st, s->n_reads, s->d_reads.as<ReadMeta>(), s->d_chunks.as<ChunkMeta>(), state, s->bufs,
-                         s->d_ey.as<uint8_t>(), s->d_delta.as<uint64_t>(), s->d_hmm2.as<HmmDev>(),
-                         s->d_wide_scratch.as<double>(), s->wide_stride, s->n_wide_waves, s->d_wide_counter.as<uint32_t>(), &s->tk_wide,
-                         s->d_raw.as<double>(), s->d_rawG.as<int>(), s->d_lk.as<double>(), s->max_tmpl, s->max_read, 0,
-                         s->max_wide_radius);
+    queue_open_and_sweep(s);
     std::vector<ChunkState> cs(n_chunks);
     JTK_HIP_TRY(hipMemcpyAsync(cs.data(), state, cs.size() * sizeof(ChunkState), hipMemcpyDeviceToHost, st));
     JTK_HIP_TRY(hipMemcpyAsync(lk_out, s->d_lk.p, (size_t)s->n_reads * 8, hipMemcpyDeviceToHost, st));

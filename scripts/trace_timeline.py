@@ -16,10 +16,7 @@ import sys
 
 def short(name):
     # (the kernels live in anonymous namespaces: "(anonymous namespace)::mcmc_kernel_light(ChunkMeta const*, ...")
-    # (the merged round kernels first: "phmm_merged_kernel" contains no single-session kernel's name, the others' names must not
-    # fall through to the 40-character tail)
-    for key in ("phmm_merged_kernel", "sum_final_merged_kernel", "rethread_merged_kernel", "band_prep_merged_kernel",
-                "commit_merged_kernel", "select_edits_merged_kernel", "reset_pass_merged_kernel", "mcmc_kernel_light", "mcmc_kernel_huge", "mcmc_kernel", "phmm_pair_kernel", "phmm_wide_kernel", "phmm_kernel",
+    for key in ("mcmc_kernel_light", "mcmc_kernel_huge", "mcmc_kernel", "phmm_pair_kernel", "phmm_wide_kernel", "phmm_kernel",
                 "sum_final_kernel", "finalize_kernel", "rethread_kernel", "band_prep_kernel", "commit_kernel", "select_edits_kernel",
                 "column_filter_kernel", "pick_kernel", "chunk_tables_kernel", "homop_kernel", "chain_split_kernel", "reset_pass_kernel",
                 "gather_kernel", "out_len_kernel", "encode_reads_kernel", "copyBuffer", "fillBuffer"):
@@ -66,11 +63,9 @@ def main():
     for k, iv in sorted(by.items(), key=lambda kv: -sum(b - a for a, b in kv[1])):
         s = sum(b - a for a, b in iv) / 1e6
         print("%-22s %6d %10.1f %10.1f %8.2f" % (k, len(iv), s, union_ms(iv), s / len(iv)))
-    fam = {"phmm": ("phmm_kernel", "phmm_merged_kernel", "phmm_pair_kernel", "phmm_wide_kernel"),
-           "sum/final": ("sum_final_kernel", "sum_final_merged_kernel", "finalize_kernel"),
-           "polish": ("rethread_kernel", "band_prep_kernel", "commit_kernel", "select_edits_kernel", "reset_pass_kernel",
-                      "rethread_merged_kernel", "band_prep_merged_kernel", "commit_merged_kernel", "select_edits_merged_kernel",
-                      "reset_pass_merged_kernel"),
+    fam = {"phmm": ("phmm_kernel", "phmm_pair_kernel", "phmm_wide_kernel"),
+           "sum/final": ("sum_final_kernel", "finalize_kernel"),
+           "polish": ("rethread_kernel", "band_prep_kernel", "commit_kernel", "select_edits_kernel", "reset_pass_kernel"),
            "chain": ("mcmc_kernel_light", "mcmc_kernel", "mcmc_kernel_huge")}
     for name, ks in fam.items():
         iv = [x for k in ks for x in by.get(k, [])]
@@ -112,7 +107,7 @@ def main():
     for i in range(0, len(line), 10):
         print("  " + "  ".join(line[i:i + 10]))
     # pair-HMM launches: duration against the work they carried is not in the trace; print the distribution of durations
-    ph = sorted((b - a) / 1e6 for a, b in by.get("phmm_kernel", []) + by.get("phmm_merged_kernel", []))
+    ph = sorted((b - a) / 1e6 for a, b in by.get("phmm_kernel", []))
     if ph:
         print("phmm_kernel durations ms: min %.2f  p25 %.2f  median %.2f  p75 %.2f  max %.2f" % (ph[0], ph[len(ph) // 4], ph[len(ph) // 2], ph[3 * len(ph) // 4], ph[-1]))
     return 0

@@ -1,11 +1,12 @@
 """Merged polish rounds on gathers that are certain (jtk_amd/csrc/session_lanes.h: RoundGather; session.hip: launch_lane_rounds;
-the segment-table kernels reset_pass_merged / band_prep_merged / phmm_merged / sum_final_merged / select_edits_merged /
-rethread_merged / commit_merged).  With JTK_LC_LANES=1 every session shares lane 0; the test holds the lane's ROUND gather
+the round kernels reset_pass / band_prep / phmm / sum_final / select_edits / rethread / commit, each of which takes a table of
+up to eight sessions' segments).  With JTK_LC_LANES=1 every session shares lane 0; the test holds the lane's ROUND gather
 (api.round_hold), starts one thread per session, waits until all are parked, releases, and reads from the lane's round ledger
 (api.round_state) which launches were made: per call the members, and per member its step (the opening or a polish round),
-its chunks and its reads in phmm_kernel's merged item space -- read back from the segment table the kernels were given.  Every
+its chunks and its reads in phmm_kernel's item space -- read back from the segment table the kernels were given.  Every
 case compares labels, posterior bits, result records, consensus and ops with each session ALONE (tests/test_gpu_lanes.py's
-comparison), in two passes, and asserts the merge it is about from the ledger.  No test passes on outputs alone.
+comparison; alone, a session goes through the same kernels as a table of one segment, which the reference tests pin), in two
+passes, and asserts the merge it is about from the ledger.  No test passes on outputs alone.
 
 Once every session of the lane that is in its polish phase is parked the launch is made, and a session leaves its polish phase
 only when its own round counter says so, so after a common start the ledger is exact: a session whose slowest chunk needs R polish
@@ -13,13 +14,13 @@ rounds takes part in the opening and the rounds 0 .. R (one round is always queu
 
 Band radius.  The pile-ups are the size tests/test_gpu_lanes.py uses (300 bp templates, 12 - 24 reads), but under its band
 fraction of 0.03 their radius is 4, which is phmm_pair_kernel's (radius <= 14): such a session has pair items and does not merge
-(case 5 uses exactly that).  The merged kernels take radius 15 .. 30, so the sessions here run under a band fraction of 0.12
+(case 5 uses exactly that).  phmm_kernel takes radius 15 .. 30, so the sessions here run under a band fraction of 0.12
 (radius 18).  Polish rounds: chosen from the generator's pile-ups 800 .. 823 so that the sessions differ (template error 0.001:
 1 - 3 rounds; 0.03: 3 - 10 rounds at 300 bp, so no longer template is needed); the `alone` fixture asserts from
 result["polish_rounds"] that one pile-up converges in round 1 and one needs >= 4.
 
-Not here, and why.  A chunk with take_num set: only the sub-sessions of the split branch set it, and they enter no gather.  A
-pile-up deep enough for batch_needs_tables: more than 65,535 reads, not a matter of seconds; the plan's CPU test covers the
+Not here, and why.  A chunk with take_num set inside a table of several: only the sub-sessions of the split branch and the
+polish_chunks calls set it, and they enter no gather (case 5 has one beside a gather).  A pile-up deep enough for batch_needs_tables: more than 65,535 reads, not a matter of seconds; the plan's CPU test covers the
 switch.
 """
 import os
@@ -35,16 +36,17 @@ from test_gpu_lanes import assert_same, snapshot
 pytestmark = [pytest.mark.gpu, pytest.mark.changes_env]
 
 # Seeded faults, one at a time in an uncommitted build beside the product (a macro around the one changed line), one run each of
-# the named tests.  Each was first checked to stay inside valid memory.
+# the named tests (made when the table forms were kernels of their own beside single-session ones; the names are today's).
+# Each was first checked to stay inside valid memory.
 SEEDED_FAULTS = {
-    "sum_final_merged_kernel reads the state of segment 0 (where segment 0 has at least as many chunks, so that the index stays "
+    "sum_final_kernel reads the state of segment 0 (where segment 0 has at least as many chunks, so that the index stays "
     "inside the array)":
         "test_nine_sessions_launch_as_eight_and_one fails on the ledger (39 member-launches for 32: sessions go on polishing on "
         "column totals summed for another session's template length).  test_three_sessions_released_together passes: there "
         "segment 0 is A with one chunk and the guard leaves B and C their own state -- the run says nothing about that test.",
-    "commit_merged_kernel stores a round's count in the slot of the next round (device counter and pinned mirror)":
+    "commit_kernel stores a round's count in the slot of the next round (device counter and pinned mirror)":
         "test_three_sessions_released_together[1] fails on the ledger: every session stops after round 1.",
-    "phmm_merged_kernel takes only_active from segment 0":
+    "phmm_kernel takes only_active from segment 0":
         "NOT caught, by any test, and cannot be on outputs: every kernel of a round is idempotent on a chunk that is not active "
         "(the sweep of a converged chunk rewrites the row sums it already holds, band_prep its deltas), and in round 0, where "
         "only_active is 0, every chunk is active.  The fault costs time, not results; the ledger does not see a flag.",
@@ -339,12 +341,21 @@ def test_nine_sessions_launch_as_eight_and_one(one_lane):
         g.close()
 
 
-def test_sessions_that_do_not_merge_run_beside_merging_ones(one_lane):
+@pytest.mark.parametrize("names, n_gather, take_num", [(("B", "C", "PAIR", "WIDE"), 2, 0), (("B",), 1, 8)],
+                         ids=["pair_wide_polish", "polish_take_num"])
+def test_sessions_that_do_not_merge_run_beside_merging_ones(one_lane, names, n_gather, take_num):
     """case 5: a session with pair items, one with wide reads and a polish_chunks call on the lane while B and C are parked; the
-    ledger shows B and C merged and nobody else"""
+    ledger shows B and C merged and nobody else.
+    polish_take_num: two lane-mates, B and a polish_chunks call in which 8 of a pile-up's 12 reads vote (take_num) and whose
+    product is the per-read tables' final pass (batch_needs_tables): its tables of one, with finalize_kernel beside them, are
+    queued on the lane's stream while B is parked at the lane's gather.  Such a session has no gather and the ledger records
+    none of its launches; what the ledger shows is that it joined nobody's table: every launch of the pass is B's alone
+    (members 1, not merged, B's two chunks)."""
     x, ref = one_lane
-    names = ("B", "C", "PAIR", "WIDE")
-    want_polish = api.polish_chunks(PARAMS, x["A"][0])
+    gathering = names[:n_gather]
+    want_polish = api.polish_chunks(PARAMS, x["A"][0], take_num=take_num)
+    n_cons, n_ops = int(want_polish["cons_off"][-1]), int(want_polish["ops_out_off"][-1])
+    assert n_cons > 0 and n_ops > 0
     g = Lane(x, names)
     got = {}
     try:
@@ -353,18 +364,18 @@ def test_sessions_that_do_not_merge_run_beside_merging_ones(one_lane):
             api.round_hold(0, True)
             held = True
             try:
-                for k in range(2):
+                for k in range(n_gather):
                     g.start(k)
                     g.wait((names[k], "parks"), lambda: api.round_state(0)["parked"] == k + 1)
                 # polish-only: no gather at all, returns under the hold
-                t = threading.Thread(target=lambda: got.update(out=api.polish_chunks(PARAMS, x["A"][0])))
+                t = threading.Thread(target=lambda: got.update(out=api.polish_chunks(PARAMS, x["A"][0], take_num=take_num)))
                 t.start()
                 t.join(DEADLINE_SECONDS)
                 assert not t.is_alive() and "out" in got, "the polish call waited for the round hold"
-                g.start(2)
-                g.start(3)   # (their chains wait for B and C, which are in their pass: they return after the release)
+                for k in range(n_gather, len(names)):
+                    g.start(k)   # (their chains wait for B and C, which are in their pass: they return after the release)
                 st = api.round_state(0)
-                assert st["parked"] == 2 and st["launch_calls"] == before["launch_calls"], st
+                assert st["parked"] == n_gather and st["launch_calls"] == before["launch_calls"], st
                 api.round_hold(0, False)
                 held = False
             finally:
@@ -372,13 +383,17 @@ def test_sessions_that_do_not_merge_run_beside_merging_ones(one_lane):
                     api.round_hold(0, False)
                 g.join()
             records = since(before)
-            check_together(x, ref, ("B", "C"), records)
+            check_together(x, ref, gathering, records)
             assert all(set(r["chunks"]) <= {2, 3} for r in records), records   # PAIR has 5 chunks, WIDE 6, the polish call 1
+            if n_gather == 1:
+                assert all(r["members"] == 1 and not r["merged"] and r["chunks"] == [2] for r in records), records
             for name, out, rc in zip(names, g.outs, g.rcs):
                 assert rc == 0
                 assert_same(out, ref[name]["out"], (name, "pass %d" % p))
             for k in ("cons_off", "ops_out_off", "result"):
                 assert got["out"][k].tobytes() == want_polish[k].tobytes(), k
+            assert got["out"]["cons"][:n_cons].tobytes() == want_polish["cons"][:n_cons].tobytes()
+            assert got["out"]["ops_out"][:n_ops].tobytes() == want_polish["ops_out"][:n_ops].tobytes()
     finally:
         g.close()
 
