@@ -714,6 +714,52 @@ JTK_LC_API int jtk_lc_settle_nodes(size_t n_reads, const uint64_t *node_off, con
                         const uint64_t *ops_off, int mode, jtk_node_stats_t *stats, uint32_t *n_kept, uint32_t *order,
                         uint8_t *keep, int32_t *read_status, int device);
 
+/* ---- repeat masking: canonical k-mer counts over the raw reads -------------------------------------------------------------
+ * `ds.mask_repeat` (repeat_masking.rs:135-158, the first thing cli/src/pipeline.rs:146 does to a data set) and its read-side
+ * counterpart, get_repetitive_kmer (:109-134) and RepeatAnnot::repetitiveness (:90-105).  Sequences are given as everywhere
+ * else, back to back with n + 1 offsets, but ANY byte is taken: the reference's tables code A C G T as 0 1 2 3 (forward) and
+ * 3 2 1 0 (complement) in either case and EVERY OTHER BYTE AS 0 IN BOTH, so a run of N counts as the k-mer of a run of A, and
+ * the reverse strand of a window that holds such a byte is not the complement of its forward strand.  The k-mer of a window is
+ * min(forward, reverse): the forward strand has base i at bits 2i, the reverse strand the last base's complement at bits 0..1
+ * (KMers, to_idx: :39-85, :196-208); a sequence shorter than k has none.  1 <= k <= 31 (pipeline.rs:83 asserts k < 32).
+ *
+ * jtk_lc_mask_repeats: every read is upper-cased (letters only), the k-mers of all reads are counted, and create_mask
+ * (:255-285) chooses: with M the distinct k-mers counted more than once, percentile = floor(M as f64 * (1.0 - freq)) and
+ * below_min = those of them counted <= min_count, the mask is all M of them where percentile < below_min (takes_all = 1,
+ * thr = 0); otherwise thr = the count at index percentile of the M counts in ascending order and the mask is the k-mers counted
+ * MORE than thr times.  A base j of a read then becomes lower case iff a masked k-mer starts in [j - k + 1, j] (mask_repeats,
+ * :287-325).  masked receives the reads (it may be `bases` itself); mask_kmers the mask, ascending, if mask_cap holds it
+ * (NULL with mask_cap = 0: the list is not asked for).  report: the bases, the k-mers (windows), the distinct k-mers, those counted once, the
+ * mask's size, the lower-case bases (the reference's MASKREPEAT debug rows), thr and takes_all.
+ * JTK_ERR_CHUNK_FAILED where the reference's counts[percentile] panics -- M = 0 (no reads, no k-mer, none counted twice), or
+ * freq so small that 1.0 - freq == 1.0: the report's counts are filled in (thr, takes_all, n_masked_kmers, n_lower are 0) and
+ * masked holds the upper-cased reads.  JTK_ERR_INVALID_ARG with report->n_masked_kmers = the need, and everything else valid,
+ * when mask_cap is too small (the convention of jtk_lc_fill_candidates).
+ *
+ * jtk_lc_repetitive_kmers: the k-mers of every window of the reads AS GIVEN whose k bytes are all ASCII lower case (a lower-case
+ * letter that is no base codes as 0), ascending and unique; *n_kmers = their number, also where cap is too small
+ * (JTK_ERR_INVALID_ARG, nothing written to kmers).
+ *
+ * jtk_lc_repetitiveness: for every sequence, rep_num = the sum, over the k-mers of `kmers` that occur in it more than once,
+ * of their occurrences, and rep_den = max(len, k) - k + 1 (1 for a sequence shorter than k); the reference's f64 is
+ * rep_num / rep_den.  kmers must be ascending and unique (checked on the device: JTK_ERR_INVALID_ARG).
+ *
+ * All three, before a device is looked for: JTK_ERR_INVALID_ARG for a null pointer, offsets that do not start at 0 or decrease,
+ * k = 0, freq NaN or outside [0, 1]; JTK_ERR_UNSUPPORTED for k >= 32, 2^32 bases or sequences or more (a count must fit the
+ * reference's u32), and where the index of a sequence does not fit above the k-mer in 64 bits.  JTK_ERR_ALLOC, with the size in
+ * the message, for a work area (the keys twice, the sort's block, the runs) above 80 % of the device's free memory. */
+typedef struct jtk_mask_report {
+    uint64_t n_bases, n_kmers, n_distinct, n_singleton, n_masked_kmers, n_lower;
+    uint32_t thr, takes_all;
+} jtk_mask_report_t;
+JTK_LC_API int jtk_lc_mask_repeats(size_t n_reads, const uint8_t *bases, const uint64_t *read_off, uint32_t k, double freq,
+                        uint32_t min_count, uint8_t *masked, uint64_t *mask_kmers, uint64_t mask_cap, jtk_mask_report_t *report,
+                        int device);
+JTK_LC_API int jtk_lc_repetitive_kmers(size_t n_reads, const uint8_t *bases, const uint64_t *read_off, uint32_t k, uint64_t *kmers,
+                        uint64_t cap, uint64_t *n_kmers, int device);
+JTK_LC_API int jtk_lc_repetitiveness(size_t n_seqs, const uint8_t *bases, const uint64_t *seq_off, uint32_t k, const uint64_t *kmers,
+                        uint64_t n_kmers, uint32_t *rep_num, uint32_t *rep_den, int device);
+
 /* ---- consensus polishing that votes with banded edit distances -----------------------------------------------------------
  * What the reference gets from kiley::bialignment::guided::polish_until_converge / polish_until_converge_with:
  * `take_consensus_sequence` (encode/deletion_fill.rs:260-285, whose output is the cons_bases of jtk_lc_encode_nodes),

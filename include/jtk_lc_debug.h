@@ -50,6 +50,10 @@ JTK_LC_API void jtk_lc_debug_fill_timing(double *out);
  * (upload to the last copy back). */
 JTK_LC_API void jtk_lc_debug_settle_timing(double *out);
 
+/* Of this thread's last jtk_lc_mask_repeats call, 4 doubles, HIP-event times in ms: the emit kernel; the sort of the keys; the
+ * counting and the selections up to the mask (with the one wait for the host in it); the apply kernel. */
+JTK_LC_API void jtk_lc_debug_mask_timing(double *out);
+
 /* The work-area budget of jtk_lc_align_guided / jtk_lc_encode_nodes on this thread, in bytes (traceback cells and row tables
  * per slice of the batch; 0 = the default, 4 GiB): a small value makes a small batch run in several slices.  A pair that
  * alone needs more still runs, in a slice of its own. */

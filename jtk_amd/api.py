@@ -409,6 +409,84 @@ def settle_timing():
     return dict(n_reads=int(out[0]), n_global=int(out[1]), kernel_ms=out[2], call_ms=out[3])
 
 
+def _flat_seqs(seqs):
+    """bytes back to back and their n + 1 offsets"""
+    seqs = [bytes(s) for s in seqs]
+    off = np.zeros(len(seqs) + 1, dtype=np.uint64)
+    if seqs:
+        off[1:] = np.cumsum([len(s) for s in seqs], dtype=np.uint64)
+    bases = np.frombuffer(b"".join(seqs), dtype=np.uint8).copy() if int(off[-1]) else np.zeros(0, dtype=np.uint8)
+    return seqs, bases, off
+
+
+def mask_repeats(reads, k, freq, min_count, device=0, mask_cap=None):
+    """jtk_lc_mask_repeats, `ds.mask_repeat` (repeat_masking.rs:135-158), on a list of bytes: every read upper-cased, the
+    canonical k-mers of all reads counted, create_mask's percentile over the counts, and every base that a masked k-mer covers
+    lower-cased.  Returns (the masked reads, the report, the mask's k-mers ascending): the report is a dict of
+    ffi.MASK_REPORT_DT's fields and rc -- 0, or -6 where the reference panics (no k-mer counted twice, or 1.0 - freq == 1.0): the
+    reads are then upper-cased and no more.  mask_cap: the capacity offered for the mask first (default 1,024; a mask that does
+    not fit is fetched with a second call); every other failure raises."""
+    seqs, bases, off = _flat_seqs(reads)
+    masked = np.zeros(max(len(bases), 1), dtype=np.uint8)
+    report = np.zeros(1, dtype=ffi.MASK_REPORT_DT)
+    cap = 1024 if mask_cap is None else int(mask_cap)
+    while True:
+        kmers = np.zeros(max(cap, 1), dtype=np.uint64)
+        rc = ffi.lib().jtk_lc_mask_repeats(len(seqs), u8p(bases), u64p(off), int(k), float(freq), int(min_count), u8p(masked), u64p(kmers), cap,
+                                           report.ctypes.data, device)
+        need = int(report["n_masked_kmers"][0])
+        if rc == -1 and need > cap:
+            cap = need
+            continue
+        break
+    if rc != 0 and rc != -6:
+        check(rc)
+    out = dict((name, int(report[name][0])) for name in ffi.MASK_REPORT_DT.names)
+    out["rc"] = rc
+    raw = masked.tobytes()
+    return [raw[int(off[i]):int(off[i + 1])] for i in range(len(seqs))], out, kmers[:need].copy()
+
+
+def mask_timing():
+    """jtk_lc_debug_mask_timing (include/jtk_lc_debug.h): HIP-event ms of the last mask_repeats call's four phases"""
+    out = (C.c_double * 4)()
+    ffi.lib().jtk_lc_debug_mask_timing(out)
+    return dict(emit_ms=out[0], sort_ms=out[1], select_ms=out[2], apply_ms=out[3])
+
+
+def repetitive_kmers(reads, k, device=0, cap=None):
+    """jtk_lc_repetitive_kmers, get_repetitive_kmer (repeat_masking.rs:109-134): the k-mers of every window of `reads` (bytes, as
+    given) whose bytes are all ASCII lower case, ascending and unique (np.uint64)"""
+    seqs, bases, off = _flat_seqs(reads)
+    cap = 1024 if cap is None else int(cap)
+    n = C.c_uint64(0)
+    while True:
+        kmers = np.zeros(max(cap, 1), dtype=np.uint64)
+        rc = ffi.lib().jtk_lc_repetitive_kmers(len(seqs), u8p(bases), u64p(off), int(k), u64p(kmers), cap, C.byref(n), device)
+        if rc == -1 and n.value > cap:
+            cap = n.value
+            continue
+        break
+    check(rc)
+    return kmers[:n.value].copy()
+
+
+def repetitiveness(seqs, k, kmers, device=0, parts=False):
+    """jtk_lc_repetitiveness, RepeatAnnot::repetitiveness (repeat_masking.rs:90-105) of every sequence (bytes) against the
+    ascending, unique k-mers `kmers`: np.float64 rep_num / rep_den; parts=True: (rep_num, rep_den) as np.uint32.  A call of the
+    library takes as many sequences as have an index that fits above the k-mer in 64 bits (four at k = 31): more go in several."""
+    seqs = [bytes(s) for s in seqs]
+    kmers = np.ascontiguousarray(kmers, dtype=np.uint64)
+    num, den = np.zeros(len(seqs), dtype=np.uint32), np.zeros(len(seqs), dtype=np.uint32)
+    per_call = 1 << (64 - 2 * int(k)) if 16 < int(k) <= ffi.MASK_MAX_K else max(len(seqs), 1)
+    for first in range(0, max(len(seqs), 1), per_call):
+        part, bases, off = _flat_seqs(seqs[first:first + per_call])
+        n, d = np.zeros(len(part) + 1, dtype=np.uint32), np.zeros(len(part) + 1, dtype=np.uint32)
+        check(ffi.lib().jtk_lc_repetitiveness(len(part), u8p(bases), u64p(off), int(k), u64p(kmers), len(kmers), u32p(n), u32p(d), device))
+        num[first:first + len(part)], den[first:first + len(part)] = n[:len(part)], d[:len(part)]
+    return (num, den) if parts else num.astype(np.float64) / den.astype(np.float64)
+
+
 def _fill_reads(node_off, nodes):
     nodes = np.ascontiguousarray(nodes, dtype=ffi.FILL_NODE_DT)
     node_off = np.ascontiguousarray(node_off, dtype=np.uint64)

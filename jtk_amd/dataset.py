@@ -914,9 +914,44 @@ def correct_deletion(ds, re_clustering=False, sim_thr=None, stddev_of_error=None
     return sorted(found)
 
 
+def mask_repeat(ds, k=12, freq=0.001, min_count=10, device=0, record=None):
+    """RepeatMask::mask_repeat (repeat_masking.rs:135-158) on the parsed JSON object `ds` (modified in place): raw_reads[*].seq is
+    rewritten -- upper case, lower case where a masked k-mer covers the base -- and masked_kmers.k is set; masked_kmers.thr stays
+    as it was (the reference computes thr and drops it).  The defaults are example.toml's.  record: a list that receives the
+    reference's three debug rows.  Where the reference panics (no k-mer is counted twice, or freq is too small to matter) this
+    raises ffi.JtkError with status -6 and leaves `ds` alone.  Returns the report of api.mask_repeats."""
+    reads = ds["raw_reads"]
+    masked, report, mask = api.mask_repeats([r["seq"].encode("latin-1") for r in reads], k, freq, min_count, device=device)
+    if report["rc"] != 0:
+        raise ffi.JtkError(report["rc"], "mask_repeat: no k-mer at the percentile (create_mask's counts[percentile] panics)")
+    ds["masked_kmers"]["k"] = int(k)
+    for r, seq in zip(reads, masked):
+        r["seq"] = seq.decode("latin-1")
+    if record is not None:
+        record.append("MASKREPEAT\tMaskLen\t%d\t%d" % (k, len(mask)))
+        record.append("MASKREPEAT\tTotalMask\t%d\t%d" % (report["n_lower"], report["n_bases"]))
+        record.append("MASKREPEAT\tMaskedKmers\t%d\t%d" % (len(mask), k))
+    return report
+
+
+def get_repetitive_kmer(ds, device=0):
+    """RepeatMask::get_repetitive_kmer (repeat_masking.rs:109-134): the RepeatAnnot of a masked data set, dict(k, kmers) with the
+    k-mers of every all-lower-case window of the raw reads, ascending"""
+    k = int(ds["masked_kmers"]["k"])
+    return dict(k=k, kmers=api.repetitive_kmers([r["seq"].encode("latin-1") for r in ds["raw_reads"]], k, device=device))
+
+
+def repetitiveness(ds_or_kmers, seqs, device=0):
+    """RepeatAnnot::repetitiveness (repeat_masking.rs:90-105) of every sequence of `seqs` (str or bytes) as np.float64;
+    ds_or_kmers is a data set or what get_repetitive_kmer returned for one"""
+    annot = get_repetitive_kmer(ds_or_kmers, device=device) if "raw_reads" in ds_or_kmers else ds_or_kmers
+    seqs = [s.encode("latin-1") if isinstance(s, str) else bytes(s) for s in seqs]
+    return api.repetitiveness(seqs, annot["k"], annot["kmers"], device=device)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--stage", default="local_clustering", choices=("local_clustering", "correct_clustering", "squish_erroneous_clusters", "corrected", "realign", "purge_diverged_nodes", "fill_candidates", "consensus_sequences", "correct_deletion"),
+    ap.add_argument("--stage", default="local_clustering", choices=("local_clustering", "correct_clustering", "squish_erroneous_clusters", "corrected", "realign", "purge_diverged_nodes", "fill_candidates", "consensus_sequences", "correct_deletion", "mask_repeat"),
                     help="which JTK stage to run on the file (jtk local_clustering / jtk correct_clustering); "
                          "squish_erroneous_clusters: the step JTK runs in front of the correction, with its default "
                          "configuration; corrected: that step, then correct_clustering (cli/src/pipeline.rs:174-175); realign: "
@@ -928,11 +963,16 @@ def main(argv=None):
                          "take_consensus_sequence (deletion_fill.rs:260-285) -- also a REPORT, {\"chunk,cluster\": \"ACGT...\"}, made with "
                          "this build's guided polish (parity with kiley's polish_until_converge is not pinned); correct_deletion: "
                          "`ds.correct_deletion` without re-clustering (deletion_fill.rs:36-44: the filling rounds, then purge_largeindel "
-                         "twice), the chunk ids that changed go to stderr; the guided passes and the polish are this build's own")
+                         "twice), the chunk ids that changed go to stderr; the guided passes and the polish are this build's own; "
+                         "mask_repeat: `ds.mask_repeat` (repeat_masking.rs:135-158, the pipeline's first step) with --kmersize, "
+                         "--top-freq and --min-count; -v writes its three MASKREPEAT rows")
     ap.add_argument("input", help="DataSet JSON ('-' = stdin)")
     ap.add_argument("output", help="DataSet JSON ('-' = stdout)")
     ap.add_argument("--chunks", default="", help="comma-separated chunk ids (local_clustering_selected); default: all")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--kmersize", type=int, default=12, help="mask_repeat: k (example.toml: 12)")
+    ap.add_argument("--top-freq", type=float, default=0.001, help="mask_repeat: the fraction of the repeated k-mers to mask (0.001)")
+    ap.add_argument("--min-count", type=int, default=10, help="mask_repeat: k-mers counted this often or less are not masked (10)")
     ap.add_argument("--no-refit", action="store_true",
                     help="skip update_models_on_both_strands (mod.rs:58): cluster with model_param as found in the file")
     ap.add_argument("--recluster", action="store_true",
@@ -966,6 +1006,9 @@ def main(argv=None):
         validate(ds)
         changed = correct_deletion(ds, device=args.device)
         sys.stderr.write("CD\tChanged\t%s\n" % ",".join(str(x) for x in changed))
+    elif args.stage == "mask_repeat":
+        validate(ds)
+        mask_repeat(ds, k=args.kmersize, freq=args.top_freq, min_count=args.min_count, device=args.device, record=record)
     elif args.stage == "fill_candidates":
         ds = fill_candidates(ds, device=args.device)   # the report takes the data set's place in the output
     elif args.stage == "consensus_sequences":

@@ -69,6 +69,12 @@ pub struct JtkSettleNode {
 pub struct JtkNodeStats {
     pub score: i32, pub total: u32, pub indel: u32, pub del_size: i64,
 }
+// the numbers of mask_repeat's MASKREPEAT debug rows (repeat_masking.rs:144-157, :262), thr and the TakesAll branch of create_mask
+#[repr(C)] #[derive(Clone, Copy, Default, Debug)]
+pub struct JtkMaskReport {
+    pub n_bases: u64, pub n_kmers: u64, pub n_distinct: u64, pub n_singleton: u64, pub n_masked_kmers: u64, pub n_lower: u64,
+    pub thr: u32, pub takes_all: u32,
+}
 pub const JTK_SETTLE_STATS_ONLY: c_int = 0;
 pub const JTK_SETTLE_BY_CHUNK_POS: c_int = 1;
 pub const JTK_SETTLE_BY_CHUNK: c_int = 2;
@@ -198,6 +204,20 @@ extern "C" {
         n_reads: usize, node_off: *const u64, nodes: *const JtkSettleNode, ops: *const u8, ops_off: *const u64, mode: c_int,
         stats: *mut JtkNodeStats, n_kept: *mut u32, order: *mut u32, keep: *mut u8, read_status: *mut i32,
         device: c_int) -> c_int;
+    // mask_repeat (repeat_masking.rs:135-158): the reads upper-cased, then lower-cased where a masked k-mer covers a base; masked
+    // may be `bases`; mask_kmers may be null with mask_cap 0.  -6 where create_mask's counts[percentile] panics
+    pub fn jtk_lc_mask_repeats(
+        n_reads: usize, bases: *const u8, read_off: *const u64, k: u32, freq: f64, min_count: u32, masked: *mut u8,
+        mask_kmers: *mut u64, mask_cap: u64, report: *mut JtkMaskReport, device: c_int) -> c_int;
+    // get_repetitive_kmer (repeat_masking.rs:109-134): the k-mers of the all-lower-case windows, ascending; -1 with *n_kmers = the
+    // need where cap is too small
+    pub fn jtk_lc_repetitive_kmers(
+        n_reads: usize, bases: *const u8, read_off: *const u64, k: u32, kmers: *mut u64, cap: u64, n_kmers: *mut u64,
+        device: c_int) -> c_int;
+    // RepeatAnnot::repetitiveness (repeat_masking.rs:90-105) of every sequence as rep_num / rep_den; kmers ascending and unique
+    pub fn jtk_lc_repetitiveness(
+        n_seqs: usize, bases: *const u8, seq_off: *const u64, k: u32, kmers: *const u64, n_kmers: u64, rep_num: *mut u32,
+        rep_den: *mut u32, device: c_int) -> c_int;
     // get_pileup, ins_thr and check_insertion_head / _tail of correct_deletion_error (encode/deletion_fill.rs:301-337, 642-698,
     // 883-981) for every read with target[r] == 1 (null: every read); cands sorted by (read, slot, side, chunk, cluster, is_forward)
     pub fn jtk_lc_fill_candidates(

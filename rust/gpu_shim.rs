@@ -231,6 +231,60 @@ pub(crate) fn settle_gpu(reads: &[&[definitions::Node]], mode: std::os::raw::c_i
     (kept, stats)
 }
 
+/// `RepeatMask::mask_repeat` (repeat_masking.rs:135-158) in one call: masked_kmers.k is set, every raw read is upper-cased, the
+/// canonical k-mers of all reads are counted and create_mask's percentile is taken on the device, and every base a masked k-mer
+/// covers is lower-cased in place.  `thr` is dropped, as the reference drops it.  Where create_mask's `counts[percentile]`
+/// panics the call returns -6 and this panics too.
+pub(crate) fn mask_repeat_gpu(ds: &mut definitions::DataSet, k: usize, freq: f64, min: u32) -> JtkMaskReport {
+    ds.masked_kmers.k = k;
+    let (mut bases, mut read_off) = (Vec::<u8>::new(), vec![0u64]);
+    for r in ds.raw_reads.iter() {
+        bases.extend_from_slice(r.seq());
+        read_off.push(bases.len() as u64);
+    }
+    let mut report = JtkMaskReport::default();
+    let rc = unsafe { jtk_lc_mask_repeats(ds.raw_reads.len(), bases.as_ptr(), read_off.as_ptr(), k as u32, freq, min, bases.as_mut_ptr(),
+        std::ptr::null_mut(), 0, &mut report, /*device*/ 0) };
+    assert!(rc == 0, "{}", unsafe { std::ffi::CStr::from_ptr(jtk_lc_last_error()) }.to_string_lossy());
+    for (r, w) in ds.raw_reads.iter_mut().zip(read_off.windows(2)) {
+        r.seq.seq_mut().copy_from_slice(&bases[w[0] as usize..w[1] as usize]);
+    }
+    debug!("MASKREPEAT\tMaskLen\t{}\t{}", k, report.n_masked_kmers);
+    debug!("MASKREPEAT\tTotalMask\t{}\t{}", report.n_lower, report.n_bases);
+    debug!("MASKREPEAT\tMaskedKmers\t{}\t{}", report.n_masked_kmers, k);
+    report
+}
+
+/// `get_repetitive_kmer` (repeat_masking.rs:109-134) followed by `RepeatAnnot::repetitiveness` (repeat_masking.rs:90-105) for
+/// every sequence of `seqs` -- the six calls of determine_chunks.rs:94,170,232-238,424,572,601 batched: the k-mers of the
+/// all-lower-case windows of the raw reads are collected once (ascending), then every sequence's repeated members are counted.
+pub(crate) fn repetitiveness_gpu(ds: &definitions::DataSet, seqs: &[&[u8]]) -> Vec<f64> {
+    let k = ds.masked_kmers.k as u32;
+    let (mut bases, mut read_off) = (Vec::<u8>::new(), vec![0u64]);
+    for r in ds.raw_reads.iter() {
+        bases.extend_from_slice(r.seq());
+        read_off.push(bases.len() as u64);
+    }
+    let (mut kmers, mut n_kmers) = (vec![0u64; 1 << 16], 0u64);
+    loop {
+        let rc = unsafe { jtk_lc_repetitive_kmers(ds.raw_reads.len(), bases.as_ptr(), read_off.as_ptr(), k, kmers.as_mut_ptr(),
+            kmers.len() as u64, &mut n_kmers, /*device*/ 0) };
+        if rc == -1 && n_kmers as usize > kmers.len() { kmers.resize(n_kmers as usize, 0); continue; }
+        assert!(rc == 0, "{}", unsafe { std::ffi::CStr::from_ptr(jtk_lc_last_error()) }.to_string_lossy());
+        break;
+    }
+    let (mut flat, mut seq_off) = (Vec::<u8>::new(), vec![0u64]);
+    for s in seqs.iter() {
+        flat.extend_from_slice(s);
+        seq_off.push(flat.len() as u64);
+    }
+    let (mut num, mut den) = (vec![0u32; seqs.len()], vec![0u32; seqs.len()]);
+    let rc = unsafe { jtk_lc_repetitiveness(seqs.len(), flat.as_ptr(), seq_off.as_ptr(), k, kmers.as_ptr(), n_kmers,
+        num.as_mut_ptr(), den.as_mut_ptr(), /*device*/ 0) };
+    assert!(rc == 0, "{}", unsafe { std::ffi::CStr::from_ptr(jtk_lc_last_error()) }.to_string_lossy());
+    num.iter().zip(den.iter()).map(|(&n, &d)| n as f64 / d as f64).collect()
+}
+
 /// `take_consensus_sequence` (encode/deletion_fill.rs:260-285) in one call: the nodes are bucketed by (chunk, cluster) in
 /// encoded_reads order, cluster 0 stands for the chunk's own sequence, and every other bucket is polished from the chunk's
 /// sequence: the global ops of jtk_lc_align_reads, then jtk_lc_polish_guided with radius = read_type.band_width(len) (:277).

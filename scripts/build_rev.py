@@ -22,6 +22,8 @@ def main():
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-I" + inc, "-I" + csrc] + extra
     objs, procs = [], []
     for f in jbuild.SOURCES:
+        if not os.path.exists(os.path.join(csrc, f)):
+            continue   # a file the revision does not have yet
         obj = os.path.join(out, os.path.splitext(f)[0] + ".o")
         objs.append(obj)
         cmd = [jbuild.HIPCC] + flags + (["-x", "hip"] if f.endswith(".hip") else []) + ["-c", os.path.join(csrc, f), "-o", obj]
