@@ -818,7 +818,12 @@ JTK_LC_API int jtk_lc_device_ok(int device);
  * The figures come from event pairs on the session's stream.  Sessions that share a lane (more sessions on a device than
  * its hardware queues pay for streams: INTEGRATION.md section 4) share that stream, and a family's figure then includes
  * whatever kernels of the lane's other sessions ran in between; kernel_ms[JTK_K_MCMC] is the merged chain launch that
- * carried the session's chunks, plus the wait for the sessions it was gathered with. */
+ * carried the session's chunks, plus the wait for the sessions it was gathered with.
+ * A session that shared a merged chain launch with lane-mates does not wait for the launch's end but for its own chunks
+ * ("Leaving a merged chain launch"), and HIP gives no elapsed time for an event that has not completed.
+ * For such a pass total_ms and kernel_ms[JTK_K_MCMC] are host-clock figures: from the start of the call, and from the return of
+ * the chain launch, to the moment the session saw its chunks done.  Every other figure stays an event pair, and a pass that
+ * ended with its launch's event (a lane to itself, or the fallback) is timed by events throughout, as before. */
 enum jtk_kernel_id { JTK_K_PHMM = 0, JTK_K_POLISH = 1, JTK_K_FILTER = 2, JTK_K_MCMC = 3, JTK_K_COUNT = 4 };
 typedef struct jtk_lc_timing {
     double total_ms;

@@ -167,6 +167,35 @@ typedef struct jtk_lc_debug_round_state {
 JTK_LC_API int jtk_lc_debug_round_hold(int device, int lane, int hold);
 JTK_LC_API int jtk_lc_debug_round_state(int device, int lane, jtk_lc_debug_round_state_t *out);
 
+/* How a session's passes ended ("Leaving a merged chain launch"): a session whose chains went out in a
+ * merged launch of several lane-mates waits for a word that the chain kernels write when ITS chunks are done, with the launch's
+ * end event as the fallback, and goes on while the launch still runs.  Host bookkeeping only; one record per pass
+ * (jtk_lc_session_run), the last JTK_LC_DEBUG_PASS_RECORDS kept.
+ *
+ *   pass           the session's pass count, from 1
+ *   how            JTK_LC_DEBUG_LEFT_BY_EVENT: waited for its launch's end event (every pass that shared no launch, and the
+ *                  fallback); JTK_LC_DEBUG_LEFT_BY_WORD: left through its word; 0: the pass has not reached that point
+ *   event_pending  hipEventQuery of the launch's end event said "not ready" at the moment the session left
+ *   members        sessions the chain launch carried (1: its own launch)
+ *   still_waiting  of those, the ones that had not left yet when this one did (0: the launch ended with this session)
+ *   round_stream / next_round_stream
+ *                  which of the lane's two streams (0: the first, 1: the side stream) carried this pass's rounds, and which
+ *                  carries the session's fetch and next rounds after it left
+ *   stamp_*        order stamps from one process-wide counter (larger = later; 0 = has not happened): the session left its
+ *                  launch; jtk_lc_session_run returned; a jtk_lc_session_fetch after this pass returned; and, of THIS pass's
+ *                  own rounds, the host saw round 0 complete (which the opening of the pass precedes on its stream).
+ * jtk_lc_debug_session_passes copies the records of the last min(passes, cap, JTK_LC_DEBUG_PASS_RECORDS) passes, oldest first,
+ * and returns their number (negative: a jtk_status). */
+#define JTK_LC_DEBUG_PASS_RECORDS 4
+#define JTK_LC_DEBUG_LEFT_BY_WORD 1
+#define JTK_LC_DEBUG_LEFT_BY_EVENT 2
+typedef struct jtk_lc_debug_pass {
+    uint64_t pass;
+    uint32_t how, event_pending, members, still_waiting, round_stream, next_round_stream;
+    uint64_t stamp_left, stamp_returned, stamp_fetched, stamp_round0;
+} jtk_lc_debug_pass_t;
+JTK_LC_API int jtk_lc_debug_session_passes(jtk_lc_session_t *s, jtk_lc_debug_pass_t *out, size_t cap);
+
 /* The variant filter of a clustering pass by itself ("The filter seam"): homop_kernel, chunk_tables_kernel,
  * the column filter and the pick, through the launch functions and on the batch layout of a session, from planted input
  * instead of a pair-HMM pass.  `chunks` / `tmpl_bases` / `strand` as for jtk_lc_session_create (copy_num <= 7); the reads have

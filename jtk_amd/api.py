@@ -1098,6 +1098,21 @@ class Session:
             check(lane)
         return lane
 
+    def passes(self):
+        """jtk_lc_debug_session_passes (include/jtk_lc_debug.h): how the session's last passes ended, oldest first, each
+        dict(pass_, how ("word" / "event" / None), event_pending, members, still_waiting, round_stream, next_round_stream,
+        stamp_left, stamp_returned, stamp_fetched, stamp_round0)"""
+        rec = (ffi.PassRecord * ffi.DEBUG_PASS_RECORDS)()
+        n = self._lib.jtk_lc_debug_session_passes(self._h, rec, ffi.DEBUG_PASS_RECORDS)
+        if n < 0:
+            check(n)
+        how = {ffi.LEFT_BY_WORD: "word", ffi.LEFT_BY_EVENT: "event"}
+        return [dict(pass_=int(r.pass_), how=how.get(int(r.how)), event_pending=bool(r.event_pending), members=int(r.members),
+                     still_waiting=int(r.still_waiting), round_stream=int(r.round_stream),
+                     next_round_stream=int(r.next_round_stream), stamp_left=int(r.stamp_left),
+                     stamp_returned=int(r.stamp_returned), stamp_fetched=int(r.stamp_fetched), stamp_round0=int(r.stamp_round0))
+                for r in rec[:n]]
+
     def close(self):
         if self._h:
             self._lib.jtk_lc_session_destroy(self._h)

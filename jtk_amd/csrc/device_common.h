@@ -88,6 +88,9 @@ void launch_gather(hipStream_t s, uint32_t n_reads, uint32_t n_chunks, const Rea
                    uint8_t *ops_out, uint8_t *cons_out);
 // polish_kernels.hip
 #define JTK_NACTIVE_SLOTS (JTK_POLISH_MAX_ROUNDS + 3)  // one "chunks still active" counter per polish round of a pass
+// a session's mapped pinned page: the round counters' mirror, then the word the chain kernels report a finished segment in
+#define JTK_PINNED_CHAIN_WORD JTK_NACTIVE_SLOTS
+#define JTK_PINNED_WORDS (JTK_NACTIVE_SLOTS + 1)
 // The kernels of a polish round take the rounds of up to JTK_ROUND_MAX_SEGMENTS sessions in one launch (the sessions of a
 // lane, session_lanes.h: RoundGather); a session on its own is a table of one segment -- there is one kernel per step.  A
 // segment is one session's round: its pointers, its own flags, and which step of its pass it is at -- the opening (`open`:
@@ -217,5 +220,14 @@ struct McmcSegment {
     const uint64_t *rng_resume;
     const uint32_t *order;
     uint32_t *split;
+    // The segment's own completion, or null.  `done`: a device counter that is never reset; every workgroup the launch makes
+    // for the segment adds one when it ends -- mcmc_chain_workgroups(segment) of them, the ones past the device-side list
+    // length included -- and the one that brings it to done_target (the host's count of everything launched for the segment so
+    // far) stores done_pass to *done_word, mapped pinned memory as the device addresses it.  No kernel waits for any of it.
+    uint32_t *done = nullptr, *done_word = nullptr;
+    uint32_t done_target = 0, done_pass = 0;
 };
+// the workgroups launch_mcmc_merged makes for a segment: one per chunk in the general kernel and, where the segment has a
+// split scratch and no rng_resume, one per chunk in the light kernel as well
+inline uint32_t mcmc_chain_workgroups(const McmcSegment &x) { return (x.split && !x.rng_resume ? 2u : 1u) * x.n_chunks; }
 int launch_mcmc_merged(hipStream_t s, int n_seg, const McmcSegment *seg, hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join);

@@ -583,6 +583,11 @@ struct ChainSeg {
     const uint64_t *rng_resume;
     const uint32_t *order, *order_count;
     uint32_t vt_stride_mode, post_stride, lds_n, lds_d, lds_k, wg0;
+    // Completion of the segment by itself (McmcSegment, device_common.h): every workgroup of the segment adds one to *done as
+    // its last act; the one that brings it to done_target stores done_pass to *done_word, a word of the session's pinned page.
+    // done == null: nobody counts.
+    uint32_t *done, *done_word;
+    uint32_t done_target, done_pass;
 };
 struct ChainSegTable {
     ChainSeg seg[JTK_MCMC_MAX_SEGMENTS];
@@ -597,6 +602,15 @@ __device__ __forceinline__ void mcmc_segment_body(const ChainSegTable &t) {
     mcmc_body<LIGHT>(blockIdx.x - g.wg0, g.chunks, g.state, g.params, g.feat_all, g.vtype_all, g.vt_off_all, g.vt_stride_mode,
                      g.label_all, g.post_all, g.post_stride, g.lg_all, g.lg_off, g.lds_n, g.lds_d, g.lds_k, t.seg_log, t.flags,
                      g.rng_resume, g.order, g.order_count);
+    // Every path out of the body ends here, both waves, the workgroups past the device-side list length too: the workgroup's
+    // stores are out at system scope, then it counts once.  Nothing waits for the count; all of it is read again from the
+    // kernel-argument segment, where the body's registers are dead.
+    __threadfence_system();
+    __syncthreads();
+    if (threadIdx.x == 0 && g.done) {
+        const uint32_t before = __hip_atomic_fetch_add(g.done, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        if (before + 1u == g.done_target) __hip_atomic_store(g.done_word, g.done_pass, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
 }
 __global__ __launch_bounds__(128, JTK_MCMC_WAVES) void mcmc_kernel(const ChainSegTable t) { mcmc_segment_body<false>(t); }
 // Pile-ups whose work area does not fit a CU's LDS, or of more than JTK_MAX_PILEUP reads: the per-read arrays live in a
@@ -692,7 +706,7 @@ int launch_mcmc_merged(hipStream_t s, int n_seg, const McmcSegment *seg, hipStre
         const uint32_t lds_k = clamp_k(x.lds_k);
         ChainSeg &g = general.seg[i];
         g = ChainSeg{x.chunks, x.state, x.params, x.feat, x.vtype, x.vt_off, x.label, x.post, x.lg, x.lg_off, x.rng_resume, x.order,
-                     nullptr, x.vt_stride_mode, x.post_stride, x.lds_n, x.lds_d, lds_k, grid};
+                     nullptr, x.vt_stride_mode, x.post_stride, x.lds_n, x.lds_d, lds_k, grid, x.done, x.done_word, x.done_target, x.done_pass};
         lds = std::max(lds, mcmc_lds_core(x.lds_n, x.lds_d, lds_k, JTK_SEG_LOG_GENERAL));  // the general kernel: a 12 KiB ring
         grid += x.n_chunks;
     }

@@ -16,11 +16,13 @@
 // (session_split.hip), the one-shot stage calls and window polishing (session_stages.hip), the model refit and the
 // modification table (session_refit.hip), the features-only chain (session_features.hip), the trace of a finished session
 // (session_trace.hip).
+#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
 #include <mutex>
+#include <thread>
 
 #include "session_internal.h"
 #include "session_plan.h"
@@ -153,6 +155,10 @@ struct LaneStreams {
     uint32_t *d_round_counter = nullptr;
     uint32_t tk_round = 0;
     RoundLedger round_ledger;
+    // which of {stream, side} carries rounds now, and the merged launches that members may still be waiting in
+    // (session_lanes.h: the stream rule, LaneFlow); under `flow`
+    std::mutex flow;
+    LaneFlow flights;
 };
 typedef LaneTable<LaneStreams, jtk_lc_session> DeviceLanes;
 std::mutex g_lanes_mutex;  // the map, and the late creation of a lane's side stream
@@ -162,6 +168,20 @@ DeviceLanes &device_lanes(int device) {
     DeviceLanes *&t = g_lanes[device];
     if (!t) t = new DeviceLanes();
     return *t;
+}
+
+// The session's streams as its lane has them now: `stream` the lane's round stream, `side` (if the session uses one) the other.
+// At the start of every pass and when the session has left a merged launch; returns the round stream's index.
+int bind_lane_streams(jtk_lc_session *s, bool want_side) {
+    LaneStreams &ls = device_lanes(s->device).lane(s->lane).streams;
+    std::lock_guard<std::mutex> lock(ls.flow);
+    hipStream_t two[2] = {ls.stream, ls.side};
+    const int idx = ls.flights.round_stream(ls.side != nullptr);
+    s->stream = two[idx];
+    // (After a leave this is the stream that still carries the light chain the session left.  Only the launches of a session
+    // that enters no gather read s->side, and such a session never leaves; anything else put there would queue behind that kernel.)
+    if (want_side && ls.side) s->side = two[1 - idx];
+    return idx;
 }
 
 // The session's streams: the least loaded lane of its device.  The lane count follows the hardware queues the process runs on
@@ -177,7 +197,6 @@ int take_lane(jtk_lc_session *s, bool want_side) {
     DeviceLanes::Lane &L = t.lane(lane);
     s->lane = lane;
     s->gather = &L.gather;
-    s->stream = L.streams.stream;
     JTK_HIP_TRY(hipEventCreateWithFlags(&s->ev_done, hipEventDisableTiming));
     {
         std::lock_guard<std::mutex> lock(g_lanes_mutex);
@@ -196,12 +215,13 @@ int take_lane(jtk_lc_session *s, bool want_side) {
             JTK_HIP_TRY(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
             JTK_HIP_TRY(hipEventCreateWithFlags(&L.streams.ev_chain[0], hipEventDisableTiming));
             JTK_HIP_TRY(hipEventCreateWithFlags(&L.streams.ev_chain[1], hipEventDisableTiming));
+            std::lock_guard<std::mutex> flow(L.streams.flow);
             L.streams.side = side;
         }
-        s->side = L.streams.side;
         s->ev_chain[0] = L.streams.ev_chain[0];
         s->ev_chain[1] = L.streams.ev_chain[1];
     }
+    (void)bind_lane_streams(s, want_side && lp.side);
     return 0;
 }
 
@@ -212,7 +232,7 @@ DevPtr::~DevPtr() {
     if (dev < 0 || dev >= JTK_POOL_DEVICES || !g_pool.give(dev, p, cap)) (void)hipFree(p);
 }
 
-// The mapped pinned pages the polish rounds report into (JTK_NACTIVE_SLOTS counters per session): taken from and returned to
+// The mapped pinned pages the polish rounds and the chain report into (JTK_PINNED_WORDS words per session): taken from and returned to
 // a process-wide free list -- sessions are created per slice per one-shot call, and hipHostFree synchronises the device,
 // which stalls the other slices' streams.  The pages are freed with the process.
 static std::mutex g_pinned_mutex;
@@ -227,7 +247,7 @@ static uint32_t *pinned_page_take() {
         }
     }
     uint32_t *p = nullptr;
-    if (hipHostMalloc(reinterpret_cast<void **>(&p), JTK_NACTIVE_SLOTS * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocPortable) != hipSuccess)
+    if (hipHostMalloc(reinterpret_cast<void **>(&p), JTK_PINNED_WORDS * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocPortable) != hipSuccess)
         return nullptr;
     return p;
 }
@@ -248,6 +268,19 @@ int session_wait(jtk_lc_session *s) {
     return 0;
 }
 
+// A session that left a merged launch through its word has kernels of that launch still running -- on its lane-mates' chunks,
+// never on its own buffers again.  Whatever frees, resizes or hands back those buffers waits for the launch as a whole all the same.
+int session_chain_settled(jtk_lc_session *s) {
+    if (s->flight && s->flight->end) JTK_HIP_TRY(hipEventSynchronize(s->flight->end));
+    s->flight.reset();
+    return 0;
+}
+
+// order stamps of the pass ledger (include/jtk_lc_debug.h)
+static std::atomic<uint64_t> g_order{0};
+static uint64_t order_stamp() { return ++g_order; }
+static jtk_lc_debug_pass_t &pass_record(jtk_lc_session *s) { return s->pass_log[s->n_passes % JTK_LC_DEBUG_PASS_RECORDS]; }  // under pass_log_mutex
+
 void timers_clear(std::vector<KernelTimer> &timers) {
     for (auto &t : timers) {
         if (t.shared) continue;
@@ -258,6 +291,7 @@ void timers_clear(std::vector<KernelTimer> &timers) {
 }
 
 jtk_lc_session::~jtk_lc_session() {
+    (void)session_chain_settled(this);
     if (stream) (void)session_wait(this);  // blocks go back to the pool, not through hipFree's implicit sync
     timers_clear(timers);
     if (ev_done) (void)hipEventDestroy(ev_done);
@@ -582,9 +616,21 @@ int jtk_lc_session_create(const jtk_lc_params_t *params, size_t n_chunks, const 
 // the class.  The second stream only if every member uses it.  What the two launches were given -- read from the segment
 // tables themselves, not from the members -- goes into the lane's ledger when the call returns.
 static int launch_lane_chains(jtk_lc_session *const *members, int n) {
-    hipStream_t side = members[0]->side;
-    for (int i = 1; i < n; i++)
-        if (!members[i]->side) side = nullptr;
+    LaneStreams &ls = device_lanes(members[0]->device).lane(members[0]->lane).streams;
+    bool all_side = true;
+    for (int i = 0; i < n; i++) all_side = all_side && members[i]->side;
+    // The light chain behind the members' rounds and filters, on the stream that carried them (every member of a gather was
+    // bound to the same one: the lane's round stream moves only here, and nobody is in a pass now); the general chain on the
+    // other stream -- unless a light chain that some lane-mate has not left yet runs there (a member that left it and came
+    // round alone): then one behind the other.
+    hipStream_t main_stream = members[0]->stream, side = nullptr;
+    int idx;
+    {
+        std::lock_guard<std::mutex> lock(ls.flow);
+        idx = ls.side && main_stream == ls.side ? 1 : 0;
+        hipStream_t two[2] = {ls.stream, ls.side};
+        if (ls.side && ls.flights.general_on_other(idx, all_side)) side = two[1 - idx];
+    }
     jtk_lc_debug_lane_launch_t rec;
     memset(&rec, 0, sizeof rec);
     rec.members = (uint32_t)n;
@@ -597,27 +643,73 @@ static int launch_lane_chains(jtk_lc_session *const *members, int n) {
             lg.ring[lg.calls++ % JTK_LANE_LEDGER] = rec;
         }
     } keep{members[0], rec};
+    McmcSegment seg[2][JTK_LANE_MAX_SEGMENTS];
+    int owner[2][JTK_LANE_MAX_SEGMENTS], n_seg[2] = {0, 0};
+    uint32_t workgroups[JTK_LANE_MAX_SEGMENTS] = {};
     for (int j = 0; j < 2; j++) {
-        McmcSegment seg[JTK_LANE_MAX_SEGMENTS];
-        int n_seg = 0;
         for (int i = 0; i < n; i++) {
             jtk_lc_session *s = members[i];
             const ChainClass &cc = s->chain_class[j];
             if (cc.count == 0) continue;
             // the class's own stretch of the split scratch: 2 + 2 * count words from 2 * first + 4 * j
-            seg[n_seg++] = McmcSegment{cc.count, s->d_chunks.as<ChunkMeta>(), s->d_state.as<ChunkState>(), s->d_params.as<jtk_lc_params_t>(),
-                                       s->d_feat.as<double>(), s->d_vtype.as<uint32_t>(), nullptr, 0, s->d_label.as<uint32_t>(),
-                                       s->d_post.as<double>(), s->post_stride, s->d_lg.as<double>(), s->d_lg_off.as<uint64_t>(),
-                                       cc.lds_n, cc.lds_d, cc.lds_k, nullptr, s->d_order.as<uint32_t>() + cc.first,
-                                       s->d_chain_split.as<uint32_t>() + 2 * cc.first + 4 * j};
+            owner[j][n_seg[j]] = i;
+            seg[j][n_seg[j]] = McmcSegment{cc.count, s->d_chunks.as<ChunkMeta>(), s->d_state.as<ChunkState>(), s->d_params.as<jtk_lc_params_t>(),
+                                           s->d_feat.as<double>(), s->d_vtype.as<uint32_t>(), nullptr, 0, s->d_label.as<uint32_t>(),
+                                           s->d_post.as<double>(), s->post_stride, s->d_lg.as<double>(), s->d_lg_off.as<uint64_t>(),
+                                           cc.lds_n, cc.lds_d, cc.lds_k, nullptr, s->d_order.as<uint32_t>() + cc.first,
+                                           s->d_chain_split.as<uint32_t>() + 2 * cc.first + 4 * j};
+            workgroups[i] += mcmc_chain_workgroups(seg[j][n_seg[j]]);
+            n_seg[j]++;
         }
-        rec.segments[j] = (uint32_t)n_seg;
-        for (int i = 0; i < n_seg; i++) {
-            rec.seg_chunks[j][i] = seg[i].n_chunks;
-            rec.chunks[j] += seg[i].n_chunks;
+    }
+    // every member's completion: the counter's value once both classes' kernels have counted its workgroups, and this pass's id
+    for (int i = 0; i < n; i++) {
+        jtk_lc_session *s = members[i];
+        s->flight.reset();
+        s->may_leave = false;
+        if (!workgroups[i] || !s->h_nactive) continue;   // (nothing counts, nothing reports)
+        s->chain_done.advance(workgroups[i]);
+        __atomic_store_n(s->h_nactive + JTK_PINNED_CHAIN_WORD, 0u, __ATOMIC_RELEASE);
+    }
+    for (int j = 0; j < 2; j++)
+        for (int k = 0; k < n_seg[j]; k++) {
+            jtk_lc_session *s = members[owner[j][k]];
+            if (!s->h_nactive) continue;
+            seg[j][k].done = s->d_counter.as<uint32_t>() + 2;
+            seg[j][k].done_word = s->h_nactive_dev + JTK_PINNED_CHAIN_WORD;
+            seg[j][k].done_target = s->chain_done.target;
+            seg[j][k].done_pass = s->chain_done.pass;
         }
-        if (n_seg && launch_mcmc_merged(members[0]->stream, n_seg, seg, side, members[0]->ev_chain[0], members[0]->ev_chain[1]) != 0)
+    for (int j = 0; j < 2; j++) {
+        rec.segments[j] = (uint32_t)n_seg[j];
+        for (int i = 0; i < n_seg[j]; i++) {
+            rec.seg_chunks[j][i] = seg[j][i].n_chunks;
+            rec.chunks[j] += seg[j][i].n_chunks;
+        }
+        if (n_seg[j] && launch_mcmc_merged(main_stream, n_seg[j], seg[j], side, members[0]->ev_chain[0], members[0]->ev_chain[1]) != 0)
             return -1;
+    }
+    // More than one member, and a second stream for whoever leaves first: the members that may (lane_member_may_leave: not
+    // those with a global-memory chain still to queue behind this launch) wait for their own words (run_batch), and the other
+    // stream is the lane's round stream from here on, until every member's pass is over.
+    bool may_fly = false;
+    if (n > 1 && ls.side) {
+        std::lock_guard<std::mutex> lock(ls.flow);
+        may_fly = ls.flights.may_fly();  // (not while a lane-mate still waits in an earlier merged launch: LaneFlow)
+    }
+    if (may_fly) {
+        auto f = std::make_shared<ChainFlight>();
+        if (hipEventCreateWithFlags(&f->end, hipEventDisableTiming) != hipSuccess || hipEventRecord(f->end, main_stream) != hipSuccess)
+            return 0;  // (nobody leaves early: every member waits for its own event, as a lone one does)
+        f->members = n;
+        f->light_stream = idx;
+        for (int i = 0; i < n; i++) {
+            members[i]->flight = f;
+            members[i]->may_leave = lane_member_may_leave(workgroups[i], members[i]->h_nactive != nullptr, members[i]->chain_class[2].count);
+        }
+        f->waiting.store(n);
+        std::lock_guard<std::mutex> lock(ls.flow);
+        ls.flights.launched(f);
     }
     return 0;
 }
@@ -907,6 +999,18 @@ int run_batch(jtk_lc_session_t *s, int skip_polish) {
     // chains back until it arrives or leaves (any return below).  A session that resumes RNG streams (a sub-problem of the
     // split branch) launches alone, as does one that has no chain at all.
     LanePass<jtk_lc_session> pass(!s->polish_only && !s->resume_rng ? s->gather : nullptr);
+    // The pass's streams (session_lanes.h: the stream rule).  After enter(): no merged launch of the lane, and so no change of
+    // its round stream, can come before this session's own chain point.
+    const auto host_t0 = std::chrono::steady_clock::now();
+    const int round_idx = s->lane >= 0 ? bind_lane_streams(s, s->side != nullptr) : 0;
+    {
+        std::lock_guard<std::mutex> lock(s->pass_log_mutex);
+        s->n_passes++;
+        jtk_lc_debug_pass_t &pr = pass_record(s);
+        memset(&pr, 0, sizeof pr);
+        pr.pass = s->n_passes;
+        pr.round_stream = pr.next_round_stream = (uint32_t)round_idx;
+    }
     const double h2d = g_timing.h2d_ms;
     memset(&g_timing, 0, sizeof g_timing);
     g_timing.h2d_ms = h2d;
@@ -916,6 +1020,7 @@ int run_batch(jtk_lc_session_t *s, int skip_polish) {
     const ChunkMeta *chunks = s->d_chunks.as<ChunkMeta>();
     ChunkState *state = s->d_state.as<ChunkState>();
     const HmmDev *hmm2 = s->d_hmm2.as<HmmDev>();
+    auto host_launched = host_t0;
     hipEvent_t ev0, ev1;
     JTK_HIP_TRY(hipEventCreate(&ev0));
     JTK_HIP_TRY(hipEventCreate(&ev1));
@@ -958,10 +1063,18 @@ int run_batch(jtk_lc_session_t *s, int skip_polish) {
         if (final_pass) break;
         if (round >= 1) {
             JTK_HIP_TRY(hipEventSynchronize(s->ev_round[(round - 1) & 1]));
+            if (round == 1) {
+                std::lock_guard<std::mutex> lock(s->pass_log_mutex);
+                pass_record(s).stamp_round0 = order_stamp();
+            }
             if (s->h_nactive[round - 1] == 0) break;  // round `round` was already queued and finds nothing to do
         }
     }
     rounds.leave();  // before the chain point: the lane-mates' rounds do not wait for this session any more
+    // the merged launch this pass may leave through its word (launch_lane_chains gives it); every way out of this function
+    // takes the session out of it
+    std::shared_ptr<ChainFlight> flight;
+    LaneFlightLeave leaving(nullptr);
     if (!s->polish_only) {
         tstart(s, JTK_K_FILTER);
         launch_filter(st, s->n_chunks, reads, chunks, state, s->bufs, s->d_params.as<jtk_lc_params_t>(),
@@ -972,7 +1085,11 @@ int run_batch(jtk_lc_session_t *s, int skip_polish) {
         tstop(s);
         tstart(s, JTK_K_MCMC);
         int mcmc_rc = 0;
-        if (pass.g) mcmc_rc = pass.arrive(s, launch_lane_chains);  // with the lane's other sessions, or at once if none is in a pass
+        if (pass.g) {  // with the lane's other sessions, or at once if none is in a pass
+            mcmc_rc = pass.arrive(s, launch_lane_chains);
+            flight = s->flight;
+            leaving.f = flight.get();
+        }
         for (int j = 0; j < 2 && !pass.g; j++) {
             const ChainClass &cc = s->chain_class[j];
             if (cc.count == 0 || mcmc_rc != 0) continue;
@@ -992,7 +1109,9 @@ int run_batch(jtk_lc_session_t *s, int skip_polish) {
                                        s->d_chain_ws.as<uint8_t>(), s->d_chain_ws_off.as<uint64_t>());
         }
         tstop(s);
+        host_launched = std::chrono::steady_clock::now();
         if (mcmc_rc != 0) {
+            s->flight.reset();
             (void)session_wait(s);
             return jtk_fail(JTK_ERR_INTERNAL, "the chain kernel could not be launched (jump table upload failed)");
         }
@@ -1000,22 +1119,86 @@ int run_batch(jtk_lc_session_t *s, int skip_polish) {
         s->ran_fused = !need_tables;
     }  // !polish_only
     JTK_HIP_TRY(hipEventRecord(ev1, st));
-    JTK_HIP_TRY(hipEventSynchronize(ev1));   // the session's last kernel, not the stream: lane-mates may be queueing behind it
-    JTK_HIP_TRY(hipGetLastError());
+    // A merged launch of several lane-mates (s->flight): the session waits for its OWN chunks -- the word of its pinned page
+    // that the chain kernels write when the last workgroup of its segments has counted -- asleep between looks, with the
+    // launch's end event as the fallback, and leaves while the launch still runs for its mates.  Otherwise, and where the word
+    // does not move, the event: the session's last kernel, not the stream.
+    int how = JTK_LEAVE_EVENT;
+    jtk_lc_debug_pass_t left;
+    memset(&left, 0, sizeof left);
+    left.members = 1;
+    if (flight && s->may_leave) {
+        const uint32_t *word = s->h_nactive + JTK_PINNED_CHAIN_WORD;
+        const uint32_t id = s->chain_done.pass;
+        how = lane_leave_wait([&] { return __atomic_load_n(word, __ATOMIC_ACQUIRE) == id; },
+                              [&] {
+                                  const hipError_t e = hipEventQuery(flight->end);
+                                  return e == hipSuccess ? 1 : (e == hipErrorNotReady ? 0 : -1);
+                              },
+                              [] { std::this_thread::sleep_for(std::chrono::microseconds(100)); });
+        left.event_pending = hipEventQuery(flight->end) == hipErrorNotReady;
+        (void)hipGetLastError();  // ("not ready" is an answer, not a failure of the pass)
+    }
+    const auto host_left = std::chrono::steady_clock::now();
+    if (how == JTK_LEAVE_ERROR) {
+        (void)hipEventDestroy(ev0);
+        (void)hipEventDestroy(ev1);
+        return jtk_fail(JTK_ERR_INTERNAL, "the chain launch's end event failed and the session's completion word did not move");
+    }
+    if (how == JTK_LEAVE_EVENT) {
+        JTK_HIP_TRY(hipEventSynchronize(ev1));
+        JTK_HIP_TRY(hipGetLastError());
+    }
+    if (flight) {
+        left.members = (uint32_t)flight->members;
+        left.still_waiting = (uint32_t)leaving.leave();
+        if (how != JTK_LEAVE_WORD) s->flight.reset();  // (nothing of the launch runs on: ev1 is behind all of it)
+    }
+    left.how = how == JTK_LEAVE_WORD ? JTK_LC_DEBUG_LEFT_BY_WORD : JTK_LC_DEBUG_LEFT_BY_EVENT;
+    left.stamp_left = order_stamp();
+    // from here on the session's work goes to the stream the launch it left does not run on
+    left.next_round_stream = s->lane >= 0 && how == JTK_LEAVE_WORD ? (uint32_t)bind_lane_streams(s, s->side != nullptr) : (uint32_t)round_idx;
+    // The times.  hipEventElapsedTime needs two completed events: a pass that left through its word takes total_ms and the
+    // chain family's figure from the host clock (the call's start, and the return of the chain launch, to the moment the word
+    // was seen); every other figure is an event pair that precedes the session's chain on its stream.
+    const auto host_ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
+        return std::chrono::duration<double, std::milli>(b - a).count();
+    };
     float ms = 0;
-    (void)hipEventElapsedTime(&ms, ev0, ev1);
-    g_timing.total_ms = ms;
+    if (how == JTK_LEAVE_EVENT) (void)hipEventElapsedTime(&ms, ev0, ev1);
+    g_timing.total_ms = how == JTK_LEAVE_EVENT ? (double)ms : host_ms(host_t0, host_left);
     for (int j = 0; j < 2; j++) g_timing.chain_lds_bytes[j] = s->chain_class[j].count ? s->chain_class[j].lds_bytes : 0;
     (void)hipEventDestroy(ev0);
     (void)hipEventDestroy(ev1);
     for (auto &t : s->timers) {
         if (t.kind < 0 || t.kind >= JTK_K_COUNT) continue;
         float k = 0;
-        (void)hipEventElapsedTime(&k, t.a, t.b);
+        if (how == JTK_LEAVE_WORD && t.kind == JTK_K_MCMC) k = (float)host_ms(host_launched, host_left);
+        else (void)hipEventElapsedTime(&k, t.a, t.b);
         g_timing.kernel_ms[t.kind] += k;
         g_timing.kernel_launches[t.kind] += 1;
     }
+    {
+        std::lock_guard<std::mutex> lock(s->pass_log_mutex);
+        jtk_lc_debug_pass_t &pr = pass_record(s);
+        pr.how = left.how;
+        pr.event_pending = left.event_pending;
+        pr.members = left.members;
+        pr.still_waiting = left.still_waiting;
+        pr.next_round_stream = left.next_round_stream;
+        pr.stamp_left = left.stamp_left;
+        pr.stamp_returned = order_stamp();
+    }
     return 0;
+}
+
+int jtk_lc_debug_session_passes(jtk_lc_session_t *s, jtk_lc_debug_pass_t *out, size_t cap) {
+    g_last_error.clear();
+    if (!s || (!out && cap)) return jtk_fail(JTK_ERR_INVALID_ARG, "jtk_lc_debug_session_passes: null argument");
+    std::lock_guard<std::mutex> lock(s->pass_log_mutex);
+    const uint64_t have = std::min<uint64_t>(std::min<uint64_t>(s->n_passes, JTK_LC_DEBUG_PASS_RECORDS), cap);
+    for (uint64_t i = 0; i < have; i++) out[i] = s->pass_log[(s->n_passes - have + 1 + i) % JTK_LC_DEBUG_PASS_RECORDS];
+    return (int)have;
 }
 
 int jtk_lc_session_run(jtk_lc_session_t *s, int skip_polish) {
@@ -1135,6 +1318,10 @@ int fetch_finish(jtk_lc_session_t *s, FetchPlan &pl, uint8_t *cons_out, uint64_t
     (void)hipEventDestroy(pl.ev0);
     (void)hipEventDestroy(ev1);
     pl.ev0 = nullptr;
+    if (s->n_passes) {
+        std::lock_guard<std::mutex> lock(s->pass_log_mutex);
+        pass_record(s).stamp_fetched = order_stamp();
+    }
     return 0;
 }
 

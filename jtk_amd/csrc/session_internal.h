@@ -4,8 +4,10 @@
 // reads a finished session).  The plain records are batch_types.h's; every offset, launch class and wave count of a batch
 // is worked out by session_plan.h, which has no HIP in it.
 #pragma once
+#include <atomic>
 #include <cstring>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -60,6 +62,18 @@ struct KernelTimer {
     std::shared_ptr<void> shared;
 };
 void timers_clear(std::vector<KernelTimer> &timers);  // session.hip: destroys the events a session owns alone
+
+// A merged chain launch that carried more than one session of a lane with two streams (session.hip: launch_lane_chains), held
+// by its members until their passes are over and by the lane (session_lanes.h: LaneFlight, the stream rule).  Who may leave it
+// through its word is lane_member_may_leave: a member for which anything is queued behind the merged kernels --
+// mcmc_kernel_huge for its chunks of the global-memory class -- may not; it waits for the event behind its own last kernel
+// and keeps its streams.
+struct ChainFlight : LaneFlight {
+    hipEvent_t end = nullptr;  // behind everything the launch put on its streams
+    ~ChainFlight() override {
+        if (end) (void)hipEventDestroy(end);
+    }
+};
 
 // result of one clustering_recursive call (ClusteringDevResult, mod.rs:124)
 struct SplitResult {
@@ -140,6 +154,16 @@ struct jtk_lc_session {
     DevPtr d_chain_split;
     hipStream_t side = nullptr;
     hipEvent_t ev_chain[2] = {nullptr, nullptr};
+    // Leaving a merged launch (session_lanes.h): d_counter[2] counts the session's chain workgroups and is never reset,
+    // chain_done is the host's side of it, word JTK_PINNED_CHAIN_WORD of the pinned page is where the last workgroup reports.
+    // `flight`: the merged launch the session left through its word, until the next pass; whatever frees the session's buffers
+    // waits for its end event first (session_chain_settled).
+    ChainDone chain_done;
+    std::shared_ptr<ChainFlight> flight;
+    bool may_leave = false;  // this pass, through its word (session_lanes.h: lane_member_may_leave)
+    std::mutex pass_log_mutex;  // the ledger of the last passes (include/jtk_lc_debug.h), read by another thread
+    uint64_t n_passes = 0;
+    jtk_lc_debug_pass_t pass_log[JTK_LC_DEBUG_PASS_RECORDS] = {};
     ~jtk_lc_session();  // session.hip: waits for its own work, frees its events, returns its lane and its pinned page
 };
 
@@ -167,6 +191,7 @@ int dev_upload(jtk_lc_session *s, DevPtr &d, const std::vector<T> &v) {
     return 0;
 }
 int session_wait(jtk_lc_session *s);        // until everything the session has put on its stream so far is done
+int session_chain_settled(jtk_lc_session *s);  // until the merged chain launch the session left early has ended as a whole
 void tstart(jtk_lc_session *s, int kind);  // a timed stretch of the session's stream; ~jtk_lc_session frees the events
 void tstop(jtk_lc_session *s);
 int session_create_ex(const jtk_lc_params_t *params, size_t n_chunks, const jtk_lc_chunk_t *chunks,

@@ -94,6 +94,18 @@ class RoundState(C.Structure):
                 ("launch_calls", C.c_uint64), ("records", RoundLaunch * DEBUG_ROUND_RECORDS)]
 
 
+DEBUG_PASS_RECORDS = 4   # JTK_LC_DEBUG_PASS_RECORDS
+LEFT_BY_WORD, LEFT_BY_EVENT = 1, 2   # JTK_LC_DEBUG_LEFT_BY_*
+
+
+class PassRecord(C.Structure):
+    """jtk_lc_debug_pass_t: how one pass of a session ended"""
+    _fields_ = [("pass_", C.c_uint64), ("how", C.c_uint32), ("event_pending", C.c_uint32), ("members", C.c_uint32),
+                ("still_waiting", C.c_uint32), ("round_stream", C.c_uint32), ("next_round_stream", C.c_uint32),
+                ("stamp_left", C.c_uint64), ("stamp_returned", C.c_uint64), ("stamp_fetched", C.c_uint64),
+                ("stamp_round0", C.c_uint64)]
+
+
 class SquishConfig(C.Structure):
     """jtk_squish_config_t; the defaults are SquishConfig::default() (squish_erroneous_clusters.rs:29-38)."""
     _fields_ = [("ari_thr", C.c_double), ("match_score", C.c_double), ("mismatch_score", C.c_double), ("count_thr", C.c_uint64)]
@@ -163,7 +175,7 @@ DEBUG_SYMBOLS = (
     "jtk_lc_debug_guided_scratch_cap", "jtk_lc_debug_guided_timing", "jtk_lc_debug_encode_timing",
     "jtk_lc_debug_guided_table", "jtk_lc_debug_gpolish_timing", "jtk_lc_debug_edges_timing",
     "jtk_lc_debug_session_lane", "jtk_lc_debug_lane_hold", "jtk_lc_debug_lane_state", "jtk_lc_debug_filter",
-    "jtk_lc_debug_round_hold", "jtk_lc_debug_round_state", "jtk_lc_debug_settle_timing", "jtk_lc_debug_mask_timing",
+    "jtk_lc_debug_round_hold", "jtk_lc_debug_round_state", "jtk_lc_debug_session_passes", "jtk_lc_debug_settle_timing", "jtk_lc_debug_mask_timing",
 )
 DEBUG_FILTER_TABLE, DEBUG_FILTER_ROWS_FUSED, DEBUG_FILTER_ROWS_TABLE = 0, 1, 2   # modes of jtk_lc_debug_filter
 DEBUG_FILTER_TRACE_WORDS = 66   # JTK_LC_DEBUG_FILTER_TRACE_WORDS
@@ -280,6 +292,8 @@ def lib():
     if hasattr(L, "jtk_lc_debug_round_hold"):   # (a JTK_LC_LIB build of an earlier revision has none: scripts/build_rev.py)
         sig("jtk_lc_debug_round_hold", i32, i32, i32, i32)
         sig("jtk_lc_debug_round_state", i32, i32, i32, C.POINTER(RoundState))
+    if hasattr(L, "jtk_lc_debug_session_passes"):
+        sig("jtk_lc_debug_session_passes", i32, vp, C.POINTER(PassRecord), sz)
     sig("jtk_lc_debug_filter", i32, PP, sz, vp, PU8, PU8, i32, PD, PI32, PD, PD, PU32, PU32, PU32, PD, PU32, i32)
     _lib = L
     return L
