@@ -760,6 +760,42 @@ JTK_LC_API int jtk_lc_repetitive_kmers(size_t n_reads, const uint8_t *bases, con
 JTK_LC_API int jtk_lc_repetitiveness(size_t n_seqs, const uint8_t *bases, const uint64_t *seq_off, uint32_t k, const uint64_t *kmers,
                         uint64_t n_kmers, uint32_t *rep_num, uint32_t *rep_den, int device);
 
+/* ---- mapping: minimizer seeding and chaining of reads onto chunks -----------------------------------------------------------
+ * What the reference gets from an external minimap2 process (encode/mod.rs:41-64 and :315-355, minimap2.rs; determine_chunks.rs
+ * through `self.encode` and `remove_overlapping_chunks`): WHERE in a read a chunk lies.  minimap2 is not part of the reference
+ * tree: the mapper follows THIS build's specification, DESIGN.md section 4 ("Seeding and chaining"), and parity with minimap2's
+ * choice of seeds and chains is NOT pinned.  In short: canonical k-mers (bases upper-cased on the fly; one that holds a byte that
+ * is no base, or equals its own reverse complement, is invalid), an invertible hash of the 2k bits, minimizers over windows of w
+ * k-mer positions with EVERY position that attains a window's minimum kept, an index of the targets' minimizers in which a hash
+ * that occurs more than max_occ times is not used, hits with diag = q' - tpos on the oriented query, clusters by single linkage
+ * along the diagonal (a gap above max_gap, or another target or strand, starts a new one), and a placement for every cluster
+ * with at least min_seeds distinct target positions.  skip_self: query i against target i yields nothing (minimap2's -X).
+ * A placement is a seed cluster, not an alignment: jtk_lc_encode_nodes decides whether the chunk is there.
+ *
+ * jtk_lc_map_reads: placements in the order (query, target, reverse after forward, diag_lo).  JTK_ERR_INVALID_ARG with
+ * *n_placements = the need and nothing else written when cap is too small (the convention of jtk_lc_fill_candidates).
+ * jtk_lc_sketch: the minimizers alone, ascending by (seq, pos); hash, seq, pos, strand are parallel arrays of cap entries;
+ * JTK_ERR_INVALID_ARG with *n = the need when cap is too small.
+ *
+ * Both, before a device is looked for: JTK_ERR_INVALID_ARG for a null pointer, offsets that do not start at 0 or decrease,
+ * k = 0, w = 0 or min_seeds = 0; JTK_ERR_UNSUPPORTED for k >= 32, w > 64, a target above 65,535 bases, a query above 4,000,000
+ * bases (jtk_lc_sketch: a sequence of 2^31 bases or more), more than 2^25 targets, 2^32 bases or sequences or more on either
+ * side.  After the hits are counted: JTK_ERR_UNSUPPORTED for 2^32 hits or more, JTK_ERR_ALLOC, with the size in the message,
+ * for a hit buffer above 80 % of the device's free memory. */
+typedef struct jtk_map_params { uint32_t k, w, max_occ, max_gap, min_seeds, skip_self; } jtk_map_params_t;
+typedef struct jtk_map_placement {
+    uint32_t query, target, is_forward, n_seeds;
+    uint32_t qstart, qend;          /* forward-strand query coordinates, as a PAF line has them */
+    uint32_t oq_start, oq_end;      /* on the oriented query */
+    uint32_t tstart, tend;
+    int32_t  diag_lo, diag_hi;
+} jtk_map_placement_t;
+JTK_LC_API int jtk_lc_map_reads(size_t n_targets, const uint8_t *target_bases, const uint64_t *target_off, size_t n_queries,
+                        const uint8_t *query_bases, const uint64_t *query_off, const jtk_map_params_t *params,
+                        jtk_map_placement_t *out, uint64_t cap, uint64_t *n_placements, int device);
+JTK_LC_API int jtk_lc_sketch(size_t n_seqs, const uint8_t *bases, const uint64_t *seq_off, uint32_t k, uint32_t w, uint64_t *hash,
+                        uint32_t *seq, uint32_t *pos, uint8_t *strand, uint64_t cap, uint64_t *n, int device);
+
 /* ---- consensus polishing that votes with banded edit distances -----------------------------------------------------------
  * What the reference gets from kiley::bialignment::guided::polish_until_converge / polish_until_converge_with:
  * `take_consensus_sequence` (encode/deletion_fill.rs:260-285, whose output is the cons_bases of jtk_lc_encode_nodes),

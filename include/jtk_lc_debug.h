@@ -54,6 +54,13 @@ JTK_LC_API void jtk_lc_debug_settle_timing(double *out);
  * counting and the selections up to the mask (with the one wait for the host in it); the apply kernel. */
 JTK_LC_API void jtk_lc_debug_mask_timing(double *out);
 
+/* Of this thread's last jtk_lc_map_reads call, 10 doubles: HIP-event times in ms of the two sketches, of the index (sort, run
+ * lengths, scan), of the hits (count, scan, the wait for the host, fill), of the ordering sort, of the chaining (flags, scan,
+ * reduction, the distinct target positions) and of the compaction (with its wait and the copy back); then two counts, the
+ * minimizers of targets and queries together and the hits; then the ms of the two sketch kernels alone (the sketch phase also
+ * holds the upload of the sequences and the wait for the minimizers' number), and a 0. */
+JTK_LC_API void jtk_lc_debug_map_timing(double *out);
+
 /* The work-area budget of jtk_lc_align_guided / jtk_lc_encode_nodes on this thread, in bytes (traceback cells and row tables
  * per slice of the batch; 0 = the default, 4 GiB): a small value makes a small batch run in several slices.  A pair that
  * alone needs more still runs, in a slice of its own. */

@@ -487,6 +487,93 @@ def repetitiveness(seqs, k, kmers, device=0, parts=False):
     return (num, den) if parts else num.astype(np.float64) / den.astype(np.float64)
 
 
+def sketch(seqs, k=15, w=10, device=0, cap=None):
+    """jtk_lc_sketch: the minimizers of every sequence (bytes) by DESIGN.md section 4 "Seeding and chaining" -- canonical k-mers,
+    the invertible hash, windows of w positions, every position that attains a window's minimum -- ascending by (seq, pos).
+    -> dict(hash (np.uint64), seq, pos (np.uint32), strand (np.uint8)).  Own specification: parity with minimap2's seeds is not
+    pinned."""
+    seqs, bases, off = _flat_seqs(seqs)
+    cap = 1024 if cap is None else int(cap)
+    n = C.c_uint64(0)
+    while True:
+        size = max(cap, 1)
+        h, s, p, st = np.zeros(size, np.uint64), np.zeros(size, np.uint32), np.zeros(size, np.uint32), np.zeros(size, np.uint8)
+        rc = ffi.lib().jtk_lc_sketch(len(seqs), u8p(bases), u64p(off), int(k), int(w), u64p(h), u32p(s), u32p(p), u8p(st), cap, C.byref(n), device)
+        if rc == -1 and n.value > cap:
+            cap = n.value
+            continue
+        break
+    check(rc)
+    m = n.value
+    return dict(hash=h[:m].copy(), seq=s[:m].copy(), pos=p[:m].copy(), strand=st[:m].copy())
+
+
+def map_reads(targets, queries, k=15, w=10, max_occ=200, max_gap=100, min_seeds=4, skip_self=False, device=0, cap=None):
+    """jtk_lc_map_reads: where every target (a chunk; bytes) lies in every query (a read; bytes) -- what the reference asks an
+    external minimap2 process (encode/mod.rs:41-64, :315-355).  Minimizers of both sides (sketch), hits of equal hash (hashes that
+    occur more than max_occ times among the targets are not used), diag = q' - tpos on the oriented query, single-linkage
+    clusters along the diagonal (a gap above max_gap starts a new one), one placement per cluster of at least min_seeds distinct
+    target positions.  skip_self: query i against target i yields nothing (minimap2's -X).
+    -> np.ndarray of ffi.MAP_PLACEMENT_DT in the order (query, target, reverse after forward, diag_lo).  cap: the capacity offered
+    first (default 1,024; more placements are fetched with a second call).  A placement is a seed cluster, not an alignment:
+    map_trials and encode_nodes make a node of it.  Own specification: parity with minimap2's choice of
+    seeds and chains is not pinned."""
+    _, tb, toff = _flat_seqs(targets)
+    _, qb, qoff = _flat_seqs(queries)
+    params = np.array([(int(k), int(w), int(max_occ), int(max_gap), int(min_seeds), 1 if skip_self else 0)], dtype=ffi.MAP_PARAMS_DT)
+    cap = 1024 if cap is None else int(cap)
+    n = C.c_uint64(0)
+    while True:
+        out = np.zeros(max(cap, 1), dtype=ffi.MAP_PLACEMENT_DT)
+        rc = ffi.lib().jtk_lc_map_reads(len(toff) - 1, u8p(tb), u64p(toff), len(qoff) - 1, u8p(qb), u64p(qoff), params.ctypes.data, out.ctypes.data,
+                                        cap, C.byref(n), device)
+        if rc == -1 and n.value > cap:
+            cap = n.value
+            continue
+        break
+    check(rc)
+    return out[:n.value].copy()
+
+
+def map_timing():
+    """jtk_lc_debug_map_timing (include/jtk_lc_debug.h): HIP-event ms of the last map_reads call's six phases, two counts, and
+    the ms of the two sketch kernels alone (the sketch phase also holds the upload and a wait)"""
+    out = (C.c_double * 10)()
+    ffi.lib().jtk_lc_debug_map_timing(out)
+    return dict(sketch_ms=out[0], index_ms=out[1], hits_ms=out[2], order_ms=out[3], chain_ms=out[4], compact_ms=out[5],
+                n_minimizers=int(out[6]), n_hits=int(out[7]), sketch_kernel_ms=out[8])
+
+
+ALLOWED_END_GAP = 25     # encode/mod.rs:14
+
+
+def map_trials(placements, query_lens, target_lens, sim_thr):
+    """The window of a read that encode_node is tried on for every placement of map_reads; pure host arithmetic, no GPU.  The
+    chunk's ends are projected along the placement onto the oriented read: est_start = oq_start - tstart, est_end = oq_end +
+    (tlen - tend).  A placement whose estimate leaves the read by more than ALLOWED_END_GAP bases at either end is dropped -- the
+    reference's filter `tstart < 25 && tlen - tend < 25` (encode/mod.rs:46) asks the aligner to have reached the chunk's ends,
+    a seed cluster cannot, so the question becomes whether the read holds the whole chunk.  The estimate is widened by
+    ceil(OFFSET_FACTOR * tlen) per side (as fill_trials does), clipped to the read and turned into forward coordinates, as
+    jtk_encode_trial_t wants them.  -> list of (index of the placement, start, end, is_forward, sim_thr)."""
+    import math
+    out = []
+    for i, p in enumerate(placements):
+        qlen, tlen = int(query_lens[int(p["query"])]), int(target_lens[int(p["target"])])
+        est_start = int(p["oq_start"]) - int(p["tstart"])
+        est_end = int(p["oq_end"]) + (tlen - int(p["tend"]))
+        if est_start < -ALLOWED_END_GAP or est_end > qlen + ALLOWED_END_GAP:
+            continue
+        offset = math.ceil(OFFSET_FACTOR * float(tlen))
+        start, end = max(est_start - offset, 0), min(est_end + offset, qlen)
+        if not start < end:
+            continue
+        forward = bool(p["is_forward"])
+        if not forward:
+            start, end = qlen - end, qlen - start
+        out.append((i, start, end, 1 if forward else 0, float(sim_thr)))
+    return out
+
+
 def _fill_reads(node_off, nodes):
     nodes = np.ascontiguousarray(nodes, dtype=ffi.FILL_NODE_DT)
     node_off = np.ascontiguousarray(node_off, dtype=np.uint64)

@@ -14,7 +14,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 EXPORTS_MAP = os.path.join(CSRC, "exports.map")  # only jtk_lc_* leaves the library
 
 SOURCES = ["phmm_kernels.hip", "phmm_sweep.hip", "phmm_pair.hip", "phmm_wide.hip", "polish_kernels.hip", "filter_kernels.hip", "mcmc_kernels.hip", "session.hip",
-           "session_split.hip", "session_stages.hip", "session_refit.hip", "session_features.hip", "session_trace.hip", "filter_seam.hip", "gains.hip", "correction.hip", "squish.hip", "purge.hip", "settle.hip", "fill.hip", "mask.hip",
+           "session_split.hip", "session_stages.hip", "session_refit.hip", "session_features.hip", "session_trace.hip", "filter_seam.hip", "gains.hip", "correction.hip", "squish.hip", "purge.hip", "settle.hip", "fill.hip", "mask.hip", "map.hip",
            "guided.hip", "gpolish.hip", "encode_nodes.hip", "encode_edges.hip", "io_kernels.hip", "align_kernels.hip", "host_api.cpp"]
 SYNTH_SOURCES = ["synth.cpp"]
 # -ffp-contract=off: device f64 arithmetic must round exactly like the reference (no implicit fma);

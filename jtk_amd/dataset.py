@@ -949,9 +949,109 @@ def repetitiveness(ds_or_kmers, seqs, device=0):
     return api.repetitiveness(seqs, annot["k"], annot["kmers"], device=device)
 
 
+def encode_by_map(ds, sim_thr, device=0, **map_params):
+    """The counterpart of encode_by_mm2 + encode_by (encode/mod.rs:41-139) on the parsed JSON object `ds` (modified in place: only
+    encoded_reads is written).  Where the reference pipes every raw read through minimap2 and makes a node of every PAF line whose
+    alignment reaches within 25 bases of the chunk's ends at an identity above 1 - sim_thr, this
+      1. maps every raw read against selected_chunks (api.map_reads; map_params are its k, w, max_occ, max_gap, min_seeds),
+      2. turns every placement into a window of the read (api.map_trials) with cons = the chunk's own sequence,
+      3. runs all windows through one api.encode_nodes call (encode_node, deletion_fill.rs:451-566: the alignment, the identity
+         and edge tests against sim_thr, the trimmed query, the ops against the chunk),
+      4. makes a Node (cluster 0) of every accepted trial,
+      5. keeps, where two accepted trials of one read and chunk overlap by more than half the chunk, the better score (of equal
+         scores the first in placement order),
+      6. settles every read's nodes in one api.settle_nodes call in mode SETTLE_BY_CHUNK (the sorts and remove_slippy_alignment of
+         encode_read_to_nodes_by_paf, :133-138, followed by remove_overlapping_encoding as that entry point always does),
+      7. rebuilds gaps and edges (nodes_to_encoded_read); reads without a node are dropped (:75-79).
+    The mapper and the guided passes follow this build's own specifications: parity with minimap2's
+    alignments is not pinned.  Returns the number of trials that were tried."""
+    chunks, reads = ds["selected_chunks"], ds["raw_reads"]
+    chunk_seqs = [c["seq"].upper().encode("latin-1") for c in chunks]
+    read_seqs = [r["seq"].encode("latin-1") for r in reads]
+    with _Clock("map_reads"):
+        placed = api.map_reads(chunk_seqs, read_seqs, device=device, **map_params)
+    picks = api.map_trials(placed, [len(s) for s in read_seqs], [len(s) for s in chunk_seqs], sim_thr)
+    ds["encoded_reads"] = []
+    if not picks:
+        return 0
+    read_off = np.zeros(len(read_seqs) + 1, dtype=np.int64)
+    read_off[1:] = np.cumsum([len(s) for s in read_seqs])
+    chunk_off = np.zeros(len(chunk_seqs) + 1, dtype=np.int64)
+    chunk_off[1:] = np.cumsum([len(s) for s in chunk_seqs])
+    read_bases = np.frombuffer(b"".join(read_seqs), dtype=np.uint8)
+    chunk_bases = np.frombuffer(b"".join(chunk_seqs), dtype=np.uint8)
+    trials = np.zeros(len(picks), dtype=ffi.ENCODE_TRIAL_DT)
+    for t, (i, start, end, forward, thr) in enumerate(picks):
+        r, c = int(placed[i]["query"]), int(placed[i]["target"])
+        trials[t] = (read_off[r], start, end, forward, len(chunk_seqs[c]), chunk_off[c], chunk_off[c], len(chunk_seqs[c]), 0, thr)
+    with _Clock("encode_nodes"):
+        enc = api.encode_nodes(trials, read_bases, chunk_bases, chunk_bases, device=device, raise_on_trial_failure=False)
+    per_read = {}
+    for t, (i, start, end, forward, _) in enumerate(picks):
+        res = enc["result"][t]
+        if int(res["status"]) != 0 or int(res["verdict"]) != ffi.ENCODE_ACCEPTED:
+            continue                                       # (a trial the device refuses is a trial that fails: encode_node's None)
+        r, c = int(placed[i]["query"]), int(placed[i]["target"])
+        window = api._oriented_window(read_bases, int(read_off[r]), start, end, forward)
+        query = window[int(res["trim_head"]):len(window) - int(res["trim_tail"])]
+        k = int(chunks[c]["cluster_num"])
+        node = {"position_from_start": int(res["position_from_start"]), "chunk": chunks[c]["id"], "cluster": 0, "seq": query.decode("ascii"),
+                "is_forward": bool(forward), "cigar": ops_to_cigar(enc["ops"][int(enc["ops_off"][t]):int(enc["ops_off"][t + 1])]),
+                "posterior": [math.log(1.0 / max(k, 1))] * k}                                        # Node::new, lib.rs:723-731
+        per_read.setdefault(r, []).append((node, int(res["score"]), len(chunk_seqs[c])))
+    kept = {r: _drop_overlapping_trials(found) for r, found in per_read.items()}
+    order = sorted(kept)
+    node_off, rec, ops, ops_off = _settle_arrays([kept[r] for r in order])
+    with _Clock("settle_nodes"):
+        out = api.settle_nodes(node_off, rec, ops, ops_off, mode=ffi.SETTLE_BY_CHUNK, device=device)
+    if out["rc"] != 0:
+        raise ValueError("encode_by_map: a node without ops")
+    for i, r in enumerate(order):
+        read = {"id": reads[r]["id"], "nodes": [kept[r][int(j)] for j in out["order"][i]]}
+        nodes_to_encoded_read(read, reads[r]["seq"])
+        ds["encoded_reads"].append({key: read[key] for key in ("id", "original_length", "leading_gap", "trailing_gap", "edges", "nodes")})
+    return len(picks)
+
+
+def _drop_overlapping_trials(found):
+    """found: (node, score, chunk length) of a read's accepted trials, in placement order.  Of two nodes of one chunk whose spans in
+    the read overlap by more than half the chunk, the better score stays (the first where they are equal); -> the nodes left"""
+    kept = []
+    for node, score, chunk_len in found:
+        start, end = node["position_from_start"], node["position_from_start"] + len(node["seq"])
+        rival = None
+        for j, (other, other_score, _) in enumerate(kept):
+            lo, hi = max(start, other["position_from_start"]), min(end, other["position_from_start"] + len(other["seq"]))
+            if other["chunk"] == node["chunk"] and 2 * (hi - lo) > chunk_len:
+                rival = j
+                break
+        if rival is None:
+            kept.append((node, score, chunk_len))
+        elif kept[rival][1] < score:
+            kept[rival] = (node, score, chunk_len)
+    return [k[0] for k in kept]
+
+
+def is_uppercase(read):
+    """encode::is_uppercase (encode/mod.rs:357-367)"""
+    upper = lambda s: all("A" <= c <= "Z" for c in s)   # noqa: E731
+    return all(upper(n["seq"]) for n in read["nodes"]) and all(upper(e["label"]) for e in read["edges"])
+
+
+def encode(ds, sim_thr, sd_of_error, device=0, **map_params):
+    """Encode::encode (encode/mod.rs:19-39) on the parsed JSON object `ds` (modified in place): encode_by_map in the place of
+    encode_by_mm2, correct_chunk_deletion with sim_thr and sd_of_error, and the reference's assertion that every node and edge
+    label is upper case.  Returns the ids of the chunks that gained a node in the second step."""
+    encode_by_map(ds, sim_thr, device=device, **map_params)
+    found = correct_chunk_deletion(ds, sim_thr=sim_thr, stddev_of_error=sd_of_error, device=device) if ds["encoded_reads"] else []
+    if not all(is_uppercase(r) for r in ds["encoded_reads"]):
+        raise ValueError("encode: a node or an edge label that is not upper case (the reference asserts)")
+    return found
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--stage", default="local_clustering", choices=("local_clustering", "correct_clustering", "squish_erroneous_clusters", "corrected", "realign", "purge_diverged_nodes", "fill_candidates", "consensus_sequences", "correct_deletion", "mask_repeat"),
+    ap.add_argument("--stage", default="local_clustering", choices=("local_clustering", "correct_clustering", "squish_erroneous_clusters", "corrected", "realign", "purge_diverged_nodes", "fill_candidates", "consensus_sequences", "correct_deletion", "mask_repeat", "encode"),
                     help="which JTK stage to run on the file (jtk local_clustering / jtk correct_clustering); "
                          "squish_erroneous_clusters: the step JTK runs in front of the correction, with its default "
                          "configuration; corrected: that step, then correct_clustering (cli/src/pipeline.rs:174-175); realign: "
@@ -965,7 +1065,10 @@ def main(argv=None):
                          "`ds.correct_deletion` without re-clustering (deletion_fill.rs:36-44: the filling rounds, then purge_largeindel "
                          "twice), the chunk ids that changed go to stderr; the guided passes and the polish are this build's own; "
                          "mask_repeat: `ds.mask_repeat` (repeat_masking.rs:135-158, the pipeline's first step) with --kmersize, "
-                         "--top-freq and --min-count; -v writes its three MASKREPEAT rows")
+                         "--top-freq and --min-count; -v writes its three MASKREPEAT rows; encode: `ds.encode` (encode/mod.rs:19-39) "
+                         "with --sim-thr and --sd-of-error: the reads are mapped onto selected_chunks by this build's own minimizer "
+                         "mapper in the place of minimap2 (--map-k, --map-w; parity with minimap2 is not pinned), encoded, and "
+                         "correct_chunk_deletion fills in what the mapping missed")
     ap.add_argument("input", help="DataSet JSON ('-' = stdin)")
     ap.add_argument("output", help="DataSet JSON ('-' = stdout)")
     ap.add_argument("--chunks", default="", help="comma-separated chunk ids (local_clustering_selected); default: all")
@@ -973,6 +1076,11 @@ def main(argv=None):
     ap.add_argument("--kmersize", type=int, default=12, help="mask_repeat: k (example.toml: 12)")
     ap.add_argument("--top-freq", type=float, default=0.001, help="mask_repeat: the fraction of the repeated k-mers to mask (0.001)")
     ap.add_argument("--min-count", type=int, default=10, help="mask_repeat: k-mers counted this often or less are not masked (10)")
+    ap.add_argument("--sim-thr", type=float, default=None, help="encode: the error rate a node may have (required there)")
+    ap.add_argument("--sd-of-error", type=float, default=None,
+                    help="encode: the standard deviation of the error rate (default: the median correct_chunk_deletion estimates)")
+    ap.add_argument("--map-k", type=int, default=15, help="encode: the mapper's k-mer size (15)")
+    ap.add_argument("--map-w", type=int, default=10, help="encode: the mapper's minimizer window (10)")
     ap.add_argument("--no-refit", action="store_true",
                     help="skip update_models_on_both_strands (mod.rs:58): cluster with model_param as found in the file")
     ap.add_argument("--recluster", action="store_true",
@@ -1009,6 +1117,12 @@ def main(argv=None):
     elif args.stage == "mask_repeat":
         validate(ds)
         mask_repeat(ds, k=args.kmersize, freq=args.top_freq, min_count=args.min_count, device=args.device, record=record)
+    elif args.stage == "encode":
+        validate(ds)
+        if args.sim_thr is None:
+            ap.error("--stage encode needs --sim-thr")
+        encode(ds, args.sim_thr, args.sd_of_error, device=args.device, k=args.map_k, w=args.map_w)
+        sys.stderr.write("ENCODE\tEncoded\t%d\t%d\n" % (len(ds["encoded_reads"]), len(ds["raw_reads"])))
     elif args.stage == "fill_candidates":
         ds = fill_candidates(ds, device=args.device)   # the report takes the data set's place in the output
     elif args.stage == "consensus_sequences":

@@ -159,11 +159,16 @@ SETTLE_DROPPED = 0xffffffff   # order[] behind a read's survivors
 MASK_REPORT_DT = np.dtype([("n_bases", "<u8"), ("n_kmers", "<u8"), ("n_distinct", "<u8"), ("n_singleton", "<u8"), ("n_masked_kmers", "<u8"),
                            ("n_lower", "<u8"), ("thr", "<u4"), ("takes_all", "<u4")])
 MASK_MAX_K = 31
+# jtk_map_params_t / jtk_map_placement_t (jtk_lc_map_reads)
+MAP_PARAMS_DT = np.dtype([(n, "<u4") for n in ("k", "w", "max_occ", "max_gap", "min_seeds", "skip_self")])
+MAP_PLACEMENT_DT = np.dtype([(n, "<u4") for n in ("query", "target", "is_forward", "n_seeds", "qstart", "qend", "oq_start", "oq_end", "tstart", "tend")]
+                            + [("diag_lo", "<i4"), ("diag_hi", "<i4")])
+MAP_MAX_K, MAP_MAX_W, MAP_MAX_TARGET_LEN, MAP_MAX_QUERY_LEN, MAP_MAX_TARGETS = 31, 64, 65535, 4000000, 1 << 25
 
 # every symbol declared in include/jtk_lc.h (tests check the library exports them)
 EXPORTED_SYMBOLS = (
     "jtk_lc_cluster_chunks", "jtk_lc_cluster_chunks_multi", "jtk_lc_cluster_polished", "jtk_lc_polish_chunks", "jtk_lc_align_reads", "jtk_lc_align_reads_mode", "jtk_lc_modification_table",
-    "jtk_lc_cluster_features", "jtk_lc_estimate_gains", "jtk_lc_estimate_minimum_gain", "jtk_lc_fit_model", "jtk_lc_correct_clustering", "jtk_lc_squish_clusters", "jtk_lc_squish_classify", "jtk_lc_node_errors", "jtk_lc_error_quantile", "jtk_lc_estimate_error_rate", "jtk_lc_purge_diverged", "jtk_lc_settle_nodes", "jtk_lc_mask_repeats", "jtk_lc_repetitive_kmers", "jtk_lc_repetitiveness", "jtk_lc_fill_candidates", "jtk_lc_align_guided", "jtk_lc_polish_guided", "jtk_lc_encode_nodes", "jtk_lc_encode_edges", "jtk_lc_trim_cache", "jtk_lc_pileup_sort_key", "jtk_lc_normalize_pileup", "jtk_lc_strerror",
+    "jtk_lc_cluster_features", "jtk_lc_estimate_gains", "jtk_lc_estimate_minimum_gain", "jtk_lc_fit_model", "jtk_lc_correct_clustering", "jtk_lc_squish_clusters", "jtk_lc_squish_classify", "jtk_lc_node_errors", "jtk_lc_error_quantile", "jtk_lc_estimate_error_rate", "jtk_lc_purge_diverged", "jtk_lc_settle_nodes", "jtk_lc_mask_repeats", "jtk_lc_repetitive_kmers", "jtk_lc_repetitiveness", "jtk_lc_map_reads", "jtk_lc_sketch", "jtk_lc_fill_candidates", "jtk_lc_align_guided", "jtk_lc_polish_guided", "jtk_lc_encode_nodes", "jtk_lc_encode_edges", "jtk_lc_trim_cache", "jtk_lc_pileup_sort_key", "jtk_lc_normalize_pileup", "jtk_lc_strerror",
     "jtk_lc_last_error", "jtk_lc_version", "jtk_lc_device_ok", "jtk_lc_last_timing",
     "jtk_lc_session_create", "jtk_lc_session_run", "jtk_lc_session_fetch", "jtk_lc_session_destroy", "jtk_lc_session_trace",
 )
@@ -175,7 +180,7 @@ DEBUG_SYMBOLS = (
     "jtk_lc_debug_guided_scratch_cap", "jtk_lc_debug_guided_timing", "jtk_lc_debug_encode_timing",
     "jtk_lc_debug_guided_table", "jtk_lc_debug_gpolish_timing", "jtk_lc_debug_edges_timing",
     "jtk_lc_debug_session_lane", "jtk_lc_debug_lane_hold", "jtk_lc_debug_lane_state", "jtk_lc_debug_filter",
-    "jtk_lc_debug_round_hold", "jtk_lc_debug_round_state", "jtk_lc_debug_session_passes", "jtk_lc_debug_settle_timing", "jtk_lc_debug_mask_timing",
+    "jtk_lc_debug_round_hold", "jtk_lc_debug_round_state", "jtk_lc_debug_session_passes", "jtk_lc_debug_settle_timing", "jtk_lc_debug_mask_timing", "jtk_lc_debug_map_timing",
 )
 DEBUG_FILTER_TABLE, DEBUG_FILTER_ROWS_FUSED, DEBUG_FILTER_ROWS_TABLE = 0, 1, 2   # modes of jtk_lc_debug_filter
 DEBUG_FILTER_TRACE_WORDS = 66   # JTK_LC_DEBUG_FILTER_TRACE_WORDS
@@ -254,6 +259,10 @@ def lib():
         sig("jtk_lc_repetitive_kmers", i32, sz, PU8, PU64, u32, PU64, u64, PU64, i32)
         sig("jtk_lc_repetitiveness", i32, sz, PU8, PU64, u32, PU64, u64, PU32, PU32, i32)
         sig("jtk_lc_debug_mask_timing", None, PD)
+    if hasattr(L, "jtk_lc_map_reads"):      # (likewise)
+        sig("jtk_lc_map_reads", i32, sz, PU8, PU64, sz, PU8, PU64, vp, vp, u64, PU64, i32)
+        sig("jtk_lc_sketch", i32, sz, PU8, PU64, u32, u32, PU64, PU32, PU32, PU8, u64, PU64, i32)
+        sig("jtk_lc_debug_map_timing", None, PD)
     sig("jtk_lc_fill_candidates", i32, sz, PU64, vp, PU8, PU32, PU32, PU64, vp, sz, PSZ, i32)
     sig("jtk_lc_debug_fill_pairs", i32, sz, PU64, vp, sz, PU32, PU32, PI32, PI32, PU8, PU64, PU32, sz, PSZ, i32)
     sig("jtk_lc_debug_fill_timing", None, PD)

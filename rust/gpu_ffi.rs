@@ -75,6 +75,19 @@ pub struct JtkMaskReport {
     pub n_bases: u64, pub n_kmers: u64, pub n_distinct: u64, pub n_singleton: u64, pub n_masked_kmers: u64, pub n_lower: u64,
     pub thr: u32, pub takes_all: u32,
 }
+// the mapper's parameters (minimap2's -k, -w, -f as a count, the chaining gap, -n, -X) and one seed cluster of a read on a chunk
+#[repr(C)] #[derive(Clone, Copy, Debug)]
+pub struct JtkMapParams {
+    pub k: u32, pub w: u32, pub max_occ: u32, pub max_gap: u32, pub min_seeds: u32, pub skip_self: u32,
+}
+#[repr(C)] #[derive(Clone, Copy, Default, Debug)]
+pub struct JtkMapPlacement {
+    pub query: u32, pub target: u32, pub is_forward: u32, pub n_seeds: u32,
+    pub qstart: u32, pub qend: u32,
+    pub oq_start: u32, pub oq_end: u32,
+    pub tstart: u32, pub tend: u32,
+    pub diag_lo: i32, pub diag_hi: i32,
+}
 pub const JTK_SETTLE_STATS_ONLY: c_int = 0;
 pub const JTK_SETTLE_BY_CHUNK_POS: c_int = 1;
 pub const JTK_SETTLE_BY_CHUNK: c_int = 2;
@@ -218,6 +231,18 @@ extern "C" {
     pub fn jtk_lc_repetitiveness(
         n_seqs: usize, bases: *const u8, seq_off: *const u64, k: u32, kmers: *const u64, n_kmers: u64, rep_num: *mut u32,
         rep_den: *mut u32, device: c_int) -> c_int;
+    // what encode_by_mm2 asks of minimap2 (encode/mod.rs:41-64, :315-355; minimap2.rs): where a chunk lies in a read, by this
+    // library's own minimizer seeding and chaining (parity with minimap2's seeds and chains is not pinned).
+    // Placements in the order (query, target, strand, diag_lo); -1 with *n_placements = the need where cap is too small.
+    // (jtk_lc_debug_map_timing of jtk_lc_debug.h, the phases' times, is diagnostic and is not bound here.)
+    pub fn jtk_lc_map_reads(
+        n_targets: usize, target_bases: *const u8, target_off: *const u64, n_queries: usize, query_bases: *const u8,
+        query_off: *const u64, params: *const JtkMapParams, out: *mut JtkMapPlacement, cap: u64, n_placements: *mut u64,
+        device: c_int) -> c_int;
+    // the minimizers alone, ascending by (seq, pos), as parallel arrays; -1 with *n = the need where cap is too small
+    pub fn jtk_lc_sketch(
+        n_seqs: usize, bases: *const u8, seq_off: *const u64, k: u32, w: u32, hash: *mut u64, seq: *mut u32, pos: *mut u32,
+        strand: *mut u8, cap: u64, n: *mut u64, device: c_int) -> c_int;
     // get_pileup, ins_thr and check_insertion_head / _tail of correct_deletion_error (encode/deletion_fill.rs:301-337, 642-698,
     // 883-981) for every read with target[r] == 1 (null: every read); cands sorted by (read, slot, side, chunk, cluster, is_forward)
     pub fn jtk_lc_fill_candidates(

@@ -285,6 +285,31 @@ pub(crate) fn repetitiveness_gpu(ds: &definitions::DataSet, seqs: &[&[u8]]) -> V
     num.iter().zip(den.iter()).map(|(&n, &d)| n as f64 / d as f64).collect()
 }
 
+/// What `encode_by_mm2` (encode/mod.rs:41-64) gets from `mm2_alignment` (:315-355) and minimap2.rs -- every raw read written to a
+/// temporary FASTA and piped through an external minimap2 -- in one call: where each of `selected_chunks` lies in each raw read.
+/// A placement is a seed cluster of the library's own minimizer mapper (parity with minimap2's seeds and
+/// chains is not pinned), not an alignment: it carries no cigar.  The PAF filter of :46-60 -- `tstart < 25 && tlen - tend < 25`,
+/// then `1 - sim_thr < percent_identity` of the cg tag -- is therefore replaced: the caller projects the chunk's ends along the
+/// placement (est_start = oq_start - tstart, est_end = oq_end + tlen - tend), drops a placement whose estimate leaves the read by
+/// more than ALLOWED_END_GAP bases, widens the rest by ceil(0.1 * tlen) per side, and lets encode_nodes_gpu (encode_node) apply the
+/// identity and edge tests against sim_thr.  `skip_self`: chunk against chunk, as remove_overlapping_chunks maps them (-X).
+pub(crate) fn map_reads_gpu(chunks: &[&[u8]], reads: &[&[u8]], k: u32, skip_self: bool) -> Vec<JtkMapPlacement> {
+    let flat = |seqs: &[&[u8]]| { let (mut b, mut off) = (Vec::<u8>::new(), vec![0u64]);
+        for s in seqs.iter() { b.extend_from_slice(s); off.push(b.len() as u64); } (b, off) };
+    let ((tb, toff), (qb, qoff)) = (flat(chunks), flat(reads));
+    let params = JtkMapParams { k, w: 10, max_occ: 200, max_gap: 100, min_seeds: 4, skip_self: skip_self as u32 };
+    let (mut out, mut n) = (vec![JtkMapPlacement::default(); 4 * reads.len() + 1], 0u64);
+    loop {
+        let rc = unsafe { jtk_lc_map_reads(chunks.len(), tb.as_ptr(), toff.as_ptr(), reads.len(), qb.as_ptr(), qoff.as_ptr(), &params,
+            out.as_mut_ptr(), out.len() as u64, &mut n, /*device*/ 0) };
+        if rc == -1 && n as usize > out.len() { out.resize(n as usize, JtkMapPlacement::default()); continue; }
+        assert!(rc == 0, "{}", unsafe { std::ffi::CStr::from_ptr(jtk_lc_last_error()) }.to_string_lossy());
+        break;
+    }
+    out.truncate(n as usize);
+    out
+}
+
 /// `take_consensus_sequence` (encode/deletion_fill.rs:260-285) in one call: the nodes are bucketed by (chunk, cluster) in
 /// encoded_reads order, cluster 0 stands for the chunk's own sequence, and every other bucket is polished from the chunk's
 /// sequence: the global ops of jtk_lc_align_reads, then jtk_lc_polish_guided with radius = read_type.band_width(len) (:277).
