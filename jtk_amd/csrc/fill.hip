@@ -433,12 +433,6 @@ __global__ void summarise_kernel(uint64_t n_rec, const uint64_t *hi, const uint6
     }
 }
 
-unsigned fc_bits(uint64_t top) {  // bits that hold 0 ..= top
-    unsigned b = 1;
-    while (b < 64 && (top >> b)) b++;
-    return b;
-}
-
 // The reads on the host, then on the device.
 struct Reads {
     uint32_t n_reads = 0, n_nodes = 0, n_keys = 0, max_nodes = 0, max_target_nodes = 0;
@@ -452,9 +446,7 @@ struct Reads {
 
 int fc_check(size_t n_reads, const uint64_t *node_off, const jtk_fill_node_t *nodes) {
     if (!node_off) return jtk_fail(JTK_ERR_INVALID_ARG, "null argument");
-    if (node_off[0] != 0) return jtk_fail(JTK_ERR_INVALID_ARG, "node_off[0] is not 0");
-    for (size_t r = 0; r < n_reads; r++)
-        if (node_off[r + 1] < node_off[r]) return jtk_fail(JTK_ERR_INVALID_ARG, "node_off decreases");
+    if (int rc = jtk_check_offsets(n_reads, node_off, "node_off")) return rc;
     if (node_off[n_reads] && !nodes) return jtk_fail(JTK_ERR_INVALID_ARG, "null argument");
     for (size_t r = 0; r < n_reads; r++)
         if (node_off[r + 1] - node_off[r] > FC_MAX_NODES) return jtk_fail(JTK_ERR_UNSUPPORTED, "a read with more than 65,535 nodes");
@@ -593,7 +585,7 @@ extern "C" int jtk_lc_fill_candidates(size_t n_reads, const uint64_t *node_off, 
         JTK_HIP_TRY(d_count.alloc(1));
         pair_emit_kernel<<<jtk_blocks(R.n_nodes, 4, 4096), 256, 0, st>>>(R.n_nodes, R.d_kid.cget(), d_read_of.cget(), d_order.cget(), d_seg.cget(),
                                                                         d_rec_off.cget(), d_raw.get());
-        const unsigned end_bit = 32 + fc_bits(R.n_reads);
+        const unsigned end_bit = 32 + jtk_bits(R.n_reads);
         JTK_HIP_TRY(tmp.run([&](void *t, size_t &bytes) {
             return rocprim::radix_sort_keys(t, bytes, d_raw.cget(), d_sorted.get(), (size_t)n_emit, 0u, end_bit, st);
         }));
@@ -664,7 +656,7 @@ extern "C" int jtk_lc_fill_candidates(size_t n_reads, const uint64_t *node_off, 
         JTK_HIP_TRY(d_pos.alloc(n_rec + 1));
         const uint32_t rec_grid = jtk_blocks(n_rec, 256, 4096);
         fc_iota_kernel<<<rec_grid, 256, 0, st>>>(n_rec, d_iota.get());
-        const unsigned lo_bits = 2 + fc_bits(R.n_keys), hi_bits = 17 + fc_bits(R.n_reads);
+        const unsigned lo_bits = 2 + jtk_bits(R.n_keys), hi_bits = 17 + jtk_bits(R.n_reads);
         // least significant part first; both sorts are stable.  Bit 0 of lo (an offset is present) is no part of the key.
         JTK_HIP_TRY(tmp.run([&](void *t, size_t &bytes) {
             return rocprim::radix_sort_pairs(t, bytes, d_lo.cget(), d_lo_s.get(), d_iota.cget(), d_perm1.get(), (size_t)n_rec, 1u, lo_bits, st);

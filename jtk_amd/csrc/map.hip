@@ -28,6 +28,7 @@
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
 #include "jtk_lc_debug.h"
+#include "kmer_tile.h"
 #include "prim_host.h"
 
 namespace {
@@ -50,7 +51,7 @@ thread_local double g_map_timing[10];  // ms of the six phases; minimizers, hits
 struct SketchTile {
     uint8_t raw[MP_BASES];
     uint8_t strand[MP_SPAN];
-    uint32_t fwd[MP_W2 + 2], bad[MP_W1 + 1];  // the words behind the streams are 0: a field may start in the last word
+    uint32_t fwd[MP_W2 + 2], bad[MP_W1 + 1];  // each stream and its zero words (kmer_tile.h)
     uint64_t hash[MP_SPAN], wmin[MP_SPAN];
 };
 
@@ -94,39 +95,14 @@ __global__ void __launch_bounds__(MP_THREADS) sketch_kernel(const uint8_t *bases
     const uint32_t n_hash = h_end - a;                                                        // <= MP_TILE + 2 w - 2 <= MP_SPAN
     const uint32_t own_end = n - s > MP_TILE ? s + MP_TILE : n;
     const uint32_t win_end = own_end < n_win ? own_end : n_win;                               // windows a .. win_end hold an owned position
-    const uint32_t left = len - a;
-    const uint8_t *seq = bases + so;
-    for (uint32_t i = threadIdx.x; i < MP_BASES; i += MP_THREADS) T.raw[i] = i < left ? seq[(uint64_t)a + i] : (uint8_t)0;
+    jtk_stage_bytes<MP_BASES, MP_THREADS>(T.raw, bases + so, len, a);
     __syncthreads();
-    for (uint32_t t = threadIdx.x; t < MP_W2 + 2; t += MP_THREADS) {
-        uint32_t f = 0;
-        if (t < MP_W2) {
-#pragma unroll
-            for (uint32_t i = 0; i < 16; i++) {
-                const uint32_t u = T.raw[16 * t + i] & 0xdfu;  // folds the two cases of a letter; no other byte becomes A, C, G or T
-                f |= (u == 'C' ? 1u : u == 'G' ? 2u : u == 'T' ? 3u : 0u) << (2 * i);
-            }
-        }
-        T.fwd[t] = f;
-    }
-    for (uint32_t t = threadIdx.x; t < MP_W1 + 1; t += MP_THREADS) {
-        uint32_t b = 0;
-        if (t < MP_W1) {
-#pragma unroll
-            for (uint32_t i = 0; i < 32; i++) {
-                const uint32_t u = T.raw[32 * t + i] & 0xdfu;
-                b |= (u == 'A' || u == 'C' || u == 'G' || u == 'T' ? 0u : 1u) << i;
-            }
-        }
-        T.bad[t] = b;
-    }
+    jtk_pack2<MP_W2, MP_THREADS>({T.fwd}, [&](uint32_t i) { return jtk_base_code(T.raw[i]); });
+    jtk_pack1<MP_W1, MP_THREADS>(T.bad, [&](uint32_t i) { return jtk_no_base(T.raw[i]); });
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < n_hash; i += MP_THREADS) {  // i + k <= MP_SPAN + 30 <= MP_BASES
-        const uint32_t w2 = i >> 4, s2 = (i & 15u) * 2, w1 = i >> 5, s1 = i & 31u;
-        uint64_t f = ((uint64_t)T.fwd[w2] | ((uint64_t)T.fwd[w2 + 1] << 32)) >> s2;
-        if (s2) f |= (uint64_t)T.fwd[w2 + 2] << (64 - s2);
-        f &= (1ull << (2 * k)) - 1;
-        const uint64_t no_base = (((uint64_t)T.bad[w1] | ((uint64_t)T.bad[w1 + 1] << 32)) >> s1) & ((1ull << k) - 1);
+        const uint64_t f = jtk_field2(T.fwd, i, k);
+        const uint32_t no_base = jtk_field1(T.bad, i, k);
         const uint64_t rc = mp_revcomp(f, k);
         const bool valid = !no_base && f != rc;
         T.hash[i] = valid ? mp_hash(f < rc ? f : rc, k) : MP_NONE;
@@ -172,19 +148,6 @@ __global__ void __launch_bounds__(MP_THREADS) sketch_kernel(const uint8_t *bases
     }
 }
 
-template <typename T>
-__device__ __forceinline__ uint64_t mp_lower_bound(const T *list, uint64_t n, T x) {
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (list[mid] < x)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    return lo;
-}
-
 // The index as the hit kernels see it: the targets' locations in hash order, the distinct hashes, their counts and first records.
 struct Index {
     const uint64_t *loc, *uniq;
@@ -194,7 +157,7 @@ struct Index {
 
 // the run of query minimizer (h, qseq): 0 where the hash is not indexed or occurs more than max_occ times
 __device__ __forceinline__ uint32_t mp_run(const Index &X, uint64_t h, uint32_t *first) {
-    const uint64_t n = *X.n_runs, at = mp_lower_bound(X.uniq, n, h);
+    const uint64_t n = *X.n_runs, at = jtk_lower_bound(X.uniq, n, h);
     if (at >= n || X.uniq[at] != h || X.count[at] > X.max_occ) return 0;
     *first = X.first[at];
     return X.count[at];
@@ -244,7 +207,7 @@ __global__ void fill_kernel(Index X, const uint64_t *q_hash, const uint64_t *q_l
 // seg[q] = the first hit of query q (q = n_queries: the total): the segments of the ordering sort
 __global__ void segment_kernel(const uint64_t *q_loc, uint64_t n, const uint64_t *hit_off, uint64_t n_queries, uint32_t *seg) {
     for (uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; q <= n_queries; q += (uint64_t)gridDim.x * blockDim.x)
-        seg[q] = (uint32_t)hit_off[mp_lower_bound(q_loc, n, q << 32)];
+        seg[q] = (uint32_t)hit_off[jtk_lower_bound(q_loc, n, q << 32)];
 }
 
 __global__ void head_kernel(const uint64_t *key, const uint32_t *qid, uint64_t n, uint32_t max_gap, uint32_t *head) {
@@ -371,9 +334,7 @@ __global__ void place_kernel(Clusters C, uint64_t n, const uint32_t *slot, const
 // ---- the host side
 
 int mp_check_seqs(size_t n, const uint8_t *bases, const uint64_t *off, const char *what) {
-    if (off[0] != 0) return jtk_fail(JTK_ERR_INVALID_ARG, std::string(what) + "[0] is not 0");
-    for (size_t i = 0; i < n; i++)
-        if (off[i + 1] < off[i]) return jtk_fail(JTK_ERR_INVALID_ARG, std::string(what) + " decreases");
+    if (int rc = jtk_check_offsets(n, off, what)) return rc;
     if (off[n] && !bases) return jtk_fail(JTK_ERR_INVALID_ARG, "null argument");
     return 0;
 }
@@ -399,67 +360,34 @@ int mp_check_kw_limits(uint32_t k, uint32_t w) {
     return 0;
 }
 
-int mp_fits(uint64_t bytes, const char *what) {
-    size_t free_b = 0, total_b = 0;
-    JTK_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    if ((double)bytes > 0.8 * (double)free_b)
-        return jtk_fail(JTK_ERR_ALLOC, std::string(what) + " of this call is " + std::to_string(bytes) + " bytes, above 80 % of the device's " +
-                                           std::to_string(free_b) + " free bytes");
-    return 0;
-}
-
-uint32_t mp_bits(uint64_t largest) {
-    uint32_t b = 0;
-    while (b < 64 && (largest >> b)) b++;
-    return b ? b : 1;
-}
-
 // A set of sequences on the device and its minimizers: (hash, loc) as the sketch kernel appended them.
 struct Sketch {
-    DevArr<uint8_t> bases;
-    DevArr<uint64_t> off, hash, loc;
-    uint64_t n_kmers = 0, n = 0;
+    DevSeqs seqs;  // (no kmer_off: the minimizers are appended at a cursor)
+    DevArr<uint64_t> hash, loc;
+    uint64_t n = 0;
     size_t n_seqs = 0;
     float kernel_ms = 0.f;  // the sketch kernel alone (run()'s events)
 
-    static uint64_t positions(size_t n_seqs, const uint64_t *h_off, uint32_t k) {
-        uint64_t n = 0;
-        for (size_t r = 0; r < n_seqs; r++) n += h_off[r + 1] - h_off[r] >= k ? h_off[r + 1] - h_off[r] - k + 1 : 0;
-        return n;
-    }
-
     int run(size_t n_seqs_, const uint8_t *h_bases, const uint64_t *h_off, uint32_t k, uint32_t w, hipStream_t st) {
         n_seqs = n_seqs_;
-        std::vector<uint32_t> tile_seq, tile_start;
-        for (size_t r = 0; r < n_seqs; r++) {
-            const uint64_t len = h_off[r + 1] - h_off[r], n_pos = len >= k ? len - k + 1 : 0;
-            for (uint64_t s = 0; s < n_pos; s += MP_TILE) {
-                tile_seq.push_back((uint32_t)r);
-                tile_start.push_back((uint32_t)s);
-            }
-            n_kmers += n_pos;
-        }
-        if (int rc = mp_fits(h_off[n_seqs] + 8 * (uint64_t)(n_seqs + 1) + 8 * (uint64_t)tile_seq.size() + 16 * n_kmers, "the sketch")) return rc;
-        DevArr<uint32_t> d_tile_seq, d_tile_start;
+        const KmerPlan P = jtk_plan_kmers(n_seqs, h_off, k, MP_TILE, KMER_TILE_POSITIONS);
+        if (int rc = jtk_fits(DevSeqs::bytes(n_seqs, h_off, P, false) + 16 * P.n_kmers, "the sketch")) return rc;
         DevArr<unsigned long long> d_cursor;
-        int rc;
-        if ((rc = bases.upload(h_bases, h_off[n_seqs], st)) || (rc = off.upload(h_off, n_seqs + 1, st)) || (rc = d_tile_seq.upload(tile_seq, st)) ||
-            (rc = d_tile_start.upload(tile_start, st)))
-            return jtk_fail(rc, "device upload failed");
-        JTK_HIP_TRY(hash.alloc(n_kmers));
-        JTK_HIP_TRY(loc.alloc(n_kmers));
+        if (int rc = seqs.upload(n_seqs, h_bases, h_off, P, false, st)) return rc;
+        JTK_HIP_TRY(hash.alloc(P.n_kmers));
+        JTK_HIP_TRY(loc.alloc(P.n_kmers));
         JTK_HIP_TRY(d_cursor.alloc(1));
         JTK_HIP_TRY(d_cursor.zero(1, st));
         DevEvents around;
         JTK_HIP_TRY(around.create(2));
         JTK_HIP_TRY(hipEventRecord(around[0], st));
-        if (!tile_seq.empty())
-            sketch_kernel<<<(uint32_t)tile_seq.size(), MP_THREADS, 0, st>>>(bases.cget(), off.cget(), d_tile_seq.cget(), d_tile_start.cget(), k, w, hash.get(),
-                                                                          loc.get(), d_cursor.get());
+        if (seqs.n_tiles)
+            sketch_kernel<<<seqs.n_tiles, MP_THREADS, 0, st>>>(seqs.bases.cget(), seqs.off.cget(), seqs.tile_seq.cget(), seqs.tile_start.cget(), k, w,
+                                                             hash.get(), loc.get(), d_cursor.get());
         JTK_HIP_TRY(hipEventRecord(around[1], st));
         unsigned long long emitted = 0;
         JTK_HIP_TRY(d_cursor.download(&emitted, 1, st));
-        JTK_HIP_TRY(hipStreamSynchronize(st));  // a sort's size is a host argument (and the tiles' host arrays live until here)
+        JTK_HIP_TRY(hipStreamSynchronize(st));  // a sort's size is a host argument (and the plan's host arrays live until here)
         JTK_HIP_TRY(hipGetLastError());
         JTK_HIP_TRY(around.elapsed(0, 1, &kernel_ms));
         n = emitted;
@@ -473,7 +401,7 @@ struct Sketch {
         JTK_HIP_TRY(h2.alloc(n));
         JTK_HIP_TRY(l2.alloc(n));
         if (by_loc) {
-            const uint32_t end_bit = 32 + mp_bits(n_seqs ? n_seqs - 1 : 0);
+            const uint32_t end_bit = 32 + jtk_bits(n_seqs ? n_seqs - 1 : 0);
             JTK_HIP_TRY(tmp.run([&](void *t, size_t &bytes) {
                 return rocprim::radix_sort_pairs(t, bytes, loc.cget(), l2.get(), hash.cget(), h2.get(), (size_t)n, 0u, end_bit, st);
             }));
@@ -541,13 +469,13 @@ int mp_map(size_t n_targets, const uint8_t *target_bases, const uint64_t *target
     g_map_timing[7] = (double)n_hits;
     if (!n_hits) return 0;
     if (n_hits >> 32) return jtk_fail(JTK_ERR_UNSUPPORTED, std::to_string(n_hits) + " hits: 2^32 or more (lower max_occ)");
-    const uint32_t key_bits = 39 + mp_bits(n_targets - 1);
+    const uint32_t key_bits = 39 + jtk_bits(n_targets - 1);
     {  // keys twice, the queries' indices, the head flags and their scan, the (cluster, tpos) keys twice, rocprim's blocks
         size_t seg_tmp = 0, sort_tmp = 0;
         JTK_HIP_TRY(rocprim::segmented_radix_sort_keys(nullptr, seg_tmp, (const uint64_t *)nullptr, (uint64_t *)nullptr, (unsigned int)n_hits,
                                                        (unsigned int)n_queries, (const uint32_t *)nullptr, (const uint32_t *)nullptr, 0u, key_bits, s.st));
         JTK_HIP_TRY(rocprim::radix_sort_keys(nullptr, sort_tmp, (const uint64_t *)nullptr, (uint64_t *)nullptr, (size_t)n_hits, 0u, 48u, s.st));
-        if (int rc = mp_fits(n_hits * 44 + seg_tmp + sort_tmp + 4 * (uint64_t)(n_queries + 1), "the hit buffer")) return rc;
+        if (int rc = jtk_fits(n_hits * 44 + seg_tmp + sort_tmp + 4 * (uint64_t)(n_queries + 1), "the hit buffer")) return rc;
     }
     DevArr<uint64_t> d_key, d_sorted, d_seed_key, d_seed_sorted;
     DevArr<uint32_t> d_qid, d_seg, d_head, d_incl;
@@ -587,7 +515,7 @@ int mp_map(size_t n_targets, const uint8_t *target_bases, const uint64_t *target
     cluster_init_kernel<<<jtk_blocks(n_clusters, 256, 4096), 256, 0, s.st>>>(C, n_clusters);
     reduce_kernel<<<jtk_blocks(n_hits, 256, 4096), 256, 0, s.st>>>(d_sorted.cget(), d_incl.cget(), n_hits, C, d_seed_key.get());
     JTK_HIP_TRY(tmp.run([&](void *t, size_t &bytes) {
-        return rocprim::radix_sort_keys(t, bytes, d_seed_key.cget(), d_seed_sorted.get(), (size_t)n_hits, 0u, 16 + mp_bits(n_clusters - 1), s.st);
+        return rocprim::radix_sort_keys(t, bytes, d_seed_key.cget(), d_seed_sorted.get(), (size_t)n_hits, 0u, 16 + jtk_bits(n_clusters - 1), s.st);
     }));
     seeds_kernel<<<jtk_blocks(n_hits, 256, 4096), 256, 0, s.st>>>(d_seed_sorted.cget(), n_hits, C.seeds);
     JTK_HIP_TRY(hipEventRecord(late[1], s.st));

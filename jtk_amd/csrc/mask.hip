@@ -28,6 +28,7 @@
 #include <rocprim/iterator/transform_iterator.hpp>
 
 #include "jtk_lc_debug.h"
+#include "kmer_tile.h"
 #include "prim_host.h"
 #include "wave_util.h"
 
@@ -48,82 +49,32 @@ thread_local double g_mask_timing[4];  // ms: emit, sort, count and select, appl
 
 struct Tile {
     uint8_t raw[MK_STAGE];
-    uint32_t fwd[MK_W2 + 2], rev[MK_W2 + 2], low[MK_W1 + 1];  // the words behind the streams are 0: a field may start in the last word
+    uint32_t fwd[MK_W2 + 2], rev[MK_W2 + 2], low[MK_W1 + 1];  // each stream and its zero words (kmer_tile.h)
 };
-
-__device__ __forceinline__ uint32_t mk_fwd(uint32_t b) {
-    const uint32_t u = b & 0xdfu;  // folds the two cases of a letter; no other byte becomes A, C, G or T
-    return u == 'C' ? 1u : u == 'G' ? 2u : u == 'T' ? 3u : 0u;
-}
-__device__ __forceinline__ uint32_t mk_cmp(uint32_t b) {
-    const uint32_t u = b & 0xdfu;
-    return u == 'A' ? 3u : u == 'C' ? 2u : u == 'G' ? 1u : 0u;
-}
 
 // Bases a .. a + MK_STAGE of the read (0 behind its end) into the tile's streams, by the whole workgroup.  Local index i is the
 // read's base a + i; it sits at position i of fwd and low and at position MK_STAGE - 1 - i of rev.
 __device__ __forceinline__ void mk_stage(Tile &T, const uint8_t *read, uint32_t len, uint32_t a) {
-    const uint32_t left = len - a;  // a < len
-    for (uint32_t i = threadIdx.x; i < MK_STAGE; i += MK_THREADS) T.raw[i] = i < left ? read[(uint64_t)a + i] : (uint8_t)0;
+    jtk_stage_bytes<MK_STAGE, MK_THREADS>(T.raw, read, len, a);
     __syncthreads();
-    for (uint32_t w = threadIdx.x; w < MK_W2 + 2; w += MK_THREADS) {
-        uint32_t f = 0, r = 0;
-        if (w < MK_W2) {
-#pragma unroll
-            for (uint32_t i = 0; i < 16; i++) {
-                f |= mk_fwd(T.raw[16 * w + i]) << (2 * i);
-                r |= mk_cmp(T.raw[MK_STAGE - 1 - 16 * w - i]) << (2 * i);
-            }
-        }
-        T.fwd[w] = f;
-        T.rev[w] = r;
-    }
-    for (uint32_t w = threadIdx.x; w < MK_W1 + 1; w += MK_THREADS) {
-        uint32_t l = 0;
-        if (w < MK_W1) {
-#pragma unroll
-            for (uint32_t i = 0; i < 32; i++) {
-                const uint32_t b = T.raw[32 * w + i];
-                l |= (b >= 'a' && b <= 'z' ? 1u : 0u) << i;
-            }
-        }
-        T.low[w] = l;
-    }
+    jtk_pack2<MK_W2, MK_THREADS>({T.fwd, T.rev}, [&](uint32_t i) { return jtk_base_code(T.raw[i]); },
+                                 [&](uint32_t i) { return jtk_base_complement(T.raw[MK_STAGE - 1 - i]); });
+    jtk_pack1<MK_W1, MK_THREADS>(T.low, [&](uint32_t i) { return T.raw[i] >= 'a' && T.raw[i] <= 'z' ? 1u : 0u; });
     __syncthreads();
-}
-
-// k 2-bit codes from position pos of a stream: three words, two shifts
-__device__ __forceinline__ uint64_t mk_field2(const uint32_t *words, uint32_t pos, uint32_t k) {
-    const uint32_t w = pos >> 4, s = (pos & 15u) * 2;
-    uint64_t v = ((uint64_t)words[w] | ((uint64_t)words[w + 1] << 32)) >> s;
-    if (s) v |= (uint64_t)words[w + 2] << (64 - s);
-    return v & ((1ull << (2 * k)) - 1);
 }
 
 // the canonical k-mer of the window at local index q
 __device__ __forceinline__ uint64_t mk_kmer(const Tile &T, uint32_t q, uint32_t k) {
-    const uint64_t f = mk_field2(T.fwd, q, k), r = mk_field2(T.rev, MK_STAGE - q - k, k);
+    const uint64_t f = jtk_field2(T.fwd, q, k), r = jtk_field2(T.rev, MK_STAGE - q - k, k);
     return f < r ? f : r;
 }
 
-__device__ __forceinline__ bool mk_all_lower(const Tile &T, uint32_t q, uint32_t k) {
-    const uint32_t w = q >> 5, s = q & 31u;
-    const uint64_t v = ((uint64_t)T.low[w] | ((uint64_t)T.low[w + 1] << 32)) >> s;
-    const uint32_t all = (1u << k) - 1;
-    return ((uint32_t)v & all) == all;
-}
+__device__ __forceinline__ bool mk_all_lower(const Tile &T, uint32_t q, uint32_t k) { return jtk_field1(T.low, q, k) == (1u << k) - 1; }
 
 template <typename Key>
 __device__ __forceinline__ bool mk_member(const Key *list, uint64_t n, Key x) {
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (list[mid] < x)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    return lo < n && list[lo] == x;
+    const uint64_t at = jtk_lower_bound(list, n, x);
+    return at < n && list[at] == x;
 }
 
 // One workgroup per tile.  MK_EVERY: the k-mer of position p of read r goes to out[kmer_off[r] + p].  MK_LOWER / MK_MEMBER:
@@ -220,7 +171,7 @@ struct MoreThan {
 // create_mask's verdict over the ascending counts of the M k-mers counted more than once: v[0] = thr, v[1] = takes all,
 // v[2] = the index is out of range (the reference panics), v[3] = the mask is the k-mers counted more than v[3] times
 __global__ void verdict_kernel(const uint32_t *sorted, uint64_t m, uint64_t percentile, uint32_t min_count, uint32_t *v) {
-    uint64_t lo = 0, hi = m;  // below_min = the counts <= min_count
+    uint64_t lo = 0, hi = m;  // below_min = the counts <= min_count (not jtk_lower_bound of min_count + 1, which is 0 at 0xffffffff)
     while (lo < hi) {
         const uint64_t mid = (lo + hi) >> 1;
         if (sorted[mid] <= min_count)
@@ -253,66 +204,19 @@ __global__ void repeated_kernel(const uint64_t *rec, const uint32_t *count, cons
 
 // ---- the host side
 
-// The tiles of a call and where each read's k-mers go.
-struct Plan {
-    uint64_t n_bases = 0, n_kmers = 0;
-    std::vector<uint64_t> kmer_off;
-    std::vector<uint32_t> tile_read, tile_start;
-};
-
 // what all three entry points ask of their sequences and k, before a device is looked for
 int mk_check(size_t n, const uint8_t *bases, const uint64_t *off, uint32_t k, const char *what) {
     if (!off) return jtk_fail(JTK_ERR_INVALID_ARG, "null argument");
     if (k == 0) return jtk_fail(JTK_ERR_INVALID_ARG, "k is 0");
     if (k > MK_MAX_K) return jtk_fail(JTK_ERR_UNSUPPORTED, "k is above 31 (the reference asserts k < 32)");
-    if (off[0] != 0) return jtk_fail(JTK_ERR_INVALID_ARG, std::string(what) + "[0] is not 0");
-    for (size_t i = 0; i < n; i++)
-        if (off[i + 1] < off[i]) return jtk_fail(JTK_ERR_INVALID_ARG, std::string(what) + " decreases");
+    if (int rc = jtk_check_offsets(n, off, what)) return rc;
     if (off[n] && !bases) return jtk_fail(JTK_ERR_INVALID_ARG, "null argument");
     if (off[n] >> 32 || (uint64_t)n >> 32) return jtk_fail(JTK_ERR_UNSUPPORTED, "2^32 bases or sequences, or more: a count would not fit the reference's u32");
     return 0;
 }
 
-void mk_plan(size_t n, const uint64_t *off, uint32_t k, Plan *P) {
-    P->n_bases = off[n];
-    P->kmer_off.assign(n + 1, 0);
-    for (size_t r = 0; r < n; r++) {
-        const uint64_t len = off[r + 1] - off[r];
-        P->kmer_off[r + 1] = P->kmer_off[r] + (len >= k ? len - k + 1 : 0);
-        for (uint64_t s = 0; s < len; s += MK_TILE) {
-            P->tile_read.push_back((uint32_t)r);
-            P->tile_start.push_back((uint32_t)s);
-        }
-    }
-    P->n_kmers = P->kmer_off[n];
-}
-
-// refuses a work area above 80 % of the device's free memory, before anything is allocated
-int mk_fits(uint64_t bytes) {
-    size_t free_b = 0, total_b = 0;
-    JTK_HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    if ((double)bytes > 0.8 * (double)free_b)
-        return jtk_fail(JTK_ERR_ALLOC, "the work area of this call is " + std::to_string(bytes) + " bytes, above 80 % of the device's " +
-                                           std::to_string(free_b) + " free bytes");
-    return 0;
-}
-
-// The reads, their offsets and the tiles on the device.
-struct DevReads {
-    DevArr<uint8_t> bases;
-    DevArr<uint64_t> off, kmer_off;
-    DevArr<uint32_t> tile_read, tile_start;
-    uint32_t n_tiles = 0;
-    static uint64_t bytes(size_t n, const Plan &P) { return P.n_bases + 16 * (uint64_t)(n + 1) + 8 * (uint64_t)P.tile_read.size(); }
-    int upload(size_t n, const uint8_t *h_bases, const uint64_t *h_off, const Plan &P, hipStream_t st) {
-        int rc;
-        if ((rc = bases.upload(h_bases, P.n_bases, st)) || (rc = off.upload(h_off, n + 1, st)) || (rc = kmer_off.upload(P.kmer_off, st)) ||
-            (rc = tile_read.upload(P.tile_read, st)) || (rc = tile_start.upload(P.tile_start, st)))
-            return jtk_fail(rc, "device upload failed");
-        n_tiles = (uint32_t)P.tile_read.size();
-        return 0;
-    }
-};
+// the tiles of a call and where each read's k-mers go: a read shorter than k has tiles too, apply_kernel copies it
+KmerPlan mk_plan(size_t n, const uint64_t *off, uint32_t k) { return jtk_plan_kmers(n, off, k, MK_TILE, KMER_TILE_BASES); }
 
 template <typename Key>
 hipError_t mk_sort(RocTemp &tmp, const Key *in, Key *out, uint64_t n, uint32_t end_bit, hipStream_t st) {
@@ -321,8 +225,8 @@ hipError_t mk_sort(RocTemp &tmp, const Key *in, Key *out, uint64_t n, uint32_t e
 
 template <typename Key>
 int mk_mask(size_t n_reads, const uint8_t *bases, const uint64_t *read_off, uint32_t k, double freq, uint32_t min_count, uint8_t *masked,
-            uint64_t *mask_kmers, uint64_t mask_cap, jtk_mask_report_t *report, const Plan &P) {
-    const uint64_t n = P.n_kmers, half = (n + 1) / 2;
+            uint64_t *mask_kmers, uint64_t mask_cap, jtk_mask_report_t *report, const KmerPlan &P) {
+    const uint64_t n = P.n_kmers, half = (n + 1) / 2, n_bases = read_off[n_reads];
     DevStream s;
     JTK_HIP_TRY(s.create(4));
     DevEvents late;
@@ -330,11 +234,11 @@ int mk_mask(size_t n_reads, const uint8_t *bases, const uint64_t *read_off, uint
     {  // keys twice, rocprim's block, the runs and their counts, the counts again for the percentile; the reads twice
         size_t sort_tmp = 0;
         if (n) JTK_HIP_TRY(rocprim::radix_sort_keys(nullptr, sort_tmp, (const Key *)nullptr, (Key *)nullptr, (size_t)n, 0u, 2 * k, s.st));
-        const uint64_t work = DevReads::bytes(n_reads, P) + P.n_bases + (2 * (n + 1) + n) * sizeof(Key) + sort_tmp + (2 * n + 2) * 4;
-        if (int rc = mk_fits(work)) return rc;
+        const uint64_t work = DevSeqs::bytes(n_reads, read_off, P, true) + n_bases + (2 * (n + 1) + n) * sizeof(Key) + sort_tmp + (2 * n + 2) * 4;
+        if (int rc = jtk_fits(work, "the work area")) return rc;
     }
-    DevReads R;
-    if (int rc = R.upload(n_reads, bases, read_off, P, s.st)) return rc;
+    DevSeqs R;
+    if (int rc = R.upload(n_reads, bases, read_off, P, true, s.st)) return rc;
     // raw: the keys as emitted; once they are sorted, its halves hold the k-mers counted more than once and the mask (each has
     // a count of two or more, so there are at most n / 2 of them)
     DevArr<Key> d_raw, d_sorted, d_uniq;
@@ -352,7 +256,7 @@ int mk_mask(size_t n_reads, const uint8_t *bases, const uint64_t *read_off, uint
     JTK_HIP_TRY(d_verdict.alloc(4));
     JTK_HIP_TRY(d_sel.alloc(3));
     JTK_HIP_TRY(d_lower.alloc(1));
-    JTK_HIP_TRY(d_out.alloc(P.n_bases));
+    JTK_HIP_TRY(d_out.alloc(n_bases));
     JTK_HIP_TRY(d_count.zero(std::max<uint64_t>(n, 1), s.st));  // the entries behind the runs are no k-mer's count
     JTK_HIP_TRY(d_runs.zero(1, s.st));
     JTK_HIP_TRY(d_verdict.zero(4, s.st));
@@ -364,7 +268,7 @@ int mk_mask(size_t n_reads, const uint8_t *bases, const uint64_t *read_off, uint
     size_t h_sel[3] = {0, 0, 0};
     unsigned long long h_lower = 0;
     JTK_HIP_TRY(hipEventRecord(s.ev[0], s.st));
-    if (n) emit_kernel<Key><<<R.n_tiles, MK_THREADS, 0, s.st>>>(R.bases.cget(), R.off.cget(), R.kmer_off.cget(), R.tile_read.cget(), R.tile_start.cget(),
+    if (n) emit_kernel<Key><<<R.n_tiles, MK_THREADS, 0, s.st>>>(R.bases.cget(), R.off.cget(), R.kmer_off.cget(), R.tile_seq.cget(), R.tile_start.cget(),
                                                                k, MK_EVERY, nullptr, 0, d_raw.get(), nullptr);
     JTK_HIP_TRY(hipEventRecord(s.ev[1], s.st));
     if (n) JTK_HIP_TRY(mk_sort<Key>(tmp, d_raw.cget(), d_sorted.get(), n, 2 * k, s.st));
@@ -396,11 +300,11 @@ int mk_mask(size_t n_reads, const uint8_t *bases, const uint64_t *read_off, uint
     }
     JTK_HIP_TRY(hipEventRecord(s.ev[3], s.st));
     if (R.n_tiles)
-        apply_kernel<Key><<<R.n_tiles, MK_THREADS, 0, s.st>>>(R.bases.cget(), R.off.cget(), R.tile_read.cget(), R.tile_start.cget(), k, d_mask,
+        apply_kernel<Key><<<R.n_tiles, MK_THREADS, 0, s.st>>>(R.bases.cget(), R.off.cget(), R.tile_seq.cget(), R.tile_start.cget(), k, d_mask,
                                                               (const unsigned long long *)(d_sel.cget() + 2), d_out.get(), d_lower.get());
     JTK_HIP_TRY(hipEventRecord(late[0], s.st));
-    std::vector<uint8_t> h_out(P.n_bases);
-    if (P.n_bases) JTK_HIP_TRY(d_out.download(h_out.data(), P.n_bases, s.st));
+    std::vector<uint8_t> h_out(n_bases);
+    if (n_bases) JTK_HIP_TRY(d_out.download(h_out.data(), n_bases, s.st));
     JTK_HIP_TRY(d_sel.download(h_sel, 3, s.st));
     JTK_HIP_TRY(d_lower.download(&h_lower, 1, s.st));
     JTK_HIP_TRY(hipStreamSynchronize(s.st));
@@ -418,8 +322,8 @@ int mk_mask(size_t n_reads, const uint8_t *bases, const uint64_t *read_off, uint
     JTK_HIP_TRY(s.elapsed(2, 3, &ms[2]));
     JTK_HIP_TRY(hipEventElapsedTime(&ms[3], s.ev[3], late[0]));
     for (int i = 0; i < 4; i++) g_mask_timing[i] = ms[i];
-    if (P.n_bases) std::memcpy(masked, h_out.data(), P.n_bases);
-    report->n_bases = P.n_bases;
+    if (n_bases) std::memcpy(masked, h_out.data(), n_bases);
+    report->n_bases = n_bases;
     report->n_kmers = n;
     report->n_distinct = h_runs;
     report->n_singleton = h_runs - h_sel[0];
@@ -437,7 +341,7 @@ int mk_mask(size_t n_reads, const uint8_t *bases, const uint64_t *read_off, uint
 
 template <typename Key>
 int mk_repetitive(size_t n_reads, const uint8_t *bases, const uint64_t *read_off, uint32_t k, uint64_t *kmers, uint64_t cap, uint64_t *n_kmers,
-                  const Plan &P) {
+                  const KmerPlan &P) {
     const uint64_t n = P.n_kmers;
     *n_kmers = 0;
     if (!n) return 0;
@@ -446,10 +350,10 @@ int mk_repetitive(size_t n_reads, const uint8_t *bases, const uint64_t *read_off
     {
         size_t sort_tmp = 0;
         JTK_HIP_TRY(rocprim::radix_sort_keys(nullptr, sort_tmp, (const Key *)nullptr, (Key *)nullptr, (size_t)n, 0u, 2 * k, s.st));
-        if (int rc = mk_fits(DevReads::bytes(n_reads, P) + 2 * n * sizeof(Key) + sort_tmp)) return rc;
+        if (int rc = jtk_fits(DevSeqs::bytes(n_reads, read_off, P, true) + 2 * n * sizeof(Key) + sort_tmp, "the work area")) return rc;
     }
-    DevReads R;
-    if (int rc = R.upload(n_reads, bases, read_off, P, s.st)) return rc;
+    DevSeqs R;
+    if (int rc = R.upload(n_reads, bases, read_off, P, true, s.st)) return rc;
     DevArr<Key> d_raw, d_sorted;
     DevArr<unsigned long long> d_cursor;
     DevArr<size_t> d_unique;
@@ -459,7 +363,7 @@ int mk_repetitive(size_t n_reads, const uint8_t *bases, const uint64_t *read_off
     JTK_HIP_TRY(d_cursor.alloc(1));
     JTK_HIP_TRY(d_unique.alloc(1));
     JTK_HIP_TRY(d_cursor.zero(1, s.st));
-    emit_kernel<Key><<<R.n_tiles, MK_THREADS, 0, s.st>>>(R.bases.cget(), R.off.cget(), R.kmer_off.cget(), R.tile_read.cget(), R.tile_start.cget(), k,
+    emit_kernel<Key><<<R.n_tiles, MK_THREADS, 0, s.st>>>(R.bases.cget(), R.off.cget(), R.kmer_off.cget(), R.tile_seq.cget(), R.tile_start.cget(), k,
                                                         MK_LOWER, nullptr, 0, d_raw.get(), d_cursor.get());
     unsigned long long emitted = 0;
     JTK_HIP_TRY(d_cursor.download(&emitted, 1, s.st));
@@ -498,8 +402,7 @@ extern "C" int jtk_lc_mask_repeats(size_t n_reads, const uint8_t *bases, const u
     if ((read_off[n_reads] && !masked) || (mask_cap && !mask_kmers)) return jtk_fail(JTK_ERR_INVALID_ARG, "null argument");
     if (int rc = jtk_require_device(device)) return rc;
     std::memset(report, 0, sizeof(*report));
-    Plan P;
-    mk_plan(n_reads, read_off, k, &P);
+    const KmerPlan P = mk_plan(n_reads, read_off, k);
     return 2 * k <= 32 ? mk_mask<uint32_t>(n_reads, bases, read_off, k, freq, min_count, masked, mask_kmers, mask_cap, report, P)
                        : mk_mask<uint64_t>(n_reads, bases, read_off, k, freq, min_count, masked, mask_kmers, mask_cap, report, P);
 }
@@ -510,8 +413,7 @@ extern "C" int jtk_lc_repetitive_kmers(size_t n_reads, const uint8_t *bases, con
     if (!n_kmers || (cap && !kmers)) return jtk_fail(JTK_ERR_INVALID_ARG, "null argument");
     if (int rc = mk_check(n_reads, bases, read_off, k, "read_off")) return rc;
     if (int rc = jtk_require_device(device)) return rc;
-    Plan P;
-    mk_plan(n_reads, read_off, k, &P);
+    const KmerPlan P = mk_plan(n_reads, read_off, k);
     return 2 * k <= 32 ? mk_repetitive<uint32_t>(n_reads, bases, read_off, k, kmers, cap, n_kmers, P)
                        : mk_repetitive<uint64_t>(n_reads, bases, read_off, k, kmers, cap, n_kmers, P);
 }
@@ -521,12 +423,10 @@ extern "C" int jtk_lc_repetitiveness(size_t n_seqs, const uint8_t *bases, const 
     g_last_error.clear();
     if ((n_kmers && !kmers) || (n_seqs && (!rep_num || !rep_den))) return jtk_fail(JTK_ERR_INVALID_ARG, "null argument");
     if (int rc = mk_check(n_seqs, bases, seq_off, k, "seq_off")) return rc;
-    uint32_t seq_bits = 0;  // of the largest index
-    while (seq_bits < 64 && ((uint64_t)(n_seqs ? n_seqs - 1 : 0) >> seq_bits)) seq_bits++;
+    const uint32_t seq_bits = n_seqs > 1 ? jtk_bits(n_seqs - 1) : 0;  // of the largest index
     if (2 * k + seq_bits > 64) return jtk_fail(JTK_ERR_UNSUPPORTED, "the sequence index does not fit above the k-mer in 64 bits");
     if (int rc = jtk_require_device(device)) return rc;
-    Plan P;
-    mk_plan(n_seqs, seq_off, k, &P);
+    const KmerPlan P = mk_plan(n_seqs, seq_off, k);
     for (size_t r = 0; r < n_seqs; r++) {
         const uint64_t len = seq_off[r + 1] - seq_off[r];
         rep_num[r] = 0;
@@ -551,10 +451,10 @@ extern "C" int jtk_lc_repetitiveness(size_t n_seqs, const uint8_t *bases, const 
     {
         size_t sort_tmp = 0;
         JTK_HIP_TRY(rocprim::radix_sort_keys(nullptr, sort_tmp, (const uint64_t *)nullptr, (uint64_t *)nullptr, (size_t)n, 0u, end_bit, s.st));
-        if (int rc = mk_fits(DevReads::bytes(n_seqs, P) + 3 * n * 8 + n * 4 + sort_tmp + 4 * (uint64_t)n_seqs)) return rc;
+        if (int rc = jtk_fits(DevSeqs::bytes(n_seqs, seq_off, P, true) + 3 * n * 8 + n * 4 + sort_tmp + 4 * (uint64_t)n_seqs, "the work area")) return rc;
     }
-    DevReads R;
-    if (int rc = R.upload(n_seqs, bases, seq_off, P, s.st)) return rc;
+    DevSeqs R;
+    if (int rc = R.upload(n_seqs, bases, seq_off, P, true, s.st)) return rc;
     DevArr<uint64_t> d_raw, d_sorted;
     DevArr<unsigned long long> d_cursor;
     DevArr<uint32_t> d_count, d_runs, d_num;
@@ -567,7 +467,7 @@ extern "C" int jtk_lc_repetitiveness(size_t n_seqs, const uint8_t *bases, const 
     JTK_HIP_TRY(d_num.alloc(n_seqs));
     JTK_HIP_TRY(d_cursor.zero(1, s.st));
     JTK_HIP_TRY(d_num.zero(n_seqs, s.st));
-    emit_kernel<uint64_t><<<R.n_tiles, MK_THREADS, 0, s.st>>>(R.bases.cget(), R.off.cget(), R.kmer_off.cget(), R.tile_read.cget(), R.tile_start.cget(),
+    emit_kernel<uint64_t><<<R.n_tiles, MK_THREADS, 0, s.st>>>(R.bases.cget(), R.off.cget(), R.kmer_off.cget(), R.tile_seq.cget(), R.tile_start.cget(),
                                                              k, MK_MEMBER, d_set.cget(), n_kmers, d_raw.get(), d_cursor.get());
     unsigned long long emitted = 0;
     JTK_HIP_TRY(d_cursor.download(&emitted, 1, s.st));

@@ -210,19 +210,8 @@ uint32_t pg_chunk_of(const jtk_cc_chunk_t *chunks, const std::vector<uint32_t> &
 
 int pg_check_reads(size_t n_reads, const uint64_t *node_off) {
     if (!node_off) return jtk_fail(JTK_ERR_INVALID_ARG, "null argument");
-    if (node_off[0] != 0) return jtk_fail(JTK_ERR_INVALID_ARG, "node_off[0] is not 0");
-    for (size_t r = 0; r < n_reads; r++)
-        if (node_off[r + 1] < node_off[r]) return jtk_fail(JTK_ERR_INVALID_ARG, "node_off decreases");
+    if (int rc = jtk_check_offsets(n_reads, node_off, "node_off")) return rc;
     if (n_reads >= PG_NONE || node_off[n_reads] >= PG_NONE) return jtk_fail(JTK_ERR_UNSUPPORTED, "more than 2^32 - 2 reads or nodes");
-    return 0;
-}
-// offsets of `n` slices: they start at 0, never decrease, and no slice is longer than 2^31 - 1
-int pg_check_offsets(size_t n, const uint64_t *off, const char *what) {
-    if (off[0] != 0) return jtk_fail(JTK_ERR_INVALID_ARG, std::string(what) + "[0] is not 0");
-    for (size_t i = 0; i < n; i++) {
-        if (off[i + 1] < off[i]) return jtk_fail(JTK_ERR_INVALID_ARG, std::string(what) + " decreases");
-        if (off[i + 1] - off[i] > PG_MAX_LEN) return jtk_fail(JTK_ERR_UNSUPPORTED, std::string(what) + ": a slice of 2^31 bytes or more");
-    }
     return 0;
 }
 
@@ -399,9 +388,9 @@ int pg_open(Work &w, size_t n_reads, const uint64_t *node_off, const jtk_cc_node
 int pg_check_sequences(const Work &w, size_t n_chunks, const uint8_t *seq_bases, const uint64_t *seq_off, const uint8_t *ops, const uint64_t *ops_off,
                        const uint8_t *tmpl_bases, const uint64_t *tmpl_off) {
     if (!seq_off || !ops_off || !tmpl_off) return jtk_fail(JTK_ERR_INVALID_ARG, "null argument");
-    if (int rc = pg_check_offsets(w.n_nodes, seq_off, "seq_off")) return rc;
-    if (int rc = pg_check_offsets(w.n_nodes, ops_off, "ops_off")) return rc;
-    if (int rc = pg_check_offsets(n_chunks, tmpl_off, "tmpl_off")) return rc;
+    if (int rc = jtk_check_offsets(w.n_nodes, seq_off, "seq_off", PG_MAX_LEN)) return rc;  // no slice of 2^31 bytes or more
+    if (int rc = jtk_check_offsets(w.n_nodes, ops_off, "ops_off", PG_MAX_LEN)) return rc;
+    if (int rc = jtk_check_offsets(n_chunks, tmpl_off, "tmpl_off", PG_MAX_LEN)) return rc;
     if ((seq_off[w.n_nodes] && !seq_bases) || (ops_off[w.n_nodes] && !ops) || (tmpl_off[n_chunks] && !tmpl_bases))
         return jtk_fail(JTK_ERR_INVALID_ARG, "null argument");
     return 0;

@@ -265,15 +265,6 @@ __global__ void __launch_bounds__(ST_WAVES * 64) settle_kernel(uint32_t n_reads,
     }
 }
 
-int st_check_offsets(size_t n, const uint64_t *off, const char *what, uint64_t max_slice) {
-    if (off[0] != 0) return jtk_fail(JTK_ERR_INVALID_ARG, std::string(what) + "[0] is not 0");
-    for (size_t i = 0; i < n; i++) {
-        if (off[i + 1] < off[i]) return jtk_fail(JTK_ERR_INVALID_ARG, std::string(what) + " decreases");
-        if (off[i + 1] - off[i] > max_slice) return jtk_fail(JTK_ERR_UNSUPPORTED, std::string(what) + ": a slice of 2^31 entries or more");
-    }
-    return 0;
-}
-
 }  // namespace
 
 extern "C" void jtk_lc_debug_settle_timing(double *out) {
@@ -289,12 +280,12 @@ extern "C" int jtk_lc_settle_nodes(size_t n_reads, const uint64_t *node_off, con
         return jtk_fail(JTK_ERR_INVALID_ARG, "mode is none of jtk_settle_mode");
     if (!node_off || (n_reads && (!n_kept || !read_status))) return jtk_fail(JTK_ERR_INVALID_ARG, "null argument");
     if (n_reads > ST_MAX_NODES) return jtk_fail(JTK_ERR_UNSUPPORTED, "2^31 reads or more");
-    if (int rc = st_check_offsets(n_reads, node_off, "node_off", ST_MAX_NODES)) return rc;
+    if (int rc = jtk_check_offsets(n_reads, node_off, "node_off", ST_MAX_NODES)) return rc;
     const uint64_t n = node_off[n_reads];
     if (n > ST_MAX_NODES) return jtk_fail(JTK_ERR_UNSUPPORTED, "2^31 nodes or more");
     if (n && (!nodes || !ops_off || !stats || !order || !keep)) return jtk_fail(JTK_ERR_INVALID_ARG, "null argument");
     if (n) {
-        if (int rc = st_check_offsets(n, ops_off, "ops_off", ST_MAX_NODES)) return rc;
+        if (int rc = jtk_check_offsets(n, ops_off, "ops_off", ST_MAX_NODES)) return rc;
         if (ops_off[n] && !ops) return jtk_fail(JTK_ERR_INVALID_ARG, "null argument");
     }
     if (int rc = jtk_require_device(device)) return rc;

@@ -94,6 +94,10 @@ def _sketch_seqs(k, w, rng):
 SKETCH_CASES = []
 for _k, _w in ((15, 1), (15, 5), (15, 10), (15, 20), (17, 1), (17, 5), (17, 10), (17, 64), (16, 10), (1, 1), (31, 3)):
     SKETCH_CASES.append(dict(name="k%d_w%d" % (_k, _w), k=_k, w=_w, seqs=_sketch_seqs(_k, _w, random.Random(1000 * _k + _w))))
+# The one case that stages all of a tile's span: a middle tile with w - 1 positions of halo on both sides needs a sequence of
+# 2 * TILE + w k-mer positions or more (the longest above has 2 * TILE + 10 at k = 31).  Its last sequence is the long one.
+_rng = random.Random(1000 * 31 + 64)
+SKETCH_CASES.append(dict(name="k31_w64", k=31, w=64, seqs=_sketch_seqs(31, 64, _rng) + [rand_seq(_rng, 3 * TILE + 31)]))
 
 DEFAULTS = dict(k=15, w=10, max_occ=200, max_gap=100, min_seeds=4, skip_self=False)
 

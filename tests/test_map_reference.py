@@ -67,6 +67,17 @@ def test_sketch_against_the_definition_and_the_reverse_complement(k, w):
     assert R.sketch(b"N" * 50, k, w) == [] and R.sketch(b"ACG", 4, w) == []
 
 
+def test_the_full_span_case_stages_a_full_span():
+    """k31_w64: from the lengths alone, a sequence whose middle tile has w - 1 staged positions on both sides (the existing cases
+    have none: their longest have 2,058 positions at k = 31 and 2,072 at (17, 64), the threshold is 2,112); on that sequence
+    the reference agrees with the definition"""
+    case = next(c for c in K.SKETCH_CASES if c["name"] == "k31_w64")
+    k, w, seq = case["k"], case["w"], case["seqs"][-1]
+    assert (k, w, len(seq)) == (31, 64, 3 * K.TILE + 31) and len(case["seqs"]) == 18
+    assert max(len(s) - k + 1 for s in case["seqs"]) == len(seq) - k + 1 >= 2 * K.TILE + w
+    assert R.sketch(seq, k, w) == brute_force(seq, k, w)
+
+
 def test_occurrence_cut_and_skip_self():
     homo = b"A" * 300
     assert [p["n_seeds"] for p in R.map_reads([homo], [homo], max_occ=286)] == [286] and R.map_reads([homo], [homo], max_occ=285) == []
